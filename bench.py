@@ -1,7 +1,14 @@
 """bench.py -- frames/sec of the SECOND forward on synthetic 16k-point KITTI-range clouds (BASELINE.json).
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1 without a launcher: bench.py starts the N ranks itself, launch_plan)
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+                                                             (N > 1 without a launcher: bench.py starts the N ranks itself, launch_plan)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up (W steps), times exactly K steps in one window and prints the result line (`ms_per_step` = the
+window over K).  --full adds everything else: the median of --windows (31) windows and its spread, single-frame latency, with_h2d,
+rooflines and per-stage timings, the other arithmetic, the CPU baseline and the `extra` sub-lines below.  --dump-outputs DIR
+writes what the timed path returned for its last step (forward: boxes, batch_idx, class_idx, scores) as DIR/<name>.npy; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 One step = one pass of the hot path over one batch (bs=1/GPU, configs[1]): device voxelizer + VFE -> 14-layer sparse 3-D conv
 backbone -> .dense() BEV -> dense RPN (MFMA, background tiles skipped) -> proposal stage (top-k, decode, rotated NMS, score
@@ -9,12 +16,12 @@ cut), all hand-written HIP, replayed as one HIP graph (37 kernels) with a single
 capacity-overflow word).  The timed loop cycles through --stream (default 8) DIFFERENT clouds per rank, resident in HBM before
 the timed region.  By default several frames are in flight per GPU (one graph and plan arena per slot, one slot more than
 frames in flight; up to 4, streams and depth picked by measurement before the warm-up -- config.pipeline_tuning); every step
-submits one frame and the timed region completes exactly K of them.  The same graph run one frame at a time is reported as
-single_frame_ms / frames_per_s_one_at_a_time.  Frames are independent, so N GPUs run N replicas on different frames with no
+submits one frame and the timed region completes exactly K of them.  With --full the same graph run one frame at a time is
+reported as single_frame_ms / frames_per_s_one_at_a_time.  Frames are independent, so N GPUs run N replicas on different frames with no
 data-path collective (weak scaling); the only communication is the timing barrier / max-reduce.  Rank 0 prints ONE JSON line.
 Other lines of BASELINE.json: --workload waymo (configs[4]), --mode train (configs[2]), --mode pvrcnn (configs[3]).
 
-Extra objects on that line:
+Extra objects on that line (--full):
   roofline        the dominant sparse kernel (KITTI: spconv_fwd_rows_ring<64,64>, 7 launches/frame; Waymo:
                   spconv_fwd_rows_kouter<64,64>): algorithmic bytes A_min = 4*(N_in*Cin + N_out*Cout + K*Cin*Cout) + 8*R per launch
                    divided by its average duration measured with HIP events over graph-captured repeats on the launch
@@ -110,19 +117,79 @@ def parse(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-launch event timing pass (profiling runs)")
     ap.add_argument("--cpu-frames", type=int, default=4, help="frames of the CPU baseline sample (about 1.4 s each on one core: ~6 s)")
-    ap.add_argument("--windows", type=int, default=31,
+    ap.add_argument("--windows", type=int, default=None,
                     help="forward mode: back-to-back timed windows of --steps steps each (barrier + synchronize on both sides of every "
                          "window, pipeline empty at its start, max over ranks per window); `value` is the MEDIAN window, "
-                         "value_p10 / value_p90 the spread.  The count is cut down so that the windows take at most ~20 s")
+                         "value_p10 / value_p90 the spread.  The count is cut down so that the windows take at most ~20 s.  "
+                         "Default: 31 with --full, else 1 (exactly --steps timed steps)")
     ap.add_argument("--end-to-end", action="store_true",
                     help="--mode pvrcnn: time PV_RCNN.inference(item) from raw points (device voxelizer + sparse CNN + stage-1 head + "
                          "stage 2 + refinement NMS), one frame at a time, instead of stage 2 on resident stage-1 outputs")
     ap.add_argument("--no-h2d", action="store_true", help="skip the with_h2d line (pinned host cloud copied in every step)")
     ap.add_argument("--single-frames", type=int, default=200, help="frames timed one at a time for single_frame_ms (median, p10, p90)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default forward run on one GPU: skip the compact sub-lines of the OTHER BASELINE configurations (`extra`: Waymo-range "
+                    help="--full forward run on one GPU: skip the compact sub-lines of the OTHER BASELINE configurations (`extra`: Waymo-range "
                          "sweep, bs = 8 KITTI batch, plumbing, PV-RCNN stage 2, train step), each a short in-process run of its own mode")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: the median of --windows timed windows with its spread, single-frame "
+                         "latency, with_h2d, rooflines and per-stage timings, the other arithmetic (fast_mode / fp32_script), the CPU "
+                         "baseline and the `extra` sub-lines.  Without it a run sets up, warms up, times exactly --steps steps in one "
+                         "window and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy (float32, or "
+                         "float64 for integer and float64 arrays; at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 31 if args.full else 1
+    if not args.full:  # a plain run measures the headline and nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_fast_mode = args.no_h2d = args.no_extra = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _flatten_outputs(prefix, obj, out):
+    if obj is None:
+        return
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            _flatten_outputs(f"{prefix}_{k}" if prefix else str(k), v, out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _flatten_outputs(f"{prefix}_{i}" if prefix else f"out{i}", v, out)
+    elif isinstance(obj, (torch.Tensor, np.ndarray, float, int, bool, np.number)):
+        out[prefix or "out"] = obj
+
+
+def write_outputs(dirname, outputs):
+    """--dump-outputs: `outputs` (a tensor, or a dict / list / tuple of them) -> dirname/<name>.npy.  Floating arrays are written
+    as float32 (float64 ones as float64), integer and boolean ones as float64 (exact).  Above DUMP_LIMIT_BYTES in all, every
+    array longer than its share keeps a fixed, seeded sample of its rows (indices in increasing order, written beside it)."""
+    flat = {}
+    _flatten_outputs("", outputs, flat)
+    arrays = {}
+    for name, v in flat.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.dtype == np.float64 or a.dtype.kind in "iub":
+            a = a.astype(np.float64)
+        else:
+            a = a.astype(np.float32)
+        arrays[name] = a.reshape(1) if a.ndim == 0 else a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+        for name in list(arrays):
+            a = arrays[name]
+            if a.nbytes > share:
+                row = max(1, a.nbytes // a.shape[0])  # (+ 8 bytes of row index per kept row)
+                keep = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // (row + 8)), replace=False))
+                arrays[name] = np.ascontiguousarray(a[keep])
+                arrays[name + "_sample_rows"] = keep.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def launch_plan(gpus, environ, argv, n_devices, backend=BACKEND, port=None):
@@ -353,6 +420,8 @@ def train_main(args):
     amp = args.train_arith == "bf16" and not args.no_amp
     main = run_arith(amp)
     elapsed, loss, model, native_dense = main["elapsed"], main["loss"], main["model"], main["native_dense"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(loss=np.float32(loss)))
     second = None
     if not args.no_fast_mode:
         del model
@@ -538,14 +607,14 @@ def pvrcnn_main(args):
         graphs = None
         if os.environ.get("V3D_PVRCNN_GRAPH", "1") != "0":  # one captured HIP graph per slot: ~130 eager launches -> one replay
             try:
-                graphs = []
+                graphs, graph_outs = [], []
                 for sl in range(depth):
                     with torch.cuda.stream(slots[sl][2]):
                         step(sl)  # warm-up on the slot's stream (allocator pools, lazily built state)
                     torch.cuda.synchronize()
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, stream=slots[sl][2]):
-                        step(sl)
+                        graph_outs.append(step(sl))
                     graphs.append(g)
             except Exception as e:  # capture is an optimisation of the launch path only
                 print(f"bench: PV-RCNN graph capture unavailable ({type(e).__name__}: {str(e)[:120]}); eager launches", file=sys.stderr)
@@ -579,13 +648,16 @@ def pvrcnn_main(args):
             tuned = dict(depth=len(chosen), us_per_frame={k: round(v * 1e6, 1) for k, v in log.items()})
         n_run = len(run_streams)
 
+        last = [None]
+
         def submit(i):
             sl = i % n_run
             with torch.cuda.stream(run_streams[sl]):
                 if graphs is not None:
                     graphs[sl].replay()
+                    last[0] = graph_outs[sl]
                 else:
-                    step(sl)
+                    last[0] = step(sl)
 
         for i in range(args.warmup):
             submit(i)
@@ -598,6 +670,7 @@ def pvrcnn_main(args):
             enq += time.perf_counter() - e0
         fence()
     elapsed = dist_util.max_over_ranks(time.perf_counter() - t0, world, device=REDUCE_DEVICE)
+    dump = [last[0]]  # what the timed path of `value` returned last (the batched form below replaces it when it is the line)
     # ---- the same frames with the keypoint samplings of the frames in flight BATCHED into one launch (round 6).  Farthest-point sampling
     # is 2 048 dependent steps on ONE compute unit per cloud (2.48 ms of a 3.65 ms frame) and takes a batch: one launch samples the
     # D frames of the next round, a workgroup each, on a stream of its own, while the rest of stage 2 of the CURRENT round's D frames
@@ -628,7 +701,7 @@ def pvrcnn_main(args):
                     return model.refinement_layer(None, pooled, props)
                 cap = torch.cuda.Stream()
                 cap.wait_stream(torch.cuda.current_stream())
-                gA, gB = [], [[None, None] for _ in range(D)]
+                gA, gB, gB_out = [], [[None, None] for _ in range(D)], [[None, None] for _ in range(D)]
                 with torch.cuda.stream(cap):
                     for buf in range(2):
                         kp[buf].copy_(model.sample_keypoints(pts_all))
@@ -642,7 +715,7 @@ def pvrcnn_main(args):
                             torch.cuda.synchronize()
                             g = torch.cuda.CUDAGraph()
                             with torch.cuda.graph(g, stream=cap):
-                                rest(sl, buf)
+                                gB_out[sl][buf] = rest(sl, buf)
                             gB[sl][buf] = g
                 torch.cuda.synchronize()
                 eA = [torch.cuda.Event() for _ in range(2)]
@@ -685,11 +758,14 @@ def pvrcnn_main(args):
                 rounds(n_rounds, s_a, s_r)
                 fence()
                 el_b = dist_util.max_over_ranks(time.perf_counter() - c0, world, device=REDUCE_DEVICE)
+                dump[0] = gB_out[D - 1][(n_rounds - 1) % 2]
                 batched = dict(value=world * bs * n_rounds * D / el_b, ms_per_step=1e3 * el_b / (n_rounds * D), frames_per_round=D,
                                rounds=n_rounds, streams=len(chosen), pipeline_tuning={k: round(v * 1e6, 1) for k, v in log.items()})
         except Exception as e:  # (the per-frame form above stays the line)
             print(f"bench: batched keypoint sampling unavailable ({type(e).__name__}: {str(e)[:160]})", file=sys.stderr)
             batched = None
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dump[0])
     roofline = cpu_baseline = None
     if rank == 0 and not args.no_roofline:
         roofline = fps_roofline(model, slots[0][0]["points"])
@@ -783,6 +859,11 @@ def plumbing_main(args):
     elapsed = dist_util.max_over_ranks(time.perf_counter() - t0, world, device=REDUCE_DEVICE)
     m_vox = int(outs[0][3].item())
     n_box = int(boxes[0].shape[0])
+    if args.dump_outputs and rank == 0:
+        coords, occ, mean, n_vox, mask = outs[(args.steps - 1) % n_stream]
+        n_last = int(n_vox.item())
+        write_outputs(args.dump_outputs, dict(coords=coords[:n_last], occupancy=occ[:n_last], mean=mean[:n_last], n_voxels=n_vox,
+                                              in_box_mask=mask))
     roofline = cpu_baseline = None
     if rank == 0 and not args.no_roofline:
         def graph_us(fn, rep=20):
@@ -975,6 +1056,8 @@ def pvrcnn_end_to_end(args, model, cfg, rank, world):
         fence()
         timings[prefetch] = dist_util.max_over_ranks(time.perf_counter() - t0, world, device=REDUCE_DEVICE)
     elapsed = timings["in_flight"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(zip(("boxes", "batch_idx", "class_idx", "scores"), out)))
     if rank == 0:
         print(json.dumps(dict(
             metric="frames/sec PV-RCNN inference end to end, 16k-pt KITTI cloud", value=world * bs * args.steps / elapsed,
@@ -1106,6 +1189,8 @@ EXTRA_RUNS = [  # (key, what, argv of a short run of that mode)
     ("plumbing", "BASELINE configs[0]: voxelize + points_in_boxes, one 16 k-pt cloud", ["--mode", "plumbing", "--windows", "5", "--steps", "100"]),
     ("train", "BASELINE configs[2]: SECOND train step bf16, 8 frames per GPU", ["--mode", "train", "--steps", "6", "--warmup", "2"]),
 ]
+# every sub-line is a --full run of its mode (the roofline and single-frame fields are read from it) without the side lines
+EXTRA_FLAGS = ["--full", "--no-cpu-baseline", "--no-fast-mode", "--no-h2d", "--no-extra", "--watchdog", "240"]
 
 
 def run_extras():
@@ -1119,7 +1204,7 @@ def run_extras():
     for key, what, argv in EXTRA_RUNS:
         t0 = time.perf_counter()
         try:
-            cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--no-fast-mode", "--no-h2d", "--no-extra", "--watchdog", "240"]
+            cmd = [sys.executable, os.path.abspath(__file__)] + argv + EXTRA_FLAGS
             res = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             lines = [ln for ln in res.stdout.strip().splitlines() if ln.startswith("{")]
             if res.returncode != 0 or not lines:
@@ -1266,6 +1351,8 @@ def forward_main(args):
     n_win = max(5, min(args.windows, int(20.0 / max(first[0], 1e-6)))) if args.windows > 1 else 1
     rest_t, out2 = windows(stream, args.steps, n_win - 1) if n_win > 1 else ([], None)
     out = out2 if out2 is not None else out
+    if args.dump_outputs and rank == 0:  # before anything else reuses the slots' static output buffers
+        write_outputs(args.dump_outputs, dict(zip(("boxes", "batch_idx", "class_idx", "scores"), out)))
     win_t = np.sort(np.asarray(first + rest_t))
     elapsed = float(np.median(win_t))
     frames = world * args.steps * args.batch
@@ -1286,7 +1373,7 @@ def forward_main(args):
     # one frame at a time through the same captured graph (latency view of the same work), not part of `value`: every frame timed on
     # its own (host clock around submit + collect, the frame's 8-byte read is the synchronisation), median / p10 / p90 of >= 200
     single_ms, single_stats = None, None
-    if args.path == "graph":
+    if args.path == "graph" and args.full:
         g1 = graphed.slots[0] if pipelined else graphed
         with torch.no_grad():
             for i in range(10):

@@ -27,7 +27,12 @@ def golden_geom():
 
 @pytest.fixture(scope="session")
 def golden_core():
-    return np.load(os.path.join(GOLDEN, "core.npz"), allow_pickle=True)
+    """core.npz and its parts (tests/golden/npz_parts.py: no committed file above 1 MiB)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("v3d_npz_parts", os.path.join(GOLDEN, "npz_parts.py"))
+    parts = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(parts)
+    return parts.load_parts(os.path.join(GOLDEN, "core"))
 
 
 @pytest.fixture(scope="session")

@@ -310,7 +310,9 @@ def main():
     c["pta_M_reg_idx"] = mr.nonzero().numpy().astype(np.int32)
     c["pta_G_reg_vals"] = item["G_reg"][mr].numpy()
     c["pta_shapes"] = np.array([list(item["G_cls"].shape) + [0], list(item["G_reg"].shape)], dtype=object).astype(str)
-    np.savez_compressed(os.path.join(HERE, "core.npz"), **c)
+    sys.path.insert(0, HERE)
+    from npz_parts import save_parts
+    save_parts(os.path.join(HERE, "core"), c)  # core.npz + core.part*.npz (no committed file above 1 MiB)
     print("core.npz", {k: v.shape for k, v in c.items() if hasattr(v, "shape") and v.size > 64})
     print("detections in pl golden:", c["pl_boxes"].shape, "positives in pta:", c["pta_M_reg_idx"].shape)
 

@@ -74,8 +74,9 @@ def test_extra_sub_lines_are_valid_short_runs_of_the_other_configurations(bench)
     keys = [k for k, _, _ in bench.EXTRA_RUNS]
     assert {"waymo", "plumbing", "pvrcnn_stage2"} <= set(keys) and len(keys) == len(set(keys))
     for key, what, argv in bench.EXTRA_RUNS:
-        a = bench.parse(argv + ["--no-cpu-baseline", "--no-fast-mode", "--no-h2d", "--no-extra", "--watchdog", "240"])
+        a = bench.parse(argv + bench.EXTRA_FLAGS)
         assert a.mode in ("forward", "train", "pvrcnn", "plumbing") and a.no_extra and a.no_cpu_baseline
+        assert a.full and not a.no_roofline  # the sub-line reads the roofline and single-frame fields of its run
         assert a.steps <= 100 and a.gpus == 1, key
         assert "configs[" in what or "batch of 8" in what
 
@@ -90,3 +91,41 @@ def test_counter_summaries_attach_to_the_roofline_objects(bench):
     assert bench.mfma_busy_from_profiles("kitti", "conv2d_bf16x3_tile2d_kernel", None) is None
     k = bench.mfma_busy_from_profiles("waymo", "spconv_fwd_rows_kouter<64, 64", 47.0)
     assert k is not None and 20.0 < k["sustained_floor_us"] < 30.0  # 2 600 MFMAs per SIMD at 10 ns
+
+
+def test_plain_run_times_exactly_steps_and_full_keeps_the_rest(bench):
+    """A plain run is the headline alone: one window of exactly --steps steps, no side measurements; --full restores them."""
+    a = bench.parse(["--gpus", "1", "--steps", "40", "--warmup", "4"])
+    assert not a.full and a.windows == 1 and a.steps == 40 and a.warmup == 4
+    assert a.no_cpu_baseline and a.no_roofline and a.no_fast_mode and a.no_h2d and a.no_extra
+    f = bench.parse(["--full"])
+    assert f.full and f.windows == 31
+    assert not (f.no_cpu_baseline or f.no_roofline or f.no_fast_mode or f.no_h2d or f.no_extra)
+    assert bench.parse(["--full", "--windows", "5", "--no-h2d"]).windows == 5 and bench.parse(["--full", "--no-h2d"]).no_h2d
+    assert bench.parse(["--dump-outputs", "out"]).dump_outputs == "out" and bench.parse([]).dump_outputs is None
+
+
+def test_dump_outputs_are_float_npy_files_within_the_limit(bench, tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per returned array, float32 (float64 for integers and float64), names from the caller's keys;
+    above the limit a fixed, seeded sample of rows is kept, with its row indices, the same on every run."""
+    import numpy as np
+    torch = bench.torch
+    names = bench.write_outputs(str(tmp_path / "a"), dict(boxes=torch.arange(14, dtype=torch.float32).reshape(2, 7),
+                                                          batch_idx=torch.tensor([0, 3]), keep=torch.tensor([True, False]),
+                                                          n=torch.tensor(5, dtype=torch.int32), pair=[torch.ones(3, dtype=torch.float64), None]))
+    assert names == ["batch_idx", "boxes", "keep", "n", "pair_0"]
+    ld = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert ld["boxes"].dtype == np.float32 and ld["boxes"].shape == (2, 7) and ld["boxes"][1, 6] == 13
+    assert ld["batch_idx"].dtype == np.float64 and list(ld["batch_idx"]) == [0, 3] and list(ld["keep"]) == [1, 0]
+    assert ld["n"].shape == (1,) and ld["n"][0] == 5 and ld["pair_0"].dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    big = torch.arange(4000, dtype=torch.float32).reshape(1000, 4)
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), dict(big=big, small=torch.zeros(3)))
+    total = sum(np.load(p).nbytes for p in (tmp_path / "b").glob("*.npy"))
+    assert total <= 4096
+    rows = np.load(tmp_path / "b" / "big_sample_rows.npy").astype(np.int64)
+    got = np.load(tmp_path / "b" / "big.npy")
+    assert len(rows) > 0 and np.all(np.diff(rows) > 0) and np.array_equal(got, big.numpy()[rows])
+    assert np.array_equal(got, np.load(tmp_path / "c" / "big.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), np.zeros(3, np.float32))

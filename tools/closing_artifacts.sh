@@ -32,25 +32,25 @@ seq() {  # name, bench args...: the one-frame kernel sequence timeline
   python tools/trace_sequence.py $(find /tmp/prof_$n -name "*kernel_trace.csv" | head -1) 100 > $O/$n.txt 2>&1
   rm -rf /tmp/prof_$n
 }
-Q="--no-cpu-baseline --no-extra"
-python bench.py > $O/bench_driver_form.json 2> $O/bench_driver_form.err                      # exactly what the driver runs
-python bench.py --steps 300 --warmup 30 --no-extra > $O/bench.json 2> $O/bench.err
+Q="--full --no-cpu-baseline --no-extra"
+python bench.py --full > $O/bench_driver_form.json 2> $O/bench_driver_form.err               # the default command with every side line and `extra`
+python bench.py --full --steps 300 --warmup 30 --no-extra > $O/bench.json 2> $O/bench.err
 stats kernel_stats --steps 200 --warmup 20 $Q --no-fast-mode --no-h2d
 stats one_frame_at_a_time_kernel_stats --pipeline 1 --steps 200 --warmup 20 $Q --no-fast-mode --no-h2d --no-roofline
 seq trace_sequence --pipeline 1 --steps 300 --warmup 20 $Q --no-roofline --no-h2d --no-fast-mode --windows 1
 rm -rf /tmp/prof_o; rocprofv3 --kernel-trace --output-format csv -d /tmp/prof_o -- python bench.py --steps 200 --warmup 20 $Q --no-roofline --no-fast-mode --no-h2d > /dev/null 2> /tmp/prof_o.err
 python tools/trace_overlap.py $(find /tmp/prof_o -name "*kernel_trace.csv" | head -1) > $O/trace_overlap.txt 2>&1; rm -rf /tmp/prof_o
-python bench.py --workload waymo --no-extra > $O/waymo.json 2> $O/waymo.err
+python bench.py --full --workload waymo --no-extra > $O/waymo.json 2> $O/waymo.err
 stats waymo_kernel_stats --workload waymo --steps 40 --warmup 10 $Q --no-fast-mode --no-h2d
 stats waymo_one_frame_at_a_time_kernel_stats --workload waymo --pipeline 1 --steps 40 --warmup 10 $Q --no-fast-mode --no-h2d --no-roofline
 seq waymo_trace_sequence --workload waymo --pipeline 1 --steps 60 --warmup 10 $Q --no-roofline --no-h2d --no-fast-mode --windows 1
-python bench.py --mode train --steps 20 --warmup 5 > $O/train.json 2> $O/train.err
-stats train_kernel_stats --mode train --steps 10 --warmup 3 --no-cpu-baseline
-python bench.py --mode pvrcnn --steps 20 --warmup 5 > $O/pvrcnn.json 2> $O/pvrcnn.err
-stats pvrcnn_stage2_kernel_stats --mode pvrcnn --steps 10 --warmup 3 --no-cpu-baseline
-python bench.py --mode pvrcnn --end-to-end --steps 20 --warmup 5 > $O/pvrcnn_e2e.json 2> $O/pvrcnn_e2e.err
-stats pvrcnn_e2e_kernel_stats --mode pvrcnn --end-to-end --steps 10 --warmup 3 --no-cpu-baseline
-python bench.py --mode plumbing > $O/plumbing.json 2> $O/plumbing.err
+python bench.py --full --mode train --steps 20 --warmup 5 > $O/train.json 2> $O/train.err
+stats train_kernel_stats --full --mode train --steps 10 --warmup 3 --no-cpu-baseline
+python bench.py --full --mode pvrcnn --steps 20 --warmup 5 > $O/pvrcnn.json 2> $O/pvrcnn.err
+stats pvrcnn_stage2_kernel_stats --full --mode pvrcnn --steps 10 --warmup 3 --no-cpu-baseline
+python bench.py --full --mode pvrcnn --end-to-end --steps 20 --warmup 5 > $O/pvrcnn_e2e.json 2> $O/pvrcnn_e2e.err
+stats pvrcnn_e2e_kernel_stats --full --mode pvrcnn --end-to-end --steps 10 --warmup 3 --no-cpu-baseline
+python bench.py --full --mode plumbing > $O/plumbing.json 2> $O/plumbing.err
 bash tools/pmc_traffic.sh kitti $ROUND > $O/pmc_traffic.log 2>&1
 bash tools/pmc_traffic.sh waymo $ROUND > $O/pmc_traffic_waymo.log 2>&1
 for f in bench_driver_form bench waymo train pvrcnn pvrcnn_e2e plumbing; do cut -c1-260 $O/$f.json; echo; done

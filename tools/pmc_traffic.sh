@@ -6,8 +6,8 @@
 set -u
 WL=${1:-kitti}
 TAG=${2:-r03}
-EXTRA=""
-[ "$WL" = "waymo" ] && EXTRA="--workload waymo"
+EXTRA="--full"  # the counters cover the roofline pass too (isolated launches of the dominant kernels)
+[ "$WL" = "waymo" ] && EXTRA="$EXTRA --workload waymo"
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$R/gpurun_out"
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
