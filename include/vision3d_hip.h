@@ -665,6 +665,59 @@ int v3d_dense_train_backward_split(const void* bev_hi, const void* bev_lo, const
                                    const v3d_dense_train_layer* layers, int n_layers, const float* head_weight, int O, void* arena,
                                    float* dhead_weight, float* dhead_bias, void* dbev_hi, void* dbev_lo, v3d_stream_t stream);
 
+/* ---- KITTI BEV / 3-D average precision (vision3d_amd/evaluation/kitti.py; the protocol is written out in its docstring).
+ * The upstream project has no evaluator.  All frames form one ragged batch: rows of frame f are [off[f], off[f+1]) of the
+ * concatenated arrays, off (n_frames + 1) i32 on the device; ov_off (n_frames + 1) i64 = running sum of n_dt * n_gt.
+ *   gt (G, 7) f32 = rectified-camera (x, y_bottom, z, h, w, l, ry); gt_meta (G, 2) i32 = (class code, flags): bit d set =
+ *   "ignored at difficulty d" (occlusion / truncation / 2-D height rule, evaluated by the caller);
+ *   dt (D, 8) f32 = the same 7 columns + score; dt_meta (D, 2) i32 = (class code, flags): bit d set = 2-D height below
+ *   MIN_HEIGHT[d].  Class codes: V3D_KITTI_CODE_*.
+ * A combo is one (class, difficulty, metric, minimum overlap); up to V3D_KITTI_MAX_COMBOS of them, on the HOST.
+ * max_dt / max_gt (host) are the largest per-frame counts: beyond V3D_KITTI_MAX_DT / V3D_KITTI_MAX_GT every entry point
+ * returns V3D_EUNSUPPORTED.  Integer counters only: results are deterministic.  No host synchronisation. */
+#define V3D_KITTI_MAX_DT 1024
+#define V3D_KITTI_MAX_GT 256
+#define V3D_KITTI_MAX_COMBOS 64
+#define V3D_KITTI_SAMPLE_PTS 41
+#define V3D_KITTI_CODE_CAR 0
+#define V3D_KITTI_CODE_PEDESTRIAN 1
+#define V3D_KITTI_CODE_CYCLIST 2
+#define V3D_KITTI_CODE_VAN 3
+#define V3D_KITTI_CODE_PERSON_SITTING 4
+#define V3D_KITTI_CODE_OTHER 5 /* DontCare, Misc, Truck, Tram, ... */
+typedef struct {
+  int32_t cls;         /* class code evaluated */
+  int32_t neighbour;   /* its neighbour class code (Van for Car, Person_sitting for Pedestrian), -1: none */
+  int32_t difficulty;  /* 0 easy, 1 moderate, 2 hard: the flag bit read */
+  int32_t metric;      /* 0 BEV, 1 3-D */
+  float min_overlap;   /* a pair counts when overlap > min_overlap */
+} v3d_kitti_combo;
+/* ov_bev, ov_3d (sum n_dt * n_gt) f32: BEV and 3-D IoU, frame-major, row = detection, column = ground truth, both from ONE
+ * polygon clip per pair (rotated_iou.h).  BEV in the camera's (x, z) plane, extent l along (cos ry, -sin ry). */
+int v3d_kitti_eval_overlaps(const float* gt, const int32_t* gt_off, const float* dt, const int32_t* dt_off, const int64_t* ov_off,
+                            int n_frames, int max_dt, int max_gt, float* ov_bev, float* ov_3d, v3d_stream_t stream);
+/* Pass 1 (greedy assignment without false positives): appends every true positive's score to its combo's row of tp_scores
+ * (n_combos, capacity) at tp_count[combo] (atomic cursor; order arbitrary, capacity >= G suffices) and adds the combo's valid
+ * ground truths to n_valid[combo].  tp_count and n_valid must be zero on entry. */
+int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta, const int32_t* dt_off,
+                         const int64_t* ov_off, const float* ov_bev, const float* ov_3d, int n_frames, int max_dt, int max_gt,
+                         const v3d_kitti_combo* combos_host, int n_combos, int capacity, int32_t* tp_count, float* tp_scores,
+                         int32_t* n_valid, v3d_stream_t stream);
+/* Score thresholds of the 41 recall positions, one lane per combo, in double: sorted_scores (n_combos, capacity) = each row of
+ * tp_scores sorted in DESCENDING order (entries past tp_count[combo] are not read).  thresholds (n_combos, 41) f32, n_thresholds
+ * (n_combos) i32. */
+int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacity, const int32_t* tp_count, const int32_t* n_valid,
+                              int n_combos, float* thresholds, int32_t* n_thresholds, v3d_stream_t stream);
+/* Pass 2: one lane per threshold runs the greedy assignment with false positives; counts (n_combos, 41, 3) i32 += (tp, fp, fn).
+ * counts must be zero on entry. */
+int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta, const int32_t* dt_off,
+                         const int64_t* ov_off, const float* ov_bev, const float* ov_3d, int n_frames, int max_dt, int max_gt,
+                         const v3d_kitti_combo* combos_host, int n_combos, const float* thresholds, const int32_t* n_thresholds,
+                         int32_t* counts, v3d_stream_t stream);
+/* Precision per threshold, its running maximum from the right, and ap (n_combos, 2) f64 = (AP_R11, AP_R40) in percent, summed in
+ * the order of the definition (bit-reproducible). */
+int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresholds, int n_combos, double* ap, v3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

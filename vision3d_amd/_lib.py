@@ -137,6 +137,11 @@ _SIGNATURES = {
     "v3d_dense_train_forward_split": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "v3d_dense_train_backward_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_dense_train_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "v3d_kitti_eval_overlaps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "v3d_kitti_eval_pass1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "v3d_kitti_eval_thresholds": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "v3d_kitti_eval_pass2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "v3d_kitti_eval_ap": (_i, [_vp, _vp, _i, _vp, _vp]),
 }
 
 
@@ -174,6 +179,12 @@ class DenseTrainLayer(C.Structure):
     _fields_ = [("weight", _vp), ("gamma", _vp), ("beta", _vp), ("running_mean", _vp), ("running_var", _vp),
                 ("num_batches_tracked", _vp), ("eps", C.c_float), ("momentum", C.c_float), ("ksize", C.c_int32),
                 ("grad_weight", _vp), ("grad_gamma", _vp), ("grad_beta", _vp)]
+
+
+class KittiCombo(C.Structure):
+    """v3d_kitti_combo: one (class, difficulty, metric, minimum overlap) of the KITTI evaluation."""
+    _fields_ = [("cls", C.c_int32), ("neighbour", C.c_int32), ("difficulty", C.c_int32), ("metric", C.c_int32),
+                ("min_overlap", C.c_float)]
 
 
 _lib = None

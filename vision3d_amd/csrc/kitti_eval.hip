@@ -1,0 +1,342 @@
+// kitti_eval.hip -- KITTI BEV / 3-D average precision on the device (vision3d_amd/evaluation/kitti.py states the protocol).
+//
+// All frames go in one ragged batch (include/vision3d_hip.h "KITTI BEV / 3-D average precision"); five launches whatever the
+// frame count, no host reads in between:
+//   1. overlaps    one workgroup per (frame, chunk of 256 detection rows): the frame's ground truths are prepped into LDS once,
+//                  each lane preps its detection once and clips it against every ground truth with the rotated-IoU core
+//                  (rotated_iou.h, clipper work arrays in per-wave LDS slabs); BEV and 3-D IoU come from the same intersection;
+//   2. pass 1      one wave per (frame, combo): ground truths in file order, lanes split the detection scan, a wave argmax
+//                  (score, then earliest index) picks the match; true-positive scores are appended through an atomic cursor;
+//   3. thresholds  one lane per combo walks its descending TP scores in double (the 41-point recall sampling);
+//   4. pass 2      one wave per (frame, combo), one lane per threshold: each lane runs its own greedy assignment with an
+//                  "assigned" bitmask in LDS and adds integer (tp, fp, fn) with global atomics (order-free, deterministic);
+//   5. ap          one lane per combo: precision, its running maximum from the right, R11 / R40 sums in definition order.
+// Limits: 1 024 detections (16 bitmask words per lane in pass 2, 16 register bits per lane in pass 1) and 256 ground truths
+// (one LDS slot per thread in stage 1) per frame.
+#include "v3d_common.h"
+#include "rotated_iou.h"
+
+using v3d::BoxPrep;
+
+#define KE_NT V3D_KITTI_SAMPLE_PTS
+#define KE_WORDS (V3D_KITTI_MAX_DT / 64)
+
+struct KeCombos {
+  v3d_kitti_combo c[V3D_KITTI_MAX_COMBOS];
+};
+
+// A rectified-camera box (x, y_bottom, z, h, w, l, ry): the BEV rectangle in the (x, z) plane -- the core's extent `w` (along
+// its heading (cos a, sin a)) is the box length l, its angle a = -ry turns the heading to (cos ry, -sin ry) -- plus the
+// vertical extent [y_bottom - h, y_bottom] (y points down) and the volume.
+struct CamPrep {
+  BoxPrep bev;
+  float ytop, ybot, vol;
+};
+__device__ __forceinline__ CamPrep prep_cam(const float* b) {
+  const float bev[5] = {b[0], b[2], b[5], b[4], -b[6] * 57.29577951308232f};
+  CamPrep r;
+  r.bev = v3d::prep_box(bev);
+  r.ybot = b[1];
+  r.ytop = b[1] - b[3];
+  r.vol = b[5] * b[4] * b[3];
+  return r;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_overlaps_kernel(const float* __restrict__ gt, const int* __restrict__ gt_off,
+                                                                   const float* __restrict__ dt, const int* __restrict__ dt_off,
+                                                                   const int64_t* __restrict__ ov_off, float* __restrict__ ov_bev,
+                                                                   float* __restrict__ ov_3d) {
+  __shared__ CamPrep gts[V3D_KITTI_MAX_GT];
+  __shared__ v3d::P2 clip_pts[V3D_BLOCK / V3D_WAVE][24 * 64];  // the clipper's work arrays: LDS, not scratch (rotated_iou.h)
+  __shared__ float clip_dist[V3D_BLOCK / V3D_WAVE][24 * 64];
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng <= 0 || nd <= 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;  // (block-uniform)
+  if ((int)threadIdx.x < ng) gts[threadIdx.x] = prep_cam(gt + 7 * (size_t)(g0 + threadIdx.x));
+  __syncthreads();
+  const int j = blockIdx.y * V3D_BLOCK + threadIdx.x;
+  if (j >= nd) return;
+  const CamPrep d = prep_cam(dt + 8 * (size_t)(d0 + j));
+  v3d::P2* pts = clip_pts[threadIdx.x >> 6] + (threadIdx.x & 63);
+  float* dist = clip_dist[threadIdx.x >> 6] + (threadIdx.x & 63);
+  const size_t row = (size_t)ov_off[f] + (size_t)j * ng;
+  for (int i = 0; i < ng; i++) {
+    const CamPrep& g = gts[i];
+    float bev = 0.f, iou3 = 0.f;
+    if (v3d::iou_needs_clip(d.bev, g.bev)) {
+      const float inter = v3d::inter_prepped_lds(d.bev, g.bev, pts, dist);
+      bev = inter / (d.bev.area + g.bev.area - inter);
+      const float oh = fmaxf(fminf(d.ybot, g.ybot) - fmaxf(d.ytop, g.ytop), 0.f);
+      const float inter3 = inter * oh;
+      const float den = d.vol + g.vol - inter3;
+      iou3 = den > 0.f ? inter3 / den : 0.f;
+    }
+    ov_bev[row + i] = bev;
+    ov_3d[row + i] = iou3;
+  }
+}
+
+// ignored_gt: 0 counted, 1 ignored (neighbour class, or the class outside the difficulty), -1 not part of the combo
+__device__ __forceinline__ int ignored_gt(const int* meta, const v3d_kitti_combo& c) {
+  const int code = meta[0];
+  const bool ign = (meta[1] >> c.difficulty) & 1;
+  if (code == c.cls) return ign ? 1 : 0;
+  return code == c.neighbour ? 1 : -1;
+}
+// ignored_dt: 1 too short (first, whatever the class), 0 the class, -1 another class
+__device__ __forceinline__ int ignored_dt(const int* meta, const v3d_kitti_combo& c) {
+  if ((meta[1] >> c.difficulty) & 1) return 1;
+  return meta[0] == c.cls ? 0 : -1;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass1_kernel(const int* __restrict__ gt_meta, const int* __restrict__ gt_off,
+                                                                const float* __restrict__ dt, const int* __restrict__ dt_meta,
+                                                                const int* __restrict__ dt_off, const int64_t* __restrict__ ov_off,
+                                                                const float* __restrict__ ov_bev, const float* __restrict__ ov_3d,
+                                                                KeCombos combos, int n_combos, int capacity,
+                                                                int* __restrict__ tp_count, float* __restrict__ tp_scores,
+                                                                int* __restrict__ n_valid) {
+  const int lane = threadIdx.x & 63;
+  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
+  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
+  const v3d_kitti_combo c = combos.c[combo];
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng <= 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
+  const float* ov = (c.metric ? ov_3d : ov_bev) + ov_off[f];
+  // this lane's detections j = lane + 64 q: "in the scan" (ignored_dt != -1) and "assigned" as bits q
+  const int nq = (nd + 63) >> 6;
+  unsigned live = 0u, assigned = 0u;
+  for (int q = 0; q < nq; q++) {
+    const int j = lane + 64 * q;
+    if (j < nd && ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != -1) live |= 1u << q;
+  }
+  int valid = 0;
+  for (int i = 0; i < ng; i++) {
+    const int ig = ignored_gt(gt_meta + 2 * (size_t)(g0 + i), c);
+    if (ig == -1) continue;
+    valid += ig == 0;
+    float best_s = -INFINITY;
+    int best_j = 0x7fffffff;
+    for (int q = 0; q < nq; q++) {
+      if (!(((live & ~assigned) >> q) & 1u)) continue;
+      const int j = lane + 64 * q;
+      if (!(ov[(size_t)j * ng + i] > c.min_overlap)) continue;
+      const float s = dt[8 * (size_t)(d0 + j) + 7];
+      if (best_j == 0x7fffffff || s > best_s) {  // q ascends: ties keep the earlier detection
+        best_s = s;
+        best_j = j;
+      }
+    }
+    for (int m = 32; m >= 1; m >>= 1) {  // wave argmax: higher score, then lower index
+      const float os = __shfl_xor(best_s, m, 64);
+      const int oj = __shfl_xor(best_j, m, 64);
+      if (oj != 0x7fffffff && (best_j == 0x7fffffff || os > best_s || (os == best_s && oj < best_j))) {
+        best_s = os;
+        best_j = oj;
+      }
+    }
+    if (best_j == 0x7fffffff) continue;  // (a false negative when ig == 0: pass 2 counts those)
+    if ((best_j & 63) == lane) assigned |= 1u << (best_j >> 6);
+    if (ig == 0 && ignored_dt(dt_meta + 2 * (size_t)(d0 + best_j), c) == 0 && lane == 0) {
+      const int pos = atomicAdd(tp_count + combo, 1);
+      if (pos < capacity) tp_scores[(size_t)combo * capacity + pos] = best_s;
+    }
+  }
+  if (lane == 0 && valid) atomicAdd(n_valid + combo, valid);
+}
+
+__global__ __launch_bounds__(V3D_WAVE) void kitti_thresholds_kernel(const float* __restrict__ sorted, int capacity,
+                                                                    const int* __restrict__ tp_count, const int* __restrict__ n_valid,
+                                                                    int n_combos, float* __restrict__ thresholds,
+                                                                    int* __restrict__ n_thresholds) {
+  const int combo = threadIdx.x;
+  if (combo >= n_combos) return;
+  const int n = min(tp_count[combo], capacity), ngt = n_valid[combo];
+  const float* s = sorted + (size_t)combo * capacity;
+  int k = 0;
+  if (ngt > 0) {
+    double current = 0.0;
+    for (int i = 0; i < n && k < KE_NT; i++) {
+      const double l = (double)(i + 1) / ngt;
+      const double r = i < n - 1 ? (double)(i + 2) / ngt : l;
+      if ((r - current) < (current - l) && i < n - 1) continue;
+      thresholds[combo * KE_NT + k++] = s[i];
+      current += 1.0 / (KE_NT - 1.0);
+    }
+  }
+  n_thresholds[combo] = k;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(const int* __restrict__ gt_meta, const int* __restrict__ gt_off,
+                                                                const float* __restrict__ dt, const int* __restrict__ dt_meta,
+                                                                const int* __restrict__ dt_off, const int64_t* __restrict__ ov_off,
+                                                                const float* __restrict__ ov_bev, const float* __restrict__ ov_3d,
+                                                                KeCombos combos, int n_combos, const float* __restrict__ thresholds,
+                                                                const int* __restrict__ n_thresholds, int* __restrict__ counts) {
+  __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
+  const int lane = threadIdx.x & 63;
+  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
+  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
+  const v3d_kitti_combo c = combos.c[combo];
+  const int nt = n_thresholds[combo];
+  if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng < 0 || nd < 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
+  const float thresh = thresholds[combo * KE_NT + lane];
+  unsigned long long* assigned = assigned_lds[threadIdx.x >> 6] + lane;
+  const int nw = (nd + 63) >> 6;
+  for (int w = 0; w < nw; w++) assigned[w * 64] = 0ull;
+  const float* ov = (c.metric ? ov_3d : ov_bev) + (ng ? ov_off[f] : 0);
+  int tp = 0, fp = 0, fn = 0;
+  for (int i = 0; i < ng; i++) {
+    const int ig = ignored_gt(gt_meta + 2 * (size_t)(g0 + i), c);
+    if (ig == -1) continue;
+    int best = -1;
+    bool best_ign = false;
+    float best_ov = 0.f;
+    for (int j = 0; j < nd; j++) {
+      const int igd = ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c);
+      if (igd == -1) continue;
+      if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+      if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+      const float o = ov[(size_t)j * ng + i];
+      if (!(o > c.min_overlap)) continue;
+      if (igd == 0) {  // a counted detection: the largest overlap wins (earliest on ties), and displaces an ignored pick
+        if (best < 0 || best_ign || o > best_ov) {
+          best = j;
+          best_ov = o;
+          best_ign = false;
+        }
+      } else if (best < 0) {  // a short detection: only while nothing is picked
+        best = j;
+        best_ign = true;
+      }
+    }
+    if (best < 0) {
+      fn += ig == 0;
+      continue;
+    }
+    assigned[(best >> 6) * 64] |= 1ull << (best & 63);
+    tp += ig == 0 && !best_ign;
+  }
+  for (int j = 0; j < nd; j++) {
+    if (ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != 0) continue;
+    if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+    fp += !((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull);
+  }
+  int* out = counts + ((size_t)combo * KE_NT + lane) * 3;
+  if (tp) atomicAdd(out + 0, tp);
+  if (fp) atomicAdd(out + 1, fp);
+  if (fn) atomicAdd(out + 2, fn);
+}
+
+__global__ __launch_bounds__(V3D_WAVE) void kitti_ap_kernel(const int* __restrict__ counts, const int* __restrict__ n_thresholds,
+                                                            int n_combos, double* __restrict__ ap) {
+  const int combo = threadIdx.x;
+  if (combo >= n_combos) return;
+  const int nt = n_thresholds[combo];
+  double prec[KE_NT];
+#pragma unroll
+  for (int k = 0; k < KE_NT; k++) {
+    const int* cnt = counts + ((size_t)combo * KE_NT + k) * 3;
+    const int tp = cnt[0], fp = cnt[1];
+    prec[k] = (k < nt && tp + fp > 0) ? (double)tp / (double)(tp + fp) : 0.0;
+  }
+#pragma unroll
+  for (int k = KE_NT - 2; k >= 0; k--) prec[k] = fmax(prec[k], prec[k + 1]);
+  double r11 = 0.0, r40 = 0.0;
+#pragma unroll
+  for (int k = 0; k < KE_NT; k += 4) r11 += prec[k];
+#pragma unroll
+  for (int k = 1; k < KE_NT; k++) r40 += prec[k];
+  ap[2 * combo + 0] = r11 / 11.0 * 100.0;
+  ap[2 * combo + 1] = r40 / 40.0 * 100.0;
+}
+
+static int ke_check(int n_frames, int max_dt, int max_gt, int n_combos) {
+  if (n_frames < 0 || max_dt < 0 || max_gt < 0 || n_combos < 0) return V3D_EINVAL;
+  if (max_dt > V3D_KITTI_MAX_DT || max_gt > V3D_KITTI_MAX_GT || n_combos > V3D_KITTI_MAX_COMBOS) return V3D_EUNSUPPORTED;
+  return V3D_OK;
+}
+
+static KeCombos ke_combos(const v3d_kitti_combo* host, int n) {
+  KeCombos k = {};
+  for (int i = 0; i < n; i++) k.c[i] = host[i];
+  return k;
+}
+
+extern "C" int v3d_kitti_eval_overlaps(const float* gt, const int32_t* gt_off, const float* dt, const int32_t* dt_off,
+                                       const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_bev, float* ov_3d,
+                                       v3d_stream_t stream) {
+  const int e = ke_check(n_frames, max_dt, max_gt, 0);
+  if (e) return e;
+  if (n_frames == 0 || max_dt == 0 || max_gt == 0) return V3D_OK;
+  if (!gt || !gt_off || !dt || !dt_off || !ov_off || !ov_bev || !ov_3d) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_overlaps_kernel, dim3(n_frames, v3d_ceil_div(max_dt, V3D_BLOCK)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, gt, gt_off, dt, dt_off, ov_off, ov_bev, ov_3d);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta,
+                                    const int32_t* dt_off, const int64_t* ov_off, const float* ov_bev, const float* ov_3d,
+                                    int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,
+                                    int capacity, int32_t* tp_count, float* tp_scores, int32_t* n_valid, v3d_stream_t stream) {
+  const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
+  if (e) return e;
+  if (capacity < 0) return V3D_EINVAL;
+  if (n_frames == 0 || n_combos == 0 || max_gt == 0) return V3D_OK;
+  if (!gt_meta || !gt_off || !dt_off || !ov_off || !combos_host || !tp_count || !n_valid) return V3D_EINVAL;
+  if (max_dt > 0 && (!dt || !dt_meta || !ov_bev || !ov_3d || !tp_scores)) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_pass1_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov_bev, ov_3d,
+                     ke_combos(combos_host, n_combos), n_combos, capacity, tp_count, tp_scores, n_valid);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacity, const int32_t* tp_count, const int32_t* n_valid,
+                                         int n_combos, float* thresholds, int32_t* n_thresholds, v3d_stream_t stream) {
+  const int e = ke_check(0, 0, 0, n_combos);
+  if (e) return e;
+  if (capacity < 0) return V3D_EINVAL;
+  if (n_combos == 0) return V3D_OK;
+  if (!tp_count || !n_valid || !thresholds || !n_thresholds || (capacity > 0 && !sorted_scores)) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_thresholds_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, sorted_scores, capacity, tp_count,
+                     n_valid, n_combos, thresholds, n_thresholds);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta,
+                                    const int32_t* dt_off, const int64_t* ov_off, const float* ov_bev, const float* ov_3d,
+                                    int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,
+                                    const float* thresholds, const int32_t* n_thresholds, int32_t* counts, v3d_stream_t stream) {
+  const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
+  if (e) return e;
+  if (n_frames == 0 || n_combos == 0) return V3D_OK;
+  if (!gt_off || !dt_off || !ov_off || !combos_host || !thresholds || !n_thresholds || !counts) return V3D_EINVAL;
+  if (max_gt > 0 && !gt_meta) return V3D_EINVAL;
+  if (max_dt > 0 && (!dt || !dt_meta)) return V3D_EINVAL;
+  if (max_dt > 0 && max_gt > 0 && (!ov_bev || !ov_3d)) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_pass2_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov_bev, ov_3d,
+                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresholds, int n_combos, double* ap, v3d_stream_t stream) {
+  const int e = ke_check(0, 0, 0, n_combos);
+  if (e) return e;
+  if (n_combos == 0) return V3D_OK;
+  if (!counts || !n_thresholds || !ap) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_ap_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts, n_thresholds, n_combos, ap);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
