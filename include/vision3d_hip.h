@@ -717,6 +717,31 @@ int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const fl
 /* Precision per threshold, its running maximum from the right, and ap (n_combos, 2) f64 = (AP_R11, AP_R40) in percent, summed in
  * the order of the definition (bit-reproducible). */
 int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresholds, int n_combos, double* ap, v3d_stream_t stream);
+/* ---- KITTI 2-D bbox AP and average orientation similarity (AOS), on combos of their own.  Extra inputs, in the layouts above:
+ *   gt_img (G, 5), dt_img (D, 5) f32 = image box (x1, y1, x2, y2) and alpha; bit V3D_KITTI_DONTCARE_BIT of gt_meta[1] set = the
+ *   ground truth is a DontCare region (it is also class code OTHER, so no combo counts it).
+ * The bbox combos run v3d_kitti_eval_pass1 with ov_2d passed as ov_bev (metric 0), then the thresholds and ap as above, and
+ * v3d_kitti_eval_pass2_image in place of v3d_kitti_eval_pass2. */
+#define V3D_KITTI_DONTCARE_BIT 3
+/* ov_2d (sum n_dt * n_gt) f32: IoU of the image boxes (no +1), frame-major like ov_bev, computed in double. */
+int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t* gt_off, const float* dt_img, const int32_t* dt_off,
+                                  const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_2d, v3d_stream_t stream);
+/* Pass 2 of the bbox metric (the combos' `metric` is not read): the greedy assignment of v3d_kitti_eval_pass2 on ov_2d, then
+ * every counted (ignored_dt == 0), unassigned detection not under the threshold whose inter / area_dt with some DontCare region
+ * exceeds min_overlap is absorbed (no FP).  counts (n_combos, 41, 3) i32 += (tp, fp, fn); similarity (n_combos, 41) i64 += each
+ * frame's sum over its true positives of (1 + cos(alpha_gt - alpha_dt)) / 2 (double, ground-truth order) as 32.32 fixed point,
+ * llrint(sum * 2^32), by integer atomics: the total is deterministic and independent of frame order.  A frame adds < 2^40
+ * (<= 256 true positives), so the total is exact below 2^31 true positives per (combo, threshold): more than 8 million frames
+ * at the per-frame limit.  counts and similarity must be zero on entry. */
+int v3d_kitti_eval_pass2_image(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt,
+                               const int32_t* dt_meta, const int32_t* dt_off, const float* dt_img, const int64_t* ov_off,
+                               const float* ov_2d, int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host,
+                               int n_combos, const float* thresholds, const int32_t* n_thresholds, int32_t* counts,
+                               int64_t* similarity, v3d_stream_t stream);
+/* aos (n_combos, 2) f64 = (AOS_R11, AOS_R40) in percent: per threshold k < n_thresholds, similarity * 2^-32 / (tp + fp) (0 when
+ * tp + fp == 0 and for k >= n_thresholds), its running maximum from the right, summed as in v3d_kitti_eval_ap. */
+int v3d_kitti_eval_aos(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos, double* aos,
+                       v3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,10 @@ _SIGNATURES = {
     "v3d_kitti_eval_thresholds": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "v3d_kitti_eval_pass2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_kitti_eval_ap": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "v3d_kitti_eval_overlaps_image": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "v3d_kitti_eval_pass2_image": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "v3d_kitti_eval_aos": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
 }
 
 

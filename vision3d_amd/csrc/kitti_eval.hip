@@ -11,6 +11,12 @@
 //   4. pass 2      one wave per (frame, combo), one lane per threshold: each lane runs its own greedy assignment with an
 //                  "assigned" bitmask in LDS and adds integer (tp, fp, fn) with global atomics (order-free, deterministic);
 //   5. ap          one lane per combo: precision, its running maximum from the right, R11 / R40 sums in definition order.
+// The 2-D bbox / AOS metrics reuse pass 1, the thresholds and ap on their own combos and add three kernels:
+//   overlaps_image  the grid of stage 1: 2-D IoU of (x1, y1, x2, y2) image boxes into ov_2d (same layout as ov_bev);
+//   pass2_image     pass 2 on ov_2d plus the DontCare step (unassigned counted detections whose inter / area_dt with a DontCare
+//                   region exceeds the minimum overlap are no false positives) and each lane's true-positive similarity sum
+//                   (1 + cos(alpha_gt - alpha_dt)) / 2 in double, added as 32.32 fixed point with 64-bit integer atomics;
+//   aos             one lane per combo: similarity / (tp + fp), running maximum, R11 / R40 as in ap.
 // Limits: 1 024 detections (16 bitmask words per lane in pass 2, 16 register bits per lane in pass 1) and 256 ground truths
 // (one LDS slot per thread in stage 1) per frame.
 #include "v3d_common.h"
@@ -20,6 +26,7 @@ using v3d::BoxPrep;
 
 #define KE_NT V3D_KITTI_SAMPLE_PTS
 #define KE_WORDS (V3D_KITTI_MAX_DT / 64)
+#define KE_DONTCARE_BIT V3D_KITTI_DONTCARE_BIT  // gt_meta[1] (ignored_gt reads bits 0-2 only)
 
 struct KeCombos {
   v3d_kitti_combo c[V3D_KITTI_MAX_COMBOS];
@@ -258,6 +265,162 @@ __global__ __launch_bounds__(V3D_WAVE) void kitti_ap_kernel(const int* __restric
   ap[2 * combo + 1] = r40 / 40.0 * 100.0;
 }
 
+// ---- 2-D bbox / AOS ------------------------------------------------------------------------------------------------------
+// Image boxes are (x1, y1, x2, y2, alpha) f32 rows; overlaps are taken in double from the f32 corners, without +1.
+__device__ __forceinline__ double img_inter(double x1, double y1, double x2, double y2, const float* g) {
+  const double iw = fmin(x2, (double)g[2]) - fmax(x1, (double)g[0]);
+  const double ih = fmin(y2, (double)g[3]) - fmax(y1, (double)g[1]);
+  return (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_overlaps_image_kernel(const float* __restrict__ gt_img,
+                                                                         const int* __restrict__ gt_off,
+                                                                         const float* __restrict__ dt_img,
+                                                                         const int* __restrict__ dt_off,
+                                                                         const int64_t* __restrict__ ov_off,
+                                                                         float* __restrict__ ov_2d) {
+  __shared__ float gts[V3D_KITTI_MAX_GT][4];
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng <= 0 || nd <= 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;  // (block-uniform)
+  if ((int)threadIdx.x < ng) {
+    const float* g = gt_img + 5 * (size_t)(g0 + threadIdx.x);
+    for (int k = 0; k < 4; k++) gts[threadIdx.x][k] = g[k];
+  }
+  __syncthreads();
+  const int j = blockIdx.y * V3D_BLOCK + threadIdx.x;
+  if (j >= nd) return;
+  const float* b = dt_img + 5 * (size_t)(d0 + j);
+  const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+  const double area = (x2 - x1) * (y2 - y1);
+  const size_t row = (size_t)ov_off[f] + (size_t)j * ng;
+  for (int i = 0; i < ng; i++) {
+    const float* g = gts[i];
+    const double inter = img_inter(x1, y1, x2, y2, g);
+    // inter > 0 needs both boxes proper in x and y: the union is positive
+    ov_2d[row + i] = inter > 0.0 ? (float)(inter / (area + ((double)g[2] - g[0]) * ((double)g[3] - g[1]) - inter)) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_image_kernel(
+    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
+    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
+    const int64_t* __restrict__ ov_off, const float* __restrict__ ov_2d, KeCombos combos, int n_combos,
+    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
+    unsigned long long* __restrict__ similarity) {
+  __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
+  const int lane = threadIdx.x & 63;
+  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
+  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
+  const v3d_kitti_combo c = combos.c[combo];
+  const int nt = n_thresholds[combo];
+  if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng < 0 || nd < 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
+  const float thresh = thresholds[combo * KE_NT + lane];
+  unsigned long long* assigned = assigned_lds[threadIdx.x >> 6] + lane;
+  const int nw = (nd + 63) >> 6;
+  for (int w = 0; w < nw; w++) assigned[w * 64] = 0ull;
+  const float* ov = ov_2d + (ng ? ov_off[f] : 0);
+  int tp = 0, fp = 0, fn = 0;
+  int dc_lo = ng, dc_hi = 0;  // the DontCare regions lie in [dc_lo, dc_hi)
+  double sim = 0.0;           // this frame's true-positive similarities, in ground-truth order
+  for (int i = 0; i < ng; i++) {
+    const int* gm = gt_meta + 2 * (size_t)(g0 + i);
+    if ((gm[1] >> KE_DONTCARE_BIT) & 1) {
+      dc_lo = min(dc_lo, i);
+      dc_hi = i + 1;
+    }
+    const int ig = ignored_gt(gm, c);
+    if (ig == -1) continue;
+    int best = -1;
+    bool best_ign = false;
+    float best_ov = 0.f;
+    for (int j = 0; j < nd; j++) {  // the greedy rule of kitti_pass2_kernel
+      const int igd = ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c);
+      if (igd == -1) continue;
+      if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+      if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+      const float o = ov[(size_t)j * ng + i];
+      if (!(o > c.min_overlap)) continue;
+      if (igd == 0) {
+        if (best < 0 || best_ign || o > best_ov) {
+          best = j;
+          best_ov = o;
+          best_ign = false;
+        }
+      } else if (best < 0) {
+        best = j;
+        best_ign = true;
+      }
+    }
+    if (best < 0) {
+      fn += ig == 0;
+      continue;
+    }
+    assigned[(best >> 6) * 64] |= 1ull << (best & 63);
+    if (ig == 0 && !best_ign) {
+      tp++;
+      const double delta = (double)gt_img[5 * (size_t)(g0 + i) + 4] - (double)dt_img[5 * (size_t)(d0 + best) + 4];
+      sim += (1.0 + cos(delta)) / 2.0;
+    }
+  }
+  // false positives; an unassigned counted detection over a DontCare region (inter / area_dt > min overlap) is absorbed
+  for (int j = 0; j < nd; j++) {
+    if (ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != 0) continue;
+    if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+    if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+    bool absorbed = false;
+    if (dc_lo < dc_hi) {
+      const float* b = dt_img + 5 * (size_t)(d0 + j);
+      const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+      const double area = (x2 - x1) * (y2 - y1);  // (positive wherever the intersection is)
+      for (int i = dc_lo; i < dc_hi && !absorbed; i++) {
+        if (!((gt_meta[2 * (size_t)(g0 + i) + 1] >> KE_DONTCARE_BIT) & 1)) continue;
+        const double inter = img_inter(x1, y1, x2, y2, gt_img + 5 * (size_t)(g0 + i));
+        absorbed = inter > 0.0 && inter / area > (double)c.min_overlap;
+      }
+    }
+    fp += !absorbed;
+  }
+  const size_t at = (size_t)combo * KE_NT + lane;
+  int* out = counts + at * 3;
+  if (tp) atomicAdd(out + 0, tp);
+  if (fp) atomicAdd(out + 1, fp);
+  if (fn) atomicAdd(out + 2, fn);
+  // 32.32 fixed point: sim <= 256 per frame, so each add is < 2^40; integer adds make the total order-free and exact
+  if (tp) atomicAdd(similarity + at, (unsigned long long)llrint(sim * 4294967296.0));
+}
+
+__global__ __launch_bounds__(V3D_WAVE) void kitti_aos_kernel(const int* __restrict__ counts,
+                                                             const unsigned long long* __restrict__ similarity,
+                                                             const int* __restrict__ n_thresholds, int n_combos,
+                                                             double* __restrict__ aos) {
+  const int combo = threadIdx.x;
+  if (combo >= n_combos) return;
+  const int nt = n_thresholds[combo];
+  double a[KE_NT];
+#pragma unroll
+  for (int k = 0; k < KE_NT; k++) {
+    const int* cnt = counts + ((size_t)combo * KE_NT + k) * 3;
+    const int den = cnt[0] + cnt[1];
+    const double s = (double)(long long)similarity[(size_t)combo * KE_NT + k] * (1.0 / 4294967296.0);
+    a[k] = (k < nt && den > 0) ? s / (double)den : 0.0;
+  }
+#pragma unroll
+  for (int k = KE_NT - 2; k >= 0; k--) a[k] = fmax(a[k], a[k + 1]);
+  double r11 = 0.0, r40 = 0.0;
+#pragma unroll
+  for (int k = 0; k < KE_NT; k += 4) r11 += a[k];
+#pragma unroll
+  for (int k = 1; k < KE_NT; k++) r40 += a[k];
+  aos[2 * combo + 0] = r11 / 11.0 * 100.0;
+  aos[2 * combo + 1] = r40 / 40.0 * 100.0;
+}
+
 static int ke_check(int n_frames, int max_dt, int max_gt, int n_combos) {
   if (n_frames < 0 || max_dt < 0 || max_gt < 0 || n_combos < 0) return V3D_EINVAL;
   if (max_dt > V3D_KITTI_MAX_DT || max_gt > V3D_KITTI_MAX_GT || n_combos > V3D_KITTI_MAX_COMBOS) return V3D_EUNSUPPORTED;
@@ -337,6 +500,52 @@ extern "C" int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresho
   if (n_combos == 0) return V3D_OK;
   if (!counts || !n_thresholds || !ap) return V3D_EINVAL;
   hipLaunchKernelGGL(kitti_ap_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts, n_thresholds, n_combos, ap);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+
+extern "C" int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t* gt_off, const float* dt_img, const int32_t* dt_off,
+                                             const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_2d,
+                                             v3d_stream_t stream) {
+  const int e = ke_check(n_frames, max_dt, max_gt, 0);
+  if (e) return e;
+  if (n_frames == 0 || max_dt == 0 || max_gt == 0) return V3D_OK;
+  if (!gt_img || !gt_off || !dt_img || !dt_off || !ov_off || !ov_2d) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_overlaps_image_kernel, dim3(n_frames, v3d_ceil_div(max_dt, V3D_BLOCK)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, gt_img, gt_off, dt_img, dt_off, ov_off, ov_2d);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_pass2_image(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt,
+                                          const int32_t* dt_meta, const int32_t* dt_off, const float* dt_img, const int64_t* ov_off,
+                                          const float* ov_2d, int n_frames, int max_dt, int max_gt,
+                                          const v3d_kitti_combo* combos_host, int n_combos, const float* thresholds,
+                                          const int32_t* n_thresholds, int32_t* counts, int64_t* similarity, v3d_stream_t stream) {
+  const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
+  if (e) return e;
+  if (n_frames == 0 || n_combos == 0) return V3D_OK;
+  if (!gt_off || !dt_off || !ov_off || !combos_host || !thresholds || !n_thresholds || !counts || !similarity) return V3D_EINVAL;
+  if (max_gt > 0 && (!gt_meta || !gt_img)) return V3D_EINVAL;
+  if (max_dt > 0 && (!dt || !dt_meta || !dt_img)) return V3D_EINVAL;
+  if (max_dt > 0 && max_gt > 0 && !ov_2d) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_pass2_image_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, gt_meta, gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov_2d,
+                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts,
+                     (unsigned long long*)similarity);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_kitti_eval_aos(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos,
+                                  double* aos, v3d_stream_t stream) {
+  const int e = ke_check(0, 0, 0, n_combos);
+  if (e) return e;
+  if (n_combos == 0) return V3D_OK;
+  if (!counts || !similarity || !n_thresholds || !aos) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_aos_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts,
+                     (const unsigned long long*)similarity, n_thresholds, n_combos, aos);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

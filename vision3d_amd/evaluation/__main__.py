@@ -1,4 +1,4 @@
-"""python -m vision3d_amd.evaluation --labels DIR --results DIR [--ids FILE] [--r11]
+"""python -m vision3d_amd.evaluation --labels DIR --results DIR [--ids FILE] [--metrics bbox,bev,3d,aos] [--r11]
 
 Evaluates KITTI result files (16 fields, with score) against label_2 files of the same frame ids and prints the summary.  Frame
 ids: one per line of --ids, else every result file's name; a listed frame without a result file has no detections."""
@@ -15,6 +15,7 @@ def main(argv=None):
     ap.add_argument("--labels", required=True, help="directory of ground-truth label files (label_2)")
     ap.add_argument("--results", required=True, help="directory of result files")
     ap.add_argument("--ids", help="file with one frame id per line (default: every result file)")
+    ap.add_argument("--metrics", default="bev,3d", help="comma list of bbox, bev, 3d, aos, printed in this order (default: bev,3d)")
     ap.add_argument("--r11", action="store_true", help="also print AP on the 11 recall positions")
     args = ap.parse_args(argv)
     if args.ids:
@@ -23,7 +24,11 @@ def main(argv=None):
         ids = sorted(f[:-4] for f in os.listdir(args.results) if f.endswith(".txt"))
     if not ids:
         ap.error("no frames to evaluate")
-    ev = KittiEvaluator()
+    metrics = tuple(m.strip() for m in args.metrics.split(",") if m.strip())
+    try:
+        ev = KittiEvaluator(metrics=metrics)
+    except ValueError as e:
+        ap.error(str(e))
     for i in ids:
         name = f"{int(i):06d}" if i.isdigit() else i
         res = os.path.join(args.results, name + ".txt")

@@ -1,4 +1,5 @@
-"""KITTI BEV and 3-D average precision, evaluated on the device (csrc/kitti_eval.hip).  The upstream project has no evaluator.
+"""KITTI 2-D bbox, BEV and 3-D average precision and average orientation similarity (AOS), evaluated on the device
+(csrc/kitti_eval.hip).  The upstream project has no evaluator.
 
 The protocol is the KITTI devkit's as its widely used Python port states it, in the rectified camera frame, so the numbers
 compare with published ones.  It is NOT the loader's `Labels.level` (dataset/kitti.py `_difficulty`, the upstream loader's
@@ -9,10 +10,13 @@ Overlaps, for every (detection, ground truth) pair of a frame, from ONE polygon 
        axis (pointing down) turns the local x axis to (cos ry, -sin ry).  (The core takes degrees: -ry * 180 / pi.)
   3-D  BEV intersection * y-overlap / union of the volumes; y-overlap = min(y1, y2) - max(y1 - h1, y2 - h2) clamped at 0,
        y the box bottom.
+  bbox IoU of the image boxes (x1, y1, x2, y2), no +1: iw = min(x2) - max(x1), ih = min(y2) - max(y1); 0 unless both > 0, else
+       iw * ih / (area_dt + area_gt - iw * ih).  (Separate pass over the pairs, double precision, stored as float32.)
 
 Per class c, difficulty d (easy, moderate, hard), metric and minimum overlap t_min:
   MIN_HEIGHT = [40, 25, 25], MAX_OCCLUSION = [0, 1, 2], MAX_TRUNCATION = [0.15, 0.3, 0.5];
-  t_min "strict": Car 0.7, Pedestrian 0.5, Cyclist 0.5; "loose": 0.5 / 0.25 / 0.25 (BEV and 3-D alike).
+  t_min "strict": Car 0.7, Pedestrian 0.5, Cyclist 0.5; "loose": 0.5 / 0.25 / 0.25 (BEV and 3-D alike).  bbox and aos use
+    0.7 / 0.5 / 0.5 in both sets (the loose set loosens BEV and 3-D only).
   Ground truth (height = y2 - y1 of the 2-D box, no +1):
     valid = 1 if its name is c, 0 if it is c's neighbour (Van for Car, Person_sitting for Pedestrian), else -1 (DontCare and
     every other name included); ignore = occ > MAX_OCCLUSION[d] or trunc > MAX_TRUNCATION[d] or height <= MIN_HEIGHT[d];
@@ -25,15 +29,27 @@ Per class c, difficulty d (easy, moderate, hard), metric and minimum overlap t_m
     wins if its overlap is larger than the best so far or the current pick is an ignored detection; an ignored_dt == 1
     detection is taken only while nothing is picked.  Then: no pick and ignored_gt == 0 -> FN; a pick with ignored_gt == 1 or
     ignored_dt == 1 -> assigned, neither TP nor FP; any other pick -> TP, assigned, (pass 1) its score recorded.  With
-    compute_fp, FP = detections not assigned, with ignored_dt == 0 and not under thresh.  DontCare regions play no part.
+    compute_fp, FP = detections not assigned, with ignored_dt == 0 and not under thresh.  DontCare regions play no part in
+    BEV and 3-D.
   Pass 1: assign(., 0, False) over all frames -> TP scores.
   Thresholds: TP scores in descending order, current = 0; score i (0-based): l = (i+1)/n_valid_gt, r = (i+2)/n_valid_gt
     (r = l for the last); skip it if (r - current) < (current - l) and it is not the last, else take it and current += 1/40.
     Double precision, in this order; at most 41 thresholds.
   Pass 2: per threshold, (tp, fp, fn) = sum over frames of assign(., thresh, True).
+  Pass 2, bbox only: after the FP count, every detection still unassigned, with ignored_dt == 0 and not under thresh, whose
+    inter / area_dt (not IoU) with any ground truth named DontCare is > t_min is absorbed: fp -= 1, assigned.  (DontCare ground
+    truths stay ignored_gt == -1 for the matching; pass 1 has no DontCare step.)
   precision[k] = tp / (tp + fp) (0 when tp + fp == 0 and for k >= the number of thresholds) on 41 entries, then
     precision[k] = max(precision[k:]); AP_R11 = sum(precision[0, 4, ..., 40]) / 11 * 100, AP_R40 = sum(precision[1..40]) / 40
     * 100, summed in index order.  A class without valid ground truth gets AP 0.
+  AOS (on the bbox combos' own thresholds and counts): every true positive of pass 2 adds (1 + cos(alpha_gt - alpha_dt)) / 2,
+    in double; similarity[k] = that sum over all frames at threshold k (a frame with tp == fp == 0 adds nothing);
+    aos[k] = similarity[k] / (tp + fp) with fp after absorption (0 when tp + fp == 0 and for k >= the number of thresholds),
+    then the running maximum and the R11 / R40 sums of AP.  Each frame's sum is added as 32.32 fixed point (integer atomics),
+    so the total is deterministic whatever the frame order.
+  Alpha is taken as given: ground truth and file detections field 3 of the line, model detections
+    -atan2(-y_lidar, x_lidar) + ry (what write_kitti_results writes).  The devkit's -10 ("unknown") is not special-cased: a
+    detection with alpha -10 simply scores its cosine.
 
 Limits: 1 024 detections and 256 ground truths per frame (RuntimeError beyond them).  No CPU fallback.
 """
@@ -50,7 +66,10 @@ MAX_OCCLUSION = (0, 1, 2)
 MAX_TRUNCATION = (0.15, 0.3, 0.5)
 DIFFICULTIES = ("easy", "moderate", "hard")
 MIN_OVERLAP = {"strict": {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5},
-               "loose": {"Car": 0.5, "Pedestrian": 0.25, "Cyclist": 0.25}}
+               "loose": {"Car": 0.5, "Pedestrian": 0.25, "Cyclist": 0.25}}  # BEV and 3-D
+MIN_OVERLAP_IMAGE = {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5}  # bbox and aos, in both overlap sets
+METRICS = ("bbox", "bev", "3d", "aos")
+DONTCARE_BIT = 3  # gt_meta[1] bit: the ground truth is a DontCare region (V3D_KITTI_DONTCARE_BIT)
 NEIGHBOUR = {"Car": "Van", "Pedestrian": "Person_sitting", "Cyclist": None}
 CLASS_CODE = {"Car": 0, "Pedestrian": 1, "Cyclist": 2, "Van": 3, "Person_sitting": 4}  # every other name: OTHER
 CODE_OTHER = 5
@@ -59,6 +78,11 @@ MAX_DT, MAX_GT, SAMPLE_PTS = 1024, 256, 41
 
 def class_code(name):
     return CLASS_CODE.get(name, CODE_OTHER)
+
+
+def min_overlap(overlap_set, cls, metric):
+    """t_min of one (overlap set, class, metric): MIN_OVERLAP for BEV / 3-D, MIN_OVERLAP_IMAGE for bbox / aos."""
+    return MIN_OVERLAP_IMAGE[cls] if metric in ("bbox", "aos") else MIN_OVERLAP[overlap_set][cls]
 
 
 def calib_rows(calib):
@@ -136,8 +160,15 @@ def _gt_arrays(labels):
     flags = _height_flags(height, short=False)
     for d in range(3):
         flags |= ((labels.occlusion > MAX_OCCLUSION[d]) | (labels.truncation > MAX_TRUNCATION[d])).astype(np.int32) << d
+    flags |= np.array([n.lower() == "dontcare" for n in labels.names], np.int32).reshape(-1) << DONTCARE_BIT
     codes = np.array([class_code(n) for n in labels.names], np.int32)
     return _camera_rows(labels), np.stack((codes, flags), 1).astype(np.int32).reshape(-1, 2)
+
+
+def _image_rows(labels):
+    """(n, 5) float32 (x1, y1, x2, y2, alpha) of a Labels."""
+    return np.concatenate([np.asarray(labels.box2d, np.float64).reshape(-1, 4), np.asarray(labels.alpha, np.float64).reshape(-1, 1)],
+                          1).astype(np.float32)
 
 
 def _dt_arrays(labels):
@@ -177,8 +208,9 @@ def camera_box_overlaps(dt_boxes, gt_boxes):
 
 class KittiEvaluator:
     """Accumulates frames (`add_frame`) and evaluates them all at once on the GPU (`compute`): a fixed number of launches and one
-    host read, whatever the frame count.  `det_names[class_idx]` names model detections added as tensors (default: the KITTI
-    class order of dataset/kitti.py)."""
+    host read, whatever the frame count.  `metrics` is any of "bbox", "bev", "3d", "aos" (default BEV and 3-D); "aos" is computed
+    from the bbox combos, which run whenever "bbox" or "aos" is asked for.  `det_names[class_idx]` names model detections added
+    as tensors (default: the KITTI class order of dataset/kitti.py)."""
 
     def __init__(self, classes=("Car", "Pedestrian", "Cyclist"), metrics=("bev", "3d"), overlaps=("strict", "loose"),
                  det_names=("Car", "Pedestrian", "Cyclist"), device=None):
@@ -186,15 +218,21 @@ class KittiEvaluator:
             if c not in NEIGHBOUR:
                 raise ValueError(f"KittiEvaluator: unknown class {c!r} (Car, Pedestrian, Cyclist)")
         for m in metrics:
-            if m not in ("bev", "3d"):
-                raise ValueError(f"KittiEvaluator: unknown metric {m!r} (bev, 3d)")
+            if m not in METRICS:
+                raise ValueError(f"KittiEvaluator: unknown metric {m!r} (bbox, bev, 3d, aos)")
         for o in overlaps:
             if o not in MIN_OVERLAP:
                 raise ValueError(f"KittiEvaluator: unknown overlap set {o!r} (strict, loose)")
         self.classes, self.metrics, self.overlaps = tuple(classes), tuple(metrics), tuple(overlaps)
         self.det_names = tuple(det_names)
         self.device = torch.device(device) if device is not None else None
-        self.combos = [(o, c, m, d) for o in self.overlaps for c in self.classes for m in self.metrics for d in range(3)]
+        # device combos: BEV / 3-D first, then the bbox combos (which also carry aos)
+        self.combos = [(o, c, m, d) for o in self.overlaps for c in self.classes for m in self.metrics if m in ("bev", "3d")
+                       for d in range(3)]
+        self.n_camera_combos = len(self.combos)
+        self.image = "bbox" in self.metrics or "aos" in self.metrics
+        if self.image:
+            self.combos += [(o, c, "bbox", d) for o in self.overlaps for c in self.classes for d in range(3)]
         self.frames = []
         self.details = {}
         self.result = None
@@ -205,9 +243,9 @@ class KittiEvaluator:
     def add_frame(self, labels, detections):
         """labels: ground truth, a `dataset.kitti.Labels`.  detections: a `Labels` read from a KITTI result file, or model output
         in the lidar frame `(boxes (K, 7), class_idx (K,), scores (K,), calib)` (tensors may stay on the GPU)."""
-        gt = _gt_arrays(labels)
+        gt = _gt_arrays(labels) + (_image_rows(labels),)
         if isinstance(detections, K.Labels):
-            self.frames.append((gt, ("labels",) + _dt_arrays(detections)))
+            self.frames.append((gt, ("labels",) + _dt_arrays(detections) + (_image_rows(detections),)))
             return
         boxes, class_idx, scores, calib = detections
         L.require_gpu("KittiEvaluator.add_frame", boxes, class_idx, scores)
@@ -227,9 +265,10 @@ class KittiEvaluator:
         return torch.device("cuda", torch.cuda.current_device())
 
     def _detections(self, dev):
-        """(dt (D, 8) f32, dt_meta (D, 2) i32) on `dev`, frame-major: file detections in one upload, model detections converted
-        to the camera frame in one batch (per-frame calibration rows gathered per detection)."""
-        file_pos, file_rows, file_meta, model_pos, model, calibs, counts = [], [], [], [], [], [], []
+        """(dt (D, 8) f32, dt_meta (D, 2) i32, dt_img (D, 5) f32 or None) on `dev`, frame-major: file detections in one upload,
+        model detections converted to the camera frame in one batch (per-frame calibration rows gathered per detection).
+        dt_img (image box, alpha) is filled only when a bbox / aos metric is asked for."""
+        file_pos, file_rows, file_meta, file_img, model_pos, model, calibs, counts = [], [], [], [], [], [], [], []
         at = 0
         for _, d in self.frames:
             if d[0] == "labels":
@@ -237,6 +276,7 @@ class KittiEvaluator:
                 file_pos.append(np.arange(at, at + n))
                 file_rows.append(d[1])
                 file_meta.append(d[2])
+                file_img.append(d[3])
             else:
                 n = d[1].shape[0]
                 model_pos.append(np.arange(at, at + n))
@@ -246,10 +286,13 @@ class KittiEvaluator:
             at += n
         dt = torch.empty((max(at, 1), 8), dtype=torch.float32, device=dev)
         meta = torch.empty((max(at, 1), 2), dtype=torch.int32, device=dev)
+        img = torch.zeros((max(at, 1), 5), dtype=torch.float32, device=dev) if self.image else None
         if file_rows:
             pos = torch.from_numpy(np.concatenate(file_pos)).to(dev)
             dt[pos] = torch.from_numpy(np.concatenate(file_rows)).to(dev)
             meta[pos] = torch.from_numpy(np.concatenate(file_meta)).to(dev)
+            if self.image:
+                img[pos] = torch.from_numpy(np.concatenate(file_img)).to(dev)
         if model:
             pos = torch.from_numpy(np.concatenate(model_pos)).to(dev)
             boxes = torch.cat([d[1] for d in model]).to(dev)
@@ -265,15 +308,20 @@ class KittiEvaluator:
             code = codes[frame, torch.where((cls >= 0) & (cls < n_names), cls, torch.full_like(cls, n_names))]
             dt[pos] = torch.cat([cam, scores[:, None]], 1)
             meta[pos] = torch.stack((code, flags.int()), 1)
-        return dt, meta
+            if self.image:  # alpha as write_kitti_results computes it: in double, rounded to float32
+                alpha = -torch.atan2(-boxes[:, 1].double(), boxes[:, 0].double()) + cam[:, 6].double()
+                img[pos] = torch.cat([box2d, alpha.float()[:, None]], 1)
+        return dt, meta, img
 
     def compute(self):
         """Evaluates every frame added so far -> result[overlap_set][class][metric]["R11" | "R40"] = [easy, moderate, hard] in
-        percent.  Per-combo detail (n_valid_gt, thresholds, (tp, fp, fn) per threshold) lands in `self.details`."""
+        percent.  Per-combo detail (n_valid_gt, thresholds, (tp, fp, fn) per threshold; bbox combos also the similarity sum
+        per threshold) lands in `self.details`, keyed (overlap_set, class, "bev" | "3d" | "bbox", difficulty)."""
         n_frames, n_combos = len(self.frames), len(self.combos)
+        n_img = n_combos - self.n_camera_combos
         n_gt = np.array([len(g[0]) for g, _ in self.frames], np.int64)
         n_dt = np.array([len(d[1]) if d[0] == "labels" else d[1].shape[0] for _, d in self.frames], np.int64)
-        packed = np.zeros(n_combos * (2 + 2 + SAMPLE_PTS + 3 * SAMPLE_PTS))
+        packed = np.zeros(n_combos * (2 + 2 + SAMPLE_PTS + 3 * SAMPLE_PTS) + n_img * (2 + SAMPLE_PTS))
         if n_frames:
             packed = self._run(n_gt, n_dt)
         self._unpack(packed)
@@ -281,22 +329,23 @@ class KittiEvaluator:
 
     def _run(self, n_gt, n_dt):
         dev = self._device()
-        n_frames, n_combos = len(self.frames), len(self.combos)
+        n_frames, n_combos, n3 = len(self.frames), len(self.combos), self.n_camera_combos
+        n_img = n_combos - n3
         max_dt, max_gt = int(n_dt.max()), int(n_gt.max())
         G = int(n_gt.sum())
         with L.device_guard(dev):
             gt = torch.from_numpy(np.concatenate([g[0] for g, _ in self.frames] + [np.zeros((1, 7), np.float32)])).to(dev)
             gt_meta = torch.from_numpy(np.concatenate([g[1] for g, _ in self.frames] + [np.zeros((1, 2), np.int32)])).to(dev)
-            dt, dt_meta = self._detections(dev)
+            dt, dt_meta, dt_img = self._detections(dev)
             off = torch.from_numpy(np.concatenate([np.r_[0, np.cumsum(n_gt)], np.r_[0, np.cumsum(n_dt)]]).astype(np.int32)).to(dev)
             gt_off, dt_off = off[: n_frames + 1], off[n_frames + 1:]
             pairs = (dt_off[1:] - dt_off[:-1]).long() * (gt_off[1:] - gt_off[:-1]).long()
             ov_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(pairs, 0)])
             n_pairs = int((n_dt * n_gt).sum())
-            ov = torch.empty((2, max(n_pairs, 1)), dtype=torch.float32, device=dev)
-            combos = (L.KittiCombo * n_combos)(*[
-                L.KittiCombo(CLASS_CODE[c], CLASS_CODE.get(NEIGHBOUR[c]) if NEIGHBOUR[c] else -1, d, 0 if m == "bev" else 1,
-                             MIN_OVERLAP[o][c]) for o, c, m, d in self.combos])
+            ov = torch.empty((3 if n_img else 2, max(n_pairs, 1)), dtype=torch.float32, device=dev)  # BEV, 3-D (, 2-D)
+            rows = [L.KittiCombo(CLASS_CODE[c], CLASS_CODE.get(NEIGHBOUR[c]) if NEIGHBOUR[c] else -1, d, 1 if m == "3d" else 0,
+                                 min_overlap(o, c, m)) for o, c, m, d in self.combos]
+            combos, img_combos = (L.KittiCombo * n3)(*rows[:n3]), (L.KittiCombo * n_img)(*rows[n3:])
             cap = max(G, 1)
             ints = torch.zeros(2 * n_combos + n_combos * SAMPLE_PTS * 3, dtype=torch.int32, device=dev)
             tp_count, n_valid, counts = ints[:n_combos], ints[n_combos:2 * n_combos], ints[2 * n_combos:]
@@ -305,47 +354,80 @@ class KittiEvaluator:
             n_thr = torch.zeros(n_combos, dtype=torch.int32, device=dev)
             ap = torch.zeros((n_combos, 2), dtype=torch.float64, device=dev)
             lib, st, what = L.lib(), L.stream_ptr(), "KittiEvaluator.compute"
-            _check(lib.v3d_kitti_eval_overlaps(L.ptr(gt), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_off), L.ptr(ov_off), n_frames,
-                                               max_dt, max_gt, L.ptr(ov[0]), L.ptr(ov[1]), st), what, max_dt, max_gt)
+            if n3:
+                _check(lib.v3d_kitti_eval_overlaps(L.ptr(gt), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_off), L.ptr(ov_off), n_frames,
+                                                   max_dt, max_gt, L.ptr(ov[0]), L.ptr(ov[1]), st), what, max_dt, max_gt)
             frame_args = (L.ptr(gt_meta), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_meta), L.ptr(dt_off), L.ptr(ov_off), L.ptr(ov[0]),
-                          L.ptr(ov[1]), n_frames, max_dt, max_gt, combos, n_combos)
+                          L.ptr(ov[1]), n_frames, max_dt, max_gt, combos, n3)
             _check(lib.v3d_kitti_eval_pass1(*frame_args, cap, L.ptr(tp_count), L.ptr(tp_scores), L.ptr(n_valid), st), what,
                    max_dt, max_gt)
+            if n_img:  # the bbox combos: pass 1 on ov_2d (as its BEV matrix, metric 0), pointers at their slice
+                gt_img = torch.from_numpy(np.concatenate([g[2] for g, _ in self.frames] + [np.zeros((1, 5), np.float32)])).to(dev)
+                _check(lib.v3d_kitti_eval_overlaps_image(L.ptr(gt_img), L.ptr(gt_off), L.ptr(dt_img), L.ptr(dt_off),
+                                                         L.ptr(ov_off), n_frames, max_dt, max_gt, L.ptr(ov[2]), st),
+                       what, max_dt, max_gt)
+                _check(lib.v3d_kitti_eval_pass1(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_meta), L.ptr(dt_off),
+                                                L.ptr(ov_off), L.ptr(ov[2]), L.ptr(ov[2]), n_frames, max_dt, max_gt, img_combos,
+                                                n_img, cap, L.ptr(tp_count[n3:]), L.ptr(tp_scores[n3:]), L.ptr(n_valid[n3:]), st),
+                       what, max_dt, max_gt)
             sorted_scores = torch.sort(tp_scores, dim=1, descending=True).values.contiguous()
             L.check(lib.v3d_kitti_eval_thresholds(L.ptr(sorted_scores), cap, L.ptr(tp_count), L.ptr(n_valid), n_combos, L.ptr(thr),
                                                   L.ptr(n_thr), st), what)
             _check(lib.v3d_kitti_eval_pass2(*frame_args, L.ptr(thr), L.ptr(n_thr), L.ptr(counts), st), what, max_dt, max_gt)
+            parts = []
+            if n_img:
+                sim = torch.zeros((n_img, SAMPLE_PTS), dtype=torch.int64, device=dev)
+                aos = torch.zeros((n_img, 2), dtype=torch.float64, device=dev)
+                counts_img = counts[n3 * SAMPLE_PTS * 3:]
+                _check(lib.v3d_kitti_eval_pass2_image(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(gt_img), L.ptr(dt), L.ptr(dt_meta),
+                                                      L.ptr(dt_off), L.ptr(dt_img), L.ptr(ov_off), L.ptr(ov[2]), n_frames, max_dt,
+                                                      max_gt, img_combos, n_img, L.ptr(thr[n3:]), L.ptr(n_thr[n3:]),
+                                                      L.ptr(counts_img), L.ptr(sim), st), what, max_dt, max_gt)
+                L.check(lib.v3d_kitti_eval_aos(L.ptr(counts_img), L.ptr(sim), L.ptr(n_thr[n3:]), n_img, L.ptr(aos), st), what)
+                parts = [aos.flatten(), sim.double().flatten() * 2.0 ** -32]
             L.check(lib.v3d_kitti_eval_ap(L.ptr(counts), L.ptr(n_thr), n_combos, L.ptr(ap), st), what)
-            out = torch.cat([ap.flatten(), n_valid.double(), n_thr.double(), thr.double().flatten(), counts.double()])
+            out = torch.cat([ap.flatten(), n_valid.double(), n_thr.double(), thr.double().flatten(), counts.double()] + parts)
             return out.cpu().numpy()  # the one host read
 
     def _unpack(self, packed):
-        n = len(self.combos)
+        n, n3 = len(self.combos), self.n_camera_combos
+        n_img = n - n3
         ap = packed[: 2 * n].reshape(n, 2)
         n_valid = packed[2 * n: 3 * n].astype(np.int64)
         n_thr = packed[3 * n: 4 * n].astype(np.int64)
         thr = packed[4 * n: 4 * n + n * SAMPLE_PTS].reshape(n, SAMPLE_PTS)
-        counts = packed[4 * n + n * SAMPLE_PTS:].reshape(n, SAMPLE_PTS, 3).astype(np.int64)
+        at = 4 * n + n * SAMPLE_PTS
+        counts = packed[at: at + n * SAMPLE_PTS * 3].reshape(n, SAMPLE_PTS, 3).astype(np.int64)
+        at += n * SAMPLE_PTS * 3
+        aos = packed[at: at + 2 * n_img].reshape(n_img, 2)
+        sim = packed[at + 2 * n_img:].reshape(n_img, SAMPLE_PTS)
         result = {o: {c: {m: {"R11": [0.0] * 3, "R40": [0.0] * 3} for m in self.metrics} for c in self.classes}
                   for o in self.overlaps}
         self.details = {}
         for k, (o, c, m, d) in enumerate(self.combos):
-            result[o][c][m]["R11"][d] = float(ap[k, 0])
-            result[o][c][m]["R40"][d] = float(ap[k, 1])
+            if m in self.metrics:
+                result[o][c][m]["R11"][d] = float(ap[k, 0])
+                result[o][c][m]["R40"][d] = float(ap[k, 1])
             self.details[(o, c, m, d)] = dict(n_valid_gt=int(n_valid[k]), thresholds=thr[k, : n_thr[k]].copy(),
                                               counts=counts[k, : n_thr[k]].copy())
+            if k >= n3:
+                self.details[(o, c, m, d)]["similarity"] = sim[k - n3, : n_thr[k]].copy()
+                if "aos" in self.metrics:
+                    result[o][c]["aos"]["R11"][d] = float(aos[k - n3, 0])
+                    result[o][c]["aos"]["R40"][d] = float(aos[k - n3, 1])
         self.result = result
 
     def summary(self, r11=False):
-        """The usual text block, one line per (overlap set, class, AP kind):
-        `Car AP_R40@0.70, 0.70: bev: 89.1000, 85.2000, 80.3000  3d: ...` (R40 only unless r11)."""
+        """The usual text block, one line per (overlap set, class, AP kind), the metrics in the order asked for:
+        `Car AP_R40@0.70, 0.70: bev: 89.1000, 85.2000, 80.3000  3d: ...` (R40 only unless r11); the header holds one minimum
+        overlap per metric other than aos (aos's own when it is the only one)."""
         if self.result is None:
             self.compute()
         lines = []
         for o in self.overlaps:
             for c in self.classes:
                 for kind in (("R11", "R40") if r11 else ("R40",)):
-                    t = ", ".join(f"{MIN_OVERLAP[o][c]:.2f}" for _ in self.metrics)
+                    t = ", ".join(f"{min_overlap(o, c, m):.2f}" for m in ([m for m in self.metrics if m != "aos"] or ["aos"]))
                     parts = "  ".join(f"{m}: " + ", ".join(f"{v:.4f}" for v in self.result[o][c][m][kind]) for m in self.metrics)
                     lines.append(f"{c} AP_{kind}@{t}: {parts}")
         return "\n".join(lines)
