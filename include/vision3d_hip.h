@@ -665,14 +665,19 @@ int v3d_dense_train_backward_split(const void* bev_hi, const void* bev_lo, const
                                    const v3d_dense_train_layer* layers, int n_layers, const float* head_weight, int O, void* arena,
                                    float* dhead_weight, float* dhead_bias, void* dbev_hi, void* dbev_lo, v3d_stream_t stream);
 
-/* ---- KITTI BEV / 3-D average precision (vision3d_amd/evaluation/kitti.py; the protocol is written out in its docstring).
- * The upstream project has no evaluator.  All frames form one ragged batch: rows of frame f are [off[f], off[f+1]) of the
- * concatenated arrays, off (n_frames + 1) i32 on the device; ov_off (n_frames + 1) i64 = running sum of n_dt * n_gt.
+/* ---- KITTI 2-D bbox, BEV and 3-D average precision and average orientation similarity (AOS) (vision3d_amd/evaluation/kitti.py;
+ * the protocol is written out in its docstring).  The upstream project has no evaluator.  All frames form one ragged batch: rows
+ * of frame f are [off[f], off[f+1]) of the concatenated arrays, off (n_frames + 1) i32 on the device; ov_off (n_frames + 1) i64 =
+ * running sum of n_dt * n_gt.
  *   gt (G, 7) f32 = rectified-camera (x, y_bottom, z, h, w, l, ry); gt_meta (G, 2) i32 = (class code, flags): bit d set =
- *   "ignored at difficulty d" (occlusion / truncation / 2-D height rule, evaluated by the caller);
+ *   "ignored at difficulty d" (occlusion / truncation / 2-D height rule, evaluated by the caller), bit V3D_KITTI_DONTCARE_BIT
+ *   set = the ground truth is a DontCare region (it is also class code OTHER, so no combo counts it);
  *   dt (D, 8) f32 = the same 7 columns + score; dt_meta (D, 2) i32 = (class code, flags): bit d set = 2-D height below
  *   MIN_HEIGHT[d].  Class codes: V3D_KITTI_CODE_*.
- * A combo is one (class, difficulty, metric, minimum overlap); up to V3D_KITTI_MAX_COMBOS of them, on the HOST.
+ *   gt_img (G, 5), dt_img (D, 5) f32 = image box (x1, y1, x2, y2) and alpha (read by bbox combos only).
+ * A combo is one (class, difficulty, metric, minimum overlap); up to V3D_KITTI_MAX_COMBOS of them, on the HOST, in one array
+ * whatever their metrics.  ov holds one overlap plane per metric, ov_plane (>= sum n_dt * n_gt) floats apart: a combo reads the
+ * plane ov + metric * ov_plane (BEV, 3-D, bbox), each frame-major, row = detection, column = ground truth.
  * max_dt / max_gt (host) are the largest per-frame counts: beyond V3D_KITTI_MAX_DT / V3D_KITTI_MAX_GT every entry point
  * returns V3D_EUNSUPPORTED.  Integer counters only: results are deterministic.  No host synchronisation. */
 #define V3D_KITTI_MAX_DT 1024
@@ -685,22 +690,29 @@ int v3d_dense_train_backward_split(const void* bev_hi, const void* bev_lo, const
 #define V3D_KITTI_CODE_VAN 3
 #define V3D_KITTI_CODE_PERSON_SITTING 4
 #define V3D_KITTI_CODE_OTHER 5 /* DontCare, Misc, Truck, Tram, ... */
+#define V3D_KITTI_DONTCARE_BIT 3
+#define V3D_KITTI_METRIC_BEV 0
+#define V3D_KITTI_METRIC_3D 1
+#define V3D_KITTI_METRIC_BBOX 2 /* 2-D bbox; AOS comes from its counts */
 typedef struct {
   int32_t cls;         /* class code evaluated */
   int32_t neighbour;   /* its neighbour class code (Van for Car, Person_sitting for Pedestrian), -1: none */
   int32_t difficulty;  /* 0 easy, 1 moderate, 2 hard: the flag bit read */
-  int32_t metric;      /* 0 BEV, 1 3-D */
+  int32_t metric;      /* V3D_KITTI_METRIC_*: the overlap plane read */
   float min_overlap;   /* a pair counts when overlap > min_overlap */
 } v3d_kitti_combo;
-/* ov_bev, ov_3d (sum n_dt * n_gt) f32: BEV and 3-D IoU, frame-major, row = detection, column = ground truth, both from ONE
- * polygon clip per pair (rotated_iou.h).  BEV in the camera's (x, z) plane, extent l along (cos ry, -sin ry). */
+/* ov_bev, ov_3d (sum n_dt * n_gt) f32: BEV and 3-D IoU, both from ONE polygon clip per pair (rotated_iou.h).  BEV in the
+ * camera's (x, z) plane, extent l along (cos ry, -sin ry). */
 int v3d_kitti_eval_overlaps(const float* gt, const int32_t* gt_off, const float* dt, const int32_t* dt_off, const int64_t* ov_off,
                             int n_frames, int max_dt, int max_gt, float* ov_bev, float* ov_3d, v3d_stream_t stream);
+/* ov_2d (sum n_dt * n_gt) f32: IoU of the image boxes (no +1), computed in double. */
+int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t* gt_off, const float* dt_img, const int32_t* dt_off,
+                                  const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_2d, v3d_stream_t stream);
 /* Pass 1 (greedy assignment without false positives): appends every true positive's score to its combo's row of tp_scores
  * (n_combos, capacity) at tp_count[combo] (atomic cursor; order arbitrary, capacity >= G suffices) and adds the combo's valid
- * ground truths to n_valid[combo].  tp_count and n_valid must be zero on entry. */
+ * ground truths to n_valid[combo].  tp_count and n_valid must be zero on entry.  V3D_EINVAL for a combo metric outside 0..2. */
 int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta, const int32_t* dt_off,
-                         const int64_t* ov_off, const float* ov_bev, const float* ov_3d, int n_frames, int max_dt, int max_gt,
+                         const int64_t* ov_off, const float* ov, int64_t ov_plane, int n_frames, int max_dt, int max_gt,
                          const v3d_kitti_combo* combos_host, int n_combos, int capacity, int32_t* tp_count, float* tp_scores,
                          int32_t* n_valid, v3d_stream_t stream);
 /* Score thresholds of the 41 recall positions, one lane per combo, in double: sorted_scores (n_combos, capacity) = each row of
@@ -709,39 +721,23 @@ int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_off, const fl
 int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacity, const int32_t* tp_count, const int32_t* n_valid,
                               int n_combos, float* thresholds, int32_t* n_thresholds, v3d_stream_t stream);
 /* Pass 2: one lane per threshold runs the greedy assignment with false positives; counts (n_combos, 41, 3) i32 += (tp, fp, fn).
- * counts must be zero on entry. */
-int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta, const int32_t* dt_off,
-                         const int64_t* ov_off, const float* ov_bev, const float* ov_3d, int n_frames, int max_dt, int max_gt,
-                         const v3d_kitti_combo* combos_host, int n_combos, const float* thresholds, const int32_t* n_thresholds,
-                         int32_t* counts, v3d_stream_t stream);
+ * Bbox combos also: every counted (ignored_dt == 0), unassigned detection not under the threshold whose inter / area_dt with
+ * some DontCare region exceeds min_overlap is absorbed (no FP); similarity (n_combos, 41) i64 += each frame's sum over its true
+ * positives of (1 + cos(alpha_gt - alpha_dt)) / 2 (double, ground-truth order) as 32.32 fixed point, llrint(sum * 2^32), by
+ * integer atomics: the total is deterministic and independent of frame order.  A frame adds < 2^40 (<= 256 true positives), so
+ * the total is exact below 2^31 true positives per (combo, threshold): more than 8 million frames at the per-frame limit.
+ * gt_img, dt_img and similarity may be NULL when no combo is a bbox combo; rows of other combos stay as they are.  counts and
+ * similarity must be zero on entry.  V3D_EINVAL for a combo metric outside 0..2 or a bbox combo without the image arrays. */
+int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt, const int32_t* dt_meta,
+                         const int32_t* dt_off, const float* dt_img, const int64_t* ov_off, const float* ov, int64_t ov_plane,
+                         int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,
+                         const float* thresholds, const int32_t* n_thresholds, int32_t* counts, int64_t* similarity,
+                         v3d_stream_t stream);
 /* Precision per threshold, its running maximum from the right, and ap (n_combos, 2) f64 = (AP_R11, AP_R40) in percent, summed in
- * the order of the definition (bit-reproducible). */
-int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresholds, int n_combos, double* ap, v3d_stream_t stream);
-/* ---- KITTI 2-D bbox AP and average orientation similarity (AOS), on combos of their own.  Extra inputs, in the layouts above:
- *   gt_img (G, 5), dt_img (D, 5) f32 = image box (x1, y1, x2, y2) and alpha; bit V3D_KITTI_DONTCARE_BIT of gt_meta[1] set = the
- *   ground truth is a DontCare region (it is also class code OTHER, so no combo counts it).
- * The bbox combos run v3d_kitti_eval_pass1 with ov_2d passed as ov_bev (metric 0), then the thresholds and ap as above, and
- * v3d_kitti_eval_pass2_image in place of v3d_kitti_eval_pass2. */
-#define V3D_KITTI_DONTCARE_BIT 3
-/* ov_2d (sum n_dt * n_gt) f32: IoU of the image boxes (no +1), frame-major like ov_bev, computed in double. */
-int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t* gt_off, const float* dt_img, const int32_t* dt_off,
-                                  const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_2d, v3d_stream_t stream);
-/* Pass 2 of the bbox metric (the combos' `metric` is not read): the greedy assignment of v3d_kitti_eval_pass2 on ov_2d, then
- * every counted (ignored_dt == 0), unassigned detection not under the threshold whose inter / area_dt with some DontCare region
- * exceeds min_overlap is absorbed (no FP).  counts (n_combos, 41, 3) i32 += (tp, fp, fn); similarity (n_combos, 41) i64 += each
- * frame's sum over its true positives of (1 + cos(alpha_gt - alpha_dt)) / 2 (double, ground-truth order) as 32.32 fixed point,
- * llrint(sum * 2^32), by integer atomics: the total is deterministic and independent of frame order.  A frame adds < 2^40
- * (<= 256 true positives), so the total is exact below 2^31 true positives per (combo, threshold): more than 8 million frames
- * at the per-frame limit.  counts and similarity must be zero on entry. */
-int v3d_kitti_eval_pass2_image(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt,
-                               const int32_t* dt_meta, const int32_t* dt_off, const float* dt_img, const int64_t* ov_off,
-                               const float* ov_2d, int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host,
-                               int n_combos, const float* thresholds, const int32_t* n_thresholds, int32_t* counts,
-                               int64_t* similarity, v3d_stream_t stream);
-/* aos (n_combos, 2) f64 = (AOS_R11, AOS_R40) in percent: per threshold k < n_thresholds, similarity * 2^-32 / (tp + fp) (0 when
- * tp + fp == 0 and for k >= n_thresholds), its running maximum from the right, summed as in v3d_kitti_eval_ap. */
-int v3d_kitti_eval_aos(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos, double* aos,
-                       v3d_stream_t stream);
+ * the order of the definition (bit-reproducible).  With similarity (non-NULL), aos (n_combos, 2) f64 = (AOS_R11, AOS_R40) the same
+ * way from similarity * 2^-32 / (tp + fp) (0 when tp + fp == 0 and for k >= n_thresholds); meaningful for bbox combos. */
+int v3d_kitti_eval_ap(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos, double* ap,
+                      double* aos, v3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,8 @@
 """CPU: the KITTI 2-D bbox AP and AOS rules (vision3d_amd/evaluation/kitti.py) restated in float64
 (tests/kitti_eval_image_ref.py) on hand cases with known answers: DontCare absorption, AOS against bbox AP, the per-metric
-minimum overlaps, and the host-side DontCare flag and image rows of the evaluator."""
+minimum overlaps, the host-side DontCare flag and image rows of the evaluator, and the combo-metric argument checks of the C
+entry points."""
+import ctypes
 import os
 import sys
 
@@ -11,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kitti_eval_image_ref as RI  # noqa: E402
 import kitti_eval_ref as R  # noqa: E402
 
+from vision3d_amd import _lib as L  # noqa: E402
 from vision3d_amd.evaluation import kitti as E  # noqa: E402
 
 
@@ -121,3 +124,26 @@ def test_synthetic_generator_properties():
     assert absorbed_candidates > 10 and short_under_dc > 0
     res, det = RI.evaluate([RI.make_frame(g, d) for g, d in pairs], classes=("Car",), overlap_sets=("strict",))
     assert 0 < res["strict"]["Car"]["aos"]["R40"][1] < res["strict"]["Car"]["bbox"]["R40"][1]
+
+
+def test_pass1_pass2_refuse_bad_combo_metrics_before_launch():
+    """V3D_EINVAL for a combo metric outside 0..2 (pass 1 and pass 2) and for a bbox combo without the image arrays or the
+    similarity output (pass 2), returned before any launch: the library loads without a GPU (test_capi_symbols.py).  Every
+    pointer is a host buffer that the checks never read."""
+    lib, einval = L.lib(), -1
+    buf = (ctypes.c_int64 * 64)()
+    p = ctypes.addressof(buf)
+
+    def combos(metric):
+        return (L.KittiCombo * 2)(L.KittiCombo(0, 3, 1, E.METRIC_BEV, 0.7), L.KittiCombo(0, 3, 1, metric, 0.7))
+
+    def pass1(c):
+        return lib.v3d_kitti_eval_pass1(p, p, p, p, p, p, p, 1, 1, 1, 1, c, 2, 1, p, p, p, None)
+
+    def pass2(c, img=p, sim=p):
+        return lib.v3d_kitti_eval_pass2(p, p, img, p, p, p, img, p, p, 1, 1, 1, 1, c, 2, p, p, p, sim, None)
+
+    for bad in (-1, 3):
+        assert pass1(combos(bad)) == einval and pass2(combos(bad)) == einval
+    assert pass2(combos(E.METRIC_BBOX), img=None) == einval
+    assert pass2(combos(E.METRIC_BBOX), sim=None) == einval

@@ -138,14 +138,12 @@ _SIGNATURES = {
     "v3d_dense_train_backward_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_dense_train_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "v3d_kitti_eval_overlaps": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "v3d_kitti_eval_pass1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "v3d_kitti_eval_thresholds": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "v3d_kitti_eval_pass2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
-    "v3d_kitti_eval_ap": (_i, [_vp, _vp, _i, _vp, _vp]),
     "v3d_kitti_eval_overlaps_image": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
-    "v3d_kitti_eval_pass2_image": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp,
-                                        _vp]),
-    "v3d_kitti_eval_aos": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "v3d_kitti_eval_pass1": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "v3d_kitti_eval_thresholds": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "v3d_kitti_eval_pass2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp, _i, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "v3d_kitti_eval_ap": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
 }
 
 

@@ -1,22 +1,24 @@
-// kitti_eval.hip -- KITTI BEV / 3-D average precision on the device (vision3d_amd/evaluation/kitti.py states the protocol).
+// kitti_eval.hip -- KITTI 2-D bbox, BEV and 3-D average precision and AOS on the device (vision3d_amd/evaluation/kitti.py
+// states the protocol).
 //
-// All frames go in one ragged batch (include/vision3d_hip.h "KITTI BEV / 3-D average precision"); five launches whatever the
-// frame count, no host reads in between:
-//   1. overlaps    one workgroup per (frame, chunk of 256 detection rows): the frame's ground truths are prepped into LDS once,
-//                  each lane preps its detection once and clips it against every ground truth with the rotated-IoU core
-//                  (rotated_iou.h, clipper work arrays in per-wave LDS slabs); BEV and 3-D IoU come from the same intersection;
-//   2. pass 1      one wave per (frame, combo): ground truths in file order, lanes split the detection scan, a wave argmax
-//                  (score, then earliest index) picks the match; true-positive scores are appended through an atomic cursor;
-//   3. thresholds  one lane per combo walks its descending TP scores in double (the 41-point recall sampling);
-//   4. pass 2      one wave per (frame, combo), one lane per threshold: each lane runs its own greedy assignment with an
-//                  "assigned" bitmask in LDS and adds integer (tp, fp, fn) with global atomics (order-free, deterministic);
-//   5. ap          one lane per combo: precision, its running maximum from the right, R11 / R40 sums in definition order.
-// The 2-D bbox / AOS metrics reuse pass 1, the thresholds and ap on their own combos and add three kernels:
-//   overlaps_image  the grid of stage 1: 2-D IoU of (x1, y1, x2, y2) image boxes into ov_2d (same layout as ov_bev);
-//   pass2_image     pass 2 on ov_2d plus the DontCare step (unassigned counted detections whose inter / area_dt with a DontCare
-//                   region exceeds the minimum overlap are no false positives) and each lane's true-positive similarity sum
-//                   (1 + cos(alpha_gt - alpha_dt)) / 2 in double, added as 32.32 fixed point with 64-bit integer atomics;
-//   aos             one lane per combo: similarity / (tp + fp), running maximum, R11 / R40 as in ap.
+// All frames go in one ragged batch (include/vision3d_hip.h "KITTI 2-D bbox, BEV and 3-D average precision"); one combo array
+// covers every metric, and a combo reads the overlap plane ov + metric * ov_plane (0 BEV, 1 3-D, 2 bbox).  Whatever the frame
+// count, no host reads in between:
+//   1. overlaps        one workgroup per (frame, chunk of 256 detection rows): the frame's ground truths are prepped into LDS
+//                      once, each lane preps its detection once and clips it against every ground truth with the rotated-IoU
+//                      core (rotated_iou.h, clipper work arrays in per-wave LDS slabs); BEV and 3-D IoU come from the same
+//                      intersection;
+//      overlaps_image  (bbox) the same grid: 2-D IoU of (x1, y1, x2, y2) image boxes in double into the bbox plane;
+//   2. pass 1          one wave per (frame, combo): ground truths in file order, lanes split the detection scan, a wave argmax
+//                      (score, then earliest index) picks the match; true-positive scores are appended through an atomic cursor;
+//   3. thresholds      one lane per combo walks its descending TP scores in double (the 41-point recall sampling);
+//   4. pass 2          one wave per (frame, combo), one lane per threshold: each lane runs its own greedy assignment with an
+//                      "assigned" bitmask in LDS and adds integer (tp, fp, fn) with global atomics (order-free, deterministic);
+//                      bbox combos add the DontCare step (unassigned counted detections whose inter / area_dt with a DontCare
+//                      region exceeds the minimum overlap are no false positives) and each lane's true-positive similarity sum
+//                      (1 + cos(alpha_gt - alpha_dt)) / 2 in double, added as 32.32 fixed point with 64-bit integer atomics;
+//   5. ap              one lane per combo: precision (and with the similarity, similarity / (tp + fp)), its running maximum
+//                      from the right, R11 / R40 sums in definition order.
 // Limits: 1 024 detections (16 bitmask words per lane in pass 2, 16 register bits per lane in pass 1) and 256 ground truths
 // (one LDS slot per thread in stage 1) per frame.
 #include "v3d_common.h"
@@ -100,7 +102,7 @@ __device__ __forceinline__ int ignored_dt(const int* meta, const v3d_kitti_combo
 __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass1_kernel(const int* __restrict__ gt_meta, const int* __restrict__ gt_off,
                                                                 const float* __restrict__ dt, const int* __restrict__ dt_meta,
                                                                 const int* __restrict__ dt_off, const int64_t* __restrict__ ov_off,
-                                                                const float* __restrict__ ov_bev, const float* __restrict__ ov_3d,
+                                                                const float* __restrict__ ov, int64_t ov_plane,
                                                                 KeCombos combos, int n_combos, int capacity,
                                                                 int* __restrict__ tp_count, float* __restrict__ tp_scores,
                                                                 int* __restrict__ n_valid) {
@@ -112,7 +114,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass1_kernel(const int* __res
   const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
   const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
   if (ng <= 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
-  const float* ov = (c.metric ? ov_3d : ov_bev) + ov_off[f];
+  const float* ovf = ov + c.metric * ov_plane + ov_off[f];  // this frame's matrix of the combo's metric
   // this lane's detections j = lane + 64 q: "in the scan" (ignored_dt != -1) and "assigned" as bits q
   const int nq = (nd + 63) >> 6;
   unsigned live = 0u, assigned = 0u;
@@ -130,7 +132,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass1_kernel(const int* __res
     for (int q = 0; q < nq; q++) {
       if (!(((live & ~assigned) >> q) & 1u)) continue;
       const int j = lane + 64 * q;
-      if (!(ov[(size_t)j * ng + i] > c.min_overlap)) continue;
+      if (!(ovf[(size_t)j * ng + i] > c.min_overlap)) continue;
       const float s = dt[8 * (size_t)(d0 + j) + 7];
       if (best_j == 0x7fffffff || s > best_s) {  // q ascends: ties keep the earlier detection
         best_s = s;
@@ -177,17 +179,25 @@ __global__ __launch_bounds__(V3D_WAVE) void kitti_thresholds_kernel(const float*
   n_thresholds[combo] = k;
 }
 
-__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(const int* __restrict__ gt_meta, const int* __restrict__ gt_off,
-                                                                const float* __restrict__ dt, const int* __restrict__ dt_meta,
-                                                                const int* __restrict__ dt_off, const int64_t* __restrict__ ov_off,
-                                                                const float* __restrict__ ov_bev, const float* __restrict__ ov_3d,
-                                                                KeCombos combos, int n_combos, const float* __restrict__ thresholds,
-                                                                const int* __restrict__ n_thresholds, int* __restrict__ counts) {
+// Image boxes are (x1, y1, x2, y2, alpha) f32 rows; overlaps are taken in double from the f32 corners, without +1.
+__device__ __forceinline__ double img_inter(double x1, double y1, double x2, double y2, const float* g) {
+  const double iw = fmin(x2, (double)g[2]) - fmax(x1, (double)g[0]);
+  const double ih = fmin(y2, (double)g[3]) - fmax(y1, (double)g[1]);
+  return (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(
+    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
+    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
+    const int64_t* __restrict__ ov_off, const float* __restrict__ ov, int64_t ov_plane, KeCombos combos, int n_combos,
+    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
+    unsigned long long* __restrict__ similarity) {
   __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
   const int lane = threadIdx.x & 63;
   const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
   if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
   const v3d_kitti_combo c = combos.c[combo];
+  const bool image = c.metric == V3D_KITTI_METRIC_BBOX;  // (wave-uniform) the DontCare step and the similarity sum
   const int nt = n_thresholds[combo];
   if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
   const int f = blockIdx.x;
@@ -198,10 +208,17 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(const int* __res
   unsigned long long* assigned = assigned_lds[threadIdx.x >> 6] + lane;
   const int nw = (nd + 63) >> 6;
   for (int w = 0; w < nw; w++) assigned[w * 64] = 0ull;
-  const float* ov = (c.metric ? ov_3d : ov_bev) + (ng ? ov_off[f] : 0);
+  const float* ovf = ov + c.metric * ov_plane + (ng ? ov_off[f] : 0);  // this frame's matrix of the combo's metric
   int tp = 0, fp = 0, fn = 0;
+  int dc_lo = ng, dc_hi = 0;  // (bbox) the DontCare regions lie in [dc_lo, dc_hi)
+  double sim = 0.0;           // (bbox) this frame's true-positive similarities, in ground-truth order
   for (int i = 0; i < ng; i++) {
-    const int ig = ignored_gt(gt_meta + 2 * (size_t)(g0 + i), c);
+    const int* gm = gt_meta + 2 * (size_t)(g0 + i);
+    if (image && ((gm[1] >> KE_DONTCARE_BIT) & 1)) {
+      dc_lo = min(dc_lo, i);
+      dc_hi = i + 1;
+    }
+    const int ig = ignored_gt(gm, c);
     if (ig == -1) continue;
     int best = -1;
     bool best_ign = false;
@@ -211,7 +228,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(const int* __res
       if (igd == -1) continue;
       if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
       if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
-      const float o = ov[(size_t)j * ng + i];
+      const float o = ovf[(size_t)j * ng + i];
       if (!(o > c.min_overlap)) continue;
       if (igd == 0) {  // a counted detection: the largest overlap wins (earliest on ties), and displaces an ignored pick
         if (best < 0 || best_ign || o > best_ov) {
@@ -229,50 +246,81 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(const int* __res
       continue;
     }
     assigned[(best >> 6) * 64] |= 1ull << (best & 63);
-    tp += ig == 0 && !best_ign;
+    if (ig == 0 && !best_ign) {
+      tp++;
+      if (image) {
+        const double delta = (double)gt_img[5 * (size_t)(g0 + i) + 4] - (double)dt_img[5 * (size_t)(d0 + best) + 4];
+        sim += (1.0 + cos(delta)) / 2.0;
+      }
+    }
   }
+  // false positives; (bbox) an unassigned counted detection over a DontCare region (inter / area_dt > min overlap) is absorbed
   for (int j = 0; j < nd; j++) {
     if (ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != 0) continue;
     if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
-    fp += !((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull);
+    if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
+    bool absorbed = false;
+    if (image && dc_lo < dc_hi) {
+      const float* b = dt_img + 5 * (size_t)(d0 + j);
+      const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+      const double area = (x2 - x1) * (y2 - y1);  // (positive wherever the intersection is)
+      for (int i = dc_lo; i < dc_hi && !absorbed; i++) {
+        if (!((gt_meta[2 * (size_t)(g0 + i) + 1] >> KE_DONTCARE_BIT) & 1)) continue;
+        const double inter = img_inter(x1, y1, x2, y2, gt_img + 5 * (size_t)(g0 + i));
+        absorbed = inter > 0.0 && inter / area > (double)c.min_overlap;
+      }
+    }
+    fp += !absorbed;
   }
-  int* out = counts + ((size_t)combo * KE_NT + lane) * 3;
+  const size_t at = (size_t)combo * KE_NT + lane;
+  int* out = counts + at * 3;
   if (tp) atomicAdd(out + 0, tp);
   if (fp) atomicAdd(out + 1, fp);
   if (fn) atomicAdd(out + 2, fn);
+  // 32.32 fixed point: sim <= 256 per frame, so each add is < 2^40; integer adds make the total order-free and exact
+  if (image && tp) atomicAdd(similarity + at, (unsigned long long)llrint(sim * 4294967296.0));
 }
 
-__global__ __launch_bounds__(V3D_WAVE) void kitti_ap_kernel(const int* __restrict__ counts, const int* __restrict__ n_thresholds,
-                                                            int n_combos, double* __restrict__ ap) {
+// v (KE_NT ratios) -> its running maximum from the right, then out = (R11, R40) in percent, summed in definition order
+__device__ __forceinline__ void ke_r11_r40(double* v, double* out) {
+#pragma unroll
+  for (int k = KE_NT - 2; k >= 0; k--) v[k] = fmax(v[k], v[k + 1]);
+  double r11 = 0.0, r40 = 0.0;
+#pragma unroll
+  for (int k = 0; k < KE_NT; k += 4) r11 += v[k];
+#pragma unroll
+  for (int k = 1; k < KE_NT; k++) r40 += v[k];
+  out[0] = r11 / 11.0 * 100.0;
+  out[1] = r40 / 40.0 * 100.0;
+}
+
+__global__ __launch_bounds__(V3D_WAVE) void kitti_ap_kernel(const int* __restrict__ counts,
+                                                            const unsigned long long* __restrict__ similarity,
+                                                            const int* __restrict__ n_thresholds, int n_combos,
+                                                            double* __restrict__ ap, double* __restrict__ aos) {
   const int combo = threadIdx.x;
   if (combo >= n_combos) return;
   const int nt = n_thresholds[combo];
-  double prec[KE_NT];
+  double v[KE_NT];
 #pragma unroll
   for (int k = 0; k < KE_NT; k++) {
     const int* cnt = counts + ((size_t)combo * KE_NT + k) * 3;
     const int tp = cnt[0], fp = cnt[1];
-    prec[k] = (k < nt && tp + fp > 0) ? (double)tp / (double)(tp + fp) : 0.0;
+    v[k] = (k < nt && tp + fp > 0) ? (double)tp / (double)(tp + fp) : 0.0;
   }
+  ke_r11_r40(v, ap + 2 * combo);
+  if (!similarity) return;
 #pragma unroll
-  for (int k = KE_NT - 2; k >= 0; k--) prec[k] = fmax(prec[k], prec[k + 1]);
-  double r11 = 0.0, r40 = 0.0;
-#pragma unroll
-  for (int k = 0; k < KE_NT; k += 4) r11 += prec[k];
-#pragma unroll
-  for (int k = 1; k < KE_NT; k++) r40 += prec[k];
-  ap[2 * combo + 0] = r11 / 11.0 * 100.0;
-  ap[2 * combo + 1] = r40 / 40.0 * 100.0;
+  for (int k = 0; k < KE_NT; k++) {
+    const int* cnt = counts + ((size_t)combo * KE_NT + k) * 3;
+    const int den = cnt[0] + cnt[1];
+    const double s = (double)(long long)similarity[(size_t)combo * KE_NT + k] * (1.0 / 4294967296.0);
+    v[k] = (k < nt && den > 0) ? s / (double)den : 0.0;
+  }
+  ke_r11_r40(v, aos + 2 * combo);
 }
 
-// ---- 2-D bbox / AOS ------------------------------------------------------------------------------------------------------
-// Image boxes are (x1, y1, x2, y2, alpha) f32 rows; overlaps are taken in double from the f32 corners, without +1.
-__device__ __forceinline__ double img_inter(double x1, double y1, double x2, double y2, const float* g) {
-  const double iw = fmin(x2, (double)g[2]) - fmax(x1, (double)g[0]);
-  const double ih = fmin(y2, (double)g[3]) - fmax(y1, (double)g[1]);
-  return (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
-}
-
+// ---- 2-D bbox overlaps ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(V3D_BLOCK) void kitti_overlaps_image_kernel(const float* __restrict__ gt_img,
                                                                          const int* __restrict__ gt_off,
                                                                          const float* __restrict__ dt_img,
@@ -303,124 +351,6 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_overlaps_image_kernel(const f
   }
 }
 
-__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_image_kernel(
-    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
-    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
-    const int64_t* __restrict__ ov_off, const float* __restrict__ ov_2d, KeCombos combos, int n_combos,
-    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
-    unsigned long long* __restrict__ similarity) {
-  __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
-  const int lane = threadIdx.x & 63;
-  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
-  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
-  const v3d_kitti_combo c = combos.c[combo];
-  const int nt = n_thresholds[combo];
-  if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
-  const int f = blockIdx.x;
-  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
-  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
-  if (ng < 0 || nd < 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
-  const float thresh = thresholds[combo * KE_NT + lane];
-  unsigned long long* assigned = assigned_lds[threadIdx.x >> 6] + lane;
-  const int nw = (nd + 63) >> 6;
-  for (int w = 0; w < nw; w++) assigned[w * 64] = 0ull;
-  const float* ov = ov_2d + (ng ? ov_off[f] : 0);
-  int tp = 0, fp = 0, fn = 0;
-  int dc_lo = ng, dc_hi = 0;  // the DontCare regions lie in [dc_lo, dc_hi)
-  double sim = 0.0;           // this frame's true-positive similarities, in ground-truth order
-  for (int i = 0; i < ng; i++) {
-    const int* gm = gt_meta + 2 * (size_t)(g0 + i);
-    if ((gm[1] >> KE_DONTCARE_BIT) & 1) {
-      dc_lo = min(dc_lo, i);
-      dc_hi = i + 1;
-    }
-    const int ig = ignored_gt(gm, c);
-    if (ig == -1) continue;
-    int best = -1;
-    bool best_ign = false;
-    float best_ov = 0.f;
-    for (int j = 0; j < nd; j++) {  // the greedy rule of kitti_pass2_kernel
-      const int igd = ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c);
-      if (igd == -1) continue;
-      if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
-      if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
-      const float o = ov[(size_t)j * ng + i];
-      if (!(o > c.min_overlap)) continue;
-      if (igd == 0) {
-        if (best < 0 || best_ign || o > best_ov) {
-          best = j;
-          best_ov = o;
-          best_ign = false;
-        }
-      } else if (best < 0) {
-        best = j;
-        best_ign = true;
-      }
-    }
-    if (best < 0) {
-      fn += ig == 0;
-      continue;
-    }
-    assigned[(best >> 6) * 64] |= 1ull << (best & 63);
-    if (ig == 0 && !best_ign) {
-      tp++;
-      const double delta = (double)gt_img[5 * (size_t)(g0 + i) + 4] - (double)dt_img[5 * (size_t)(d0 + best) + 4];
-      sim += (1.0 + cos(delta)) / 2.0;
-    }
-  }
-  // false positives; an unassigned counted detection over a DontCare region (inter / area_dt > min overlap) is absorbed
-  for (int j = 0; j < nd; j++) {
-    if (ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != 0) continue;
-    if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
-    if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
-    bool absorbed = false;
-    if (dc_lo < dc_hi) {
-      const float* b = dt_img + 5 * (size_t)(d0 + j);
-      const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
-      const double area = (x2 - x1) * (y2 - y1);  // (positive wherever the intersection is)
-      for (int i = dc_lo; i < dc_hi && !absorbed; i++) {
-        if (!((gt_meta[2 * (size_t)(g0 + i) + 1] >> KE_DONTCARE_BIT) & 1)) continue;
-        const double inter = img_inter(x1, y1, x2, y2, gt_img + 5 * (size_t)(g0 + i));
-        absorbed = inter > 0.0 && inter / area > (double)c.min_overlap;
-      }
-    }
-    fp += !absorbed;
-  }
-  const size_t at = (size_t)combo * KE_NT + lane;
-  int* out = counts + at * 3;
-  if (tp) atomicAdd(out + 0, tp);
-  if (fp) atomicAdd(out + 1, fp);
-  if (fn) atomicAdd(out + 2, fn);
-  // 32.32 fixed point: sim <= 256 per frame, so each add is < 2^40; integer adds make the total order-free and exact
-  if (tp) atomicAdd(similarity + at, (unsigned long long)llrint(sim * 4294967296.0));
-}
-
-__global__ __launch_bounds__(V3D_WAVE) void kitti_aos_kernel(const int* __restrict__ counts,
-                                                             const unsigned long long* __restrict__ similarity,
-                                                             const int* __restrict__ n_thresholds, int n_combos,
-                                                             double* __restrict__ aos) {
-  const int combo = threadIdx.x;
-  if (combo >= n_combos) return;
-  const int nt = n_thresholds[combo];
-  double a[KE_NT];
-#pragma unroll
-  for (int k = 0; k < KE_NT; k++) {
-    const int* cnt = counts + ((size_t)combo * KE_NT + k) * 3;
-    const int den = cnt[0] + cnt[1];
-    const double s = (double)(long long)similarity[(size_t)combo * KE_NT + k] * (1.0 / 4294967296.0);
-    a[k] = (k < nt && den > 0) ? s / (double)den : 0.0;
-  }
-#pragma unroll
-  for (int k = KE_NT - 2; k >= 0; k--) a[k] = fmax(a[k], a[k + 1]);
-  double r11 = 0.0, r40 = 0.0;
-#pragma unroll
-  for (int k = 0; k < KE_NT; k += 4) r11 += a[k];
-#pragma unroll
-  for (int k = 1; k < KE_NT; k++) r40 += a[k];
-  aos[2 * combo + 0] = r11 / 11.0 * 100.0;
-  aos[2 * combo + 1] = r40 / 40.0 * 100.0;
-}
-
 static int ke_check(int n_frames, int max_dt, int max_gt, int n_combos) {
   if (n_frames < 0 || max_dt < 0 || max_gt < 0 || n_combos < 0) return V3D_EINVAL;
   if (max_dt > V3D_KITTI_MAX_DT || max_gt > V3D_KITTI_MAX_GT || n_combos > V3D_KITTI_MAX_COMBOS) return V3D_EUNSUPPORTED;
@@ -431,6 +361,16 @@ static KeCombos ke_combos(const v3d_kitti_combo* host, int n) {
   KeCombos k = {};
   for (int i = 0; i < n; i++) k.c[i] = host[i];
   return k;
+}
+
+// The metrics the combos use as bits 1 << metric, or -1 for a metric outside 0..2 (it indexes the overlap planes)
+static int ke_metrics(const v3d_kitti_combo* host, int n) {
+  int bits = 0;
+  for (int i = 0; i < n; i++) {
+    if (host[i].metric < V3D_KITTI_METRIC_BEV || host[i].metric > V3D_KITTI_METRIC_BBOX) return -1;
+    bits |= 1 << host[i].metric;
+  }
+  return bits;
 }
 
 extern "C" int v3d_kitti_eval_overlaps(const float* gt, const int32_t* gt_off, const float* dt, const int32_t* dt_off,
@@ -447,17 +387,18 @@ extern "C" int v3d_kitti_eval_overlaps(const float* gt, const int32_t* gt_off, c
 }
 
 extern "C" int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta,
-                                    const int32_t* dt_off, const int64_t* ov_off, const float* ov_bev, const float* ov_3d,
-                                    int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,
-                                    int capacity, int32_t* tp_count, float* tp_scores, int32_t* n_valid, v3d_stream_t stream) {
+                                    const int32_t* dt_off, const int64_t* ov_off, const float* ov, int64_t ov_plane, int n_frames,
+                                    int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos, int capacity,
+                                    int32_t* tp_count, float* tp_scores, int32_t* n_valid, v3d_stream_t stream) {
   const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
   if (e) return e;
-  if (capacity < 0) return V3D_EINVAL;
+  if (capacity < 0 || ov_plane < 0) return V3D_EINVAL;
   if (n_frames == 0 || n_combos == 0 || max_gt == 0) return V3D_OK;
   if (!gt_meta || !gt_off || !dt_off || !ov_off || !combos_host || !tp_count || !n_valid) return V3D_EINVAL;
-  if (max_dt > 0 && (!dt || !dt_meta || !ov_bev || !ov_3d || !tp_scores)) return V3D_EINVAL;
+  if (max_dt > 0 && (!dt || !dt_meta || !ov || !tp_scores)) return V3D_EINVAL;
+  if (ke_metrics(combos_host, n_combos) < 0) return V3D_EINVAL;
   hipLaunchKernelGGL(kitti_pass1_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov_bev, ov_3d,
+                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov, ov_plane,
                      ke_combos(combos_host, n_combos), n_combos, capacity, tp_count, tp_scores, n_valid);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
@@ -476,34 +417,42 @@ extern "C" int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacit
   return V3D_OK;
 }
 
-extern "C" int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* dt, const int32_t* dt_meta,
-                                    const int32_t* dt_off, const int64_t* ov_off, const float* ov_bev, const float* ov_3d,
-                                    int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,
-                                    const float* thresholds, const int32_t* n_thresholds, int32_t* counts, v3d_stream_t stream) {
+extern "C" int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt,
+                                    const int32_t* dt_meta, const int32_t* dt_off, const float* dt_img, const int64_t* ov_off,
+                                    const float* ov, int64_t ov_plane, int n_frames, int max_dt, int max_gt,
+                                    const v3d_kitti_combo* combos_host, int n_combos, const float* thresholds,
+                                    const int32_t* n_thresholds, int32_t* counts, int64_t* similarity, v3d_stream_t stream) {
   const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
   if (e) return e;
+  if (ov_plane < 0) return V3D_EINVAL;
   if (n_frames == 0 || n_combos == 0) return V3D_OK;
   if (!gt_off || !dt_off || !ov_off || !combos_host || !thresholds || !n_thresholds || !counts) return V3D_EINVAL;
   if (max_gt > 0 && !gt_meta) return V3D_EINVAL;
   if (max_dt > 0 && (!dt || !dt_meta)) return V3D_EINVAL;
-  if (max_dt > 0 && max_gt > 0 && (!ov_bev || !ov_3d)) return V3D_EINVAL;
+  if (max_dt > 0 && max_gt > 0 && !ov) return V3D_EINVAL;
+  const int metrics = ke_metrics(combos_host, n_combos);
+  if (metrics < 0) return V3D_EINVAL;
+  const bool bbox = (metrics >> V3D_KITTI_METRIC_BBOX) & 1;  // the DontCare step and the similarity read these
+  if (bbox && (!similarity || (max_gt > 0 && !gt_img) || (max_dt > 0 && !dt_img))) return V3D_EINVAL;
   hipLaunchKernelGGL(kitti_pass2_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov_bev, ov_3d,
-                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts);
+                     (hipStream_t)stream, gt_meta, gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov, ov_plane,
+                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts,
+                     (unsigned long long*)similarity);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }
 
-extern "C" int v3d_kitti_eval_ap(const int32_t* counts, const int32_t* n_thresholds, int n_combos, double* ap, v3d_stream_t stream) {
+extern "C" int v3d_kitti_eval_ap(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos,
+                                 double* ap, double* aos, v3d_stream_t stream) {
   const int e = ke_check(0, 0, 0, n_combos);
   if (e) return e;
   if (n_combos == 0) return V3D_OK;
-  if (!counts || !n_thresholds || !ap) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_ap_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts, n_thresholds, n_combos, ap);
+  if (!counts || !n_thresholds || !ap || (similarity && !aos)) return V3D_EINVAL;
+  hipLaunchKernelGGL(kitti_ap_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts,
+                     (const unsigned long long*)similarity, n_thresholds, n_combos, ap, aos);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }
-
 
 extern "C" int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t* gt_off, const float* dt_img, const int32_t* dt_off,
                                              const int64_t* ov_off, int n_frames, int max_dt, int max_gt, float* ov_2d,
@@ -514,38 +463,6 @@ extern "C" int v3d_kitti_eval_overlaps_image(const float* gt_img, const int32_t*
   if (!gt_img || !gt_off || !dt_img || !dt_off || !ov_off || !ov_2d) return V3D_EINVAL;
   hipLaunchKernelGGL(kitti_overlaps_image_kernel, dim3(n_frames, v3d_ceil_div(max_dt, V3D_BLOCK)), dim3(V3D_BLOCK), 0,
                      (hipStream_t)stream, gt_img, gt_off, dt_img, dt_off, ov_off, ov_2d);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
-}
-
-extern "C" int v3d_kitti_eval_pass2_image(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt,
-                                          const int32_t* dt_meta, const int32_t* dt_off, const float* dt_img, const int64_t* ov_off,
-                                          const float* ov_2d, int n_frames, int max_dt, int max_gt,
-                                          const v3d_kitti_combo* combos_host, int n_combos, const float* thresholds,
-                                          const int32_t* n_thresholds, int32_t* counts, int64_t* similarity, v3d_stream_t stream) {
-  const int e = ke_check(n_frames, max_dt, max_gt, n_combos);
-  if (e) return e;
-  if (n_frames == 0 || n_combos == 0) return V3D_OK;
-  if (!gt_off || !dt_off || !ov_off || !combos_host || !thresholds || !n_thresholds || !counts || !similarity) return V3D_EINVAL;
-  if (max_gt > 0 && (!gt_meta || !gt_img)) return V3D_EINVAL;
-  if (max_dt > 0 && (!dt || !dt_meta || !dt_img)) return V3D_EINVAL;
-  if (max_dt > 0 && max_gt > 0 && !ov_2d) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_pass2_image_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, gt_meta, gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov_2d,
-                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts,
-                     (unsigned long long*)similarity);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
-}
-
-extern "C" int v3d_kitti_eval_aos(const int32_t* counts, const int64_t* similarity, const int32_t* n_thresholds, int n_combos,
-                                  double* aos, v3d_stream_t stream) {
-  const int e = ke_check(0, 0, 0, n_combos);
-  if (e) return e;
-  if (n_combos == 0) return V3D_OK;
-  if (!counts || !similarity || !n_thresholds || !aos) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_aos_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts,
-                     (const unsigned long long*)similarity, n_thresholds, n_combos, aos);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

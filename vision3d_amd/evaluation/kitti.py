@@ -69,6 +69,8 @@ MIN_OVERLAP = {"strict": {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5},
                "loose": {"Car": 0.5, "Pedestrian": 0.25, "Cyclist": 0.25}}  # BEV and 3-D
 MIN_OVERLAP_IMAGE = {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5}  # bbox and aos, in both overlap sets
 METRICS = ("bbox", "bev", "3d", "aos")
+METRIC_BEV, METRIC_3D, METRIC_BBOX = 0, 1, 2  # v3d_kitti_combo.metric (V3D_KITTI_METRIC_*): the overlap plane a combo reads
+METRIC_CODE = {"bev": METRIC_BEV, "3d": METRIC_3D, "bbox": METRIC_BBOX}
 DONTCARE_BIT = 3  # gt_meta[1] bit: the ground truth is a DontCare region (V3D_KITTI_DONTCARE_BIT)
 NEIGHBOUR = {"Car": "Van", "Pedestrian": "Person_sitting", "Cyclist": None}
 CLASS_CODE = {"Car": 0, "Pedestrian": 1, "Cyclist": 2, "Van": 3, "Person_sitting": 4}  # every other name: OTHER
@@ -229,7 +231,6 @@ class KittiEvaluator:
         # device combos: BEV / 3-D first, then the bbox combos (which also carry aos)
         self.combos = [(o, c, m, d) for o in self.overlaps for c in self.classes for m in self.metrics if m in ("bev", "3d")
                        for d in range(3)]
-        self.n_camera_combos = len(self.combos)
         self.image = "bbox" in self.metrics or "aos" in self.metrics
         if self.image:
             self.combos += [(o, c, "bbox", d) for o in self.overlaps for c in self.classes for d in range(3)]
@@ -313,39 +314,48 @@ class KittiEvaluator:
                 img[pos] = torch.cat([box2d, alpha.float()[:, None]], 1)
         return dt, meta, img
 
+    def _layout(self):
+        """(name, shape) of every per-combo output, in the order of compute()'s one host read; aos and similarity (its 32.32
+        sums scaled to float) only with bbox combos, one row per combo."""
+        n = len(self.combos)
+        out = [("ap", (n, 2)), ("n_valid", (n,)), ("n_thr", (n,)), ("thr", (n, SAMPLE_PTS)), ("counts", (n, SAMPLE_PTS, 3))]
+        return out + ([("aos", (n, 2)), ("similarity", (n, SAMPLE_PTS))] if self.image else [])
+
     def compute(self):
         """Evaluates every frame added so far -> result[overlap_set][class][metric]["R11" | "R40"] = [easy, moderate, hard] in
         percent.  Per-combo detail (n_valid_gt, thresholds, (tp, fp, fn) per threshold; bbox combos also the similarity sum
         per threshold) lands in `self.details`, keyed (overlap_set, class, "bev" | "3d" | "bbox", difficulty)."""
-        n_frames, n_combos = len(self.frames), len(self.combos)
-        n_img = n_combos - self.n_camera_combos
         n_gt = np.array([len(g[0]) for g, _ in self.frames], np.int64)
         n_dt = np.array([len(d[1]) if d[0] == "labels" else d[1].shape[0] for _, d in self.frames], np.int64)
-        packed = np.zeros(n_combos * (2 + 2 + SAMPLE_PTS + 3 * SAMPLE_PTS) + n_img * (2 + SAMPLE_PTS))
-        if n_frames:
+        if self.frames:
             packed = self._run(n_gt, n_dt)
+        else:
+            packed = np.zeros(sum(int(np.prod(shape)) for _, shape in self._layout()))
         self._unpack(packed)
         return self.result
 
     def _run(self, n_gt, n_dt):
         dev = self._device()
-        n_frames, n_combos, n3 = len(self.frames), len(self.combos), self.n_camera_combos
-        n_img = n_combos - n3
+        n_frames, n_combos = len(self.frames), len(self.combos)
         max_dt, max_gt = int(n_dt.max()), int(n_gt.max())
         G = int(n_gt.sum())
         with L.device_guard(dev):
             gt = torch.from_numpy(np.concatenate([g[0] for g, _ in self.frames] + [np.zeros((1, 7), np.float32)])).to(dev)
             gt_meta = torch.from_numpy(np.concatenate([g[1] for g, _ in self.frames] + [np.zeros((1, 2), np.int32)])).to(dev)
+            gt_img = None
+            if self.image:
+                gt_img = torch.from_numpy(np.concatenate([g[2] for g, _ in self.frames] + [np.zeros((1, 5), np.float32)])).to(dev)
             dt, dt_meta, dt_img = self._detections(dev)
             off = torch.from_numpy(np.concatenate([np.r_[0, np.cumsum(n_gt)], np.r_[0, np.cumsum(n_dt)]]).astype(np.int32)).to(dev)
             gt_off, dt_off = off[: n_frames + 1], off[n_frames + 1:]
             pairs = (dt_off[1:] - dt_off[:-1]).long() * (gt_off[1:] - gt_off[:-1]).long()
             ov_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(pairs, 0)])
             n_pairs = int((n_dt * n_gt).sum())
-            ov = torch.empty((3 if n_img else 2, max(n_pairs, 1)), dtype=torch.float32, device=dev)  # BEV, 3-D (, 2-D)
-            rows = [L.KittiCombo(CLASS_CODE[c], CLASS_CODE.get(NEIGHBOUR[c]) if NEIGHBOUR[c] else -1, d, 1 if m == "3d" else 0,
-                                 min_overlap(o, c, m)) for o, c, m, d in self.combos]
-            combos, img_combos = (L.KittiCombo * n3)(*rows[:n3]), (L.KittiCombo * n_img)(*rows[n3:])
+            # one plane per metric code (BEV, 3-D, bbox); a combo reads plane `metric`
+            ov = torch.empty((3 if self.image else 2, max(n_pairs, 1)), dtype=torch.float32, device=dev)
+            combos = (L.KittiCombo * n_combos)(*[
+                L.KittiCombo(CLASS_CODE[c], CLASS_CODE.get(NEIGHBOUR[c]) if NEIGHBOUR[c] else -1, d, METRIC_CODE[m],
+                             min_overlap(o, c, m)) for o, c, m, d in self.combos])
             cap = max(G, 1)
             ints = torch.zeros(2 * n_combos + n_combos * SAMPLE_PTS * 3, dtype=torch.int32, device=dev)
             tp_count, n_valid, counts = ints[:n_combos], ints[n_combos:2 * n_combos], ints[2 * n_combos:]
@@ -353,68 +363,55 @@ class KittiEvaluator:
             thr = torch.zeros((n_combos, SAMPLE_PTS), dtype=torch.float32, device=dev)
             n_thr = torch.zeros(n_combos, dtype=torch.int32, device=dev)
             ap = torch.zeros((n_combos, 2), dtype=torch.float64, device=dev)
+            sim = torch.zeros((n_combos, SAMPLE_PTS), dtype=torch.int64, device=dev) if self.image else None
+            aos = torch.zeros((n_combos, 2), dtype=torch.float64, device=dev) if self.image else None
             lib, st, what = L.lib(), L.stream_ptr(), "KittiEvaluator.compute"
-            if n3:
+            if {"bev", "3d"} & set(self.metrics):
                 _check(lib.v3d_kitti_eval_overlaps(L.ptr(gt), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_off), L.ptr(ov_off), n_frames,
-                                                   max_dt, max_gt, L.ptr(ov[0]), L.ptr(ov[1]), st), what, max_dt, max_gt)
-            frame_args = (L.ptr(gt_meta), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_meta), L.ptr(dt_off), L.ptr(ov_off), L.ptr(ov[0]),
-                          L.ptr(ov[1]), n_frames, max_dt, max_gt, combos, n3)
-            _check(lib.v3d_kitti_eval_pass1(*frame_args, cap, L.ptr(tp_count), L.ptr(tp_scores), L.ptr(n_valid), st), what,
-                   max_dt, max_gt)
-            if n_img:  # the bbox combos: pass 1 on ov_2d (as its BEV matrix, metric 0), pointers at their slice
-                gt_img = torch.from_numpy(np.concatenate([g[2] for g, _ in self.frames] + [np.zeros((1, 5), np.float32)])).to(dev)
+                                                   max_dt, max_gt, L.ptr(ov[METRIC_BEV]), L.ptr(ov[METRIC_3D]), st),
+                       what, max_dt, max_gt)
+            if self.image:
                 _check(lib.v3d_kitti_eval_overlaps_image(L.ptr(gt_img), L.ptr(gt_off), L.ptr(dt_img), L.ptr(dt_off),
-                                                         L.ptr(ov_off), n_frames, max_dt, max_gt, L.ptr(ov[2]), st),
+                                                         L.ptr(ov_off), n_frames, max_dt, max_gt, L.ptr(ov[METRIC_BBOX]), st),
                        what, max_dt, max_gt)
-                _check(lib.v3d_kitti_eval_pass1(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_meta), L.ptr(dt_off),
-                                                L.ptr(ov_off), L.ptr(ov[2]), L.ptr(ov[2]), n_frames, max_dt, max_gt, img_combos,
-                                                n_img, cap, L.ptr(tp_count[n3:]), L.ptr(tp_scores[n3:]), L.ptr(n_valid[n3:]), st),
-                       what, max_dt, max_gt)
+            batch = (n_frames, max_dt, max_gt, combos, n_combos)
+            _check(lib.v3d_kitti_eval_pass1(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(dt), L.ptr(dt_meta), L.ptr(dt_off),
+                                            L.ptr(ov_off), L.ptr(ov), ov.stride(0), *batch, cap, L.ptr(tp_count),
+                                            L.ptr(tp_scores), L.ptr(n_valid), st), what, max_dt, max_gt)
             sorted_scores = torch.sort(tp_scores, dim=1, descending=True).values.contiguous()
             L.check(lib.v3d_kitti_eval_thresholds(L.ptr(sorted_scores), cap, L.ptr(tp_count), L.ptr(n_valid), n_combos, L.ptr(thr),
                                                   L.ptr(n_thr), st), what)
-            _check(lib.v3d_kitti_eval_pass2(*frame_args, L.ptr(thr), L.ptr(n_thr), L.ptr(counts), st), what, max_dt, max_gt)
-            parts = []
-            if n_img:
-                sim = torch.zeros((n_img, SAMPLE_PTS), dtype=torch.int64, device=dev)
-                aos = torch.zeros((n_img, 2), dtype=torch.float64, device=dev)
-                counts_img = counts[n3 * SAMPLE_PTS * 3:]
-                _check(lib.v3d_kitti_eval_pass2_image(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(gt_img), L.ptr(dt), L.ptr(dt_meta),
-                                                      L.ptr(dt_off), L.ptr(dt_img), L.ptr(ov_off), L.ptr(ov[2]), n_frames, max_dt,
-                                                      max_gt, img_combos, n_img, L.ptr(thr[n3:]), L.ptr(n_thr[n3:]),
-                                                      L.ptr(counts_img), L.ptr(sim), st), what, max_dt, max_gt)
-                L.check(lib.v3d_kitti_eval_aos(L.ptr(counts_img), L.ptr(sim), L.ptr(n_thr[n3:]), n_img, L.ptr(aos), st), what)
-                parts = [aos.flatten(), sim.double().flatten() * 2.0 ** -32]
-            L.check(lib.v3d_kitti_eval_ap(L.ptr(counts), L.ptr(n_thr), n_combos, L.ptr(ap), st), what)
-            out = torch.cat([ap.flatten(), n_valid.double(), n_thr.double(), thr.double().flatten(), counts.double()] + parts)
+            _check(lib.v3d_kitti_eval_pass2(L.ptr(gt_meta), L.ptr(gt_off), L.ptr(gt_img), L.ptr(dt), L.ptr(dt_meta),
+                                            L.ptr(dt_off), L.ptr(dt_img), L.ptr(ov_off), L.ptr(ov), ov.stride(0), *batch,
+                                            L.ptr(thr), L.ptr(n_thr), L.ptr(counts), L.ptr(sim), st), what, max_dt, max_gt)
+            L.check(lib.v3d_kitti_eval_ap(L.ptr(counts), L.ptr(sim), L.ptr(n_thr), n_combos, L.ptr(ap), L.ptr(aos), st), what)
+            parts = dict(ap=ap, n_valid=n_valid, n_thr=n_thr, thr=thr, counts=counts)
+            if self.image:
+                parts.update(aos=aos, similarity=sim.double() * 2.0 ** -32)
+            out = torch.cat([parts[name].double().flatten() for name, _ in self._layout()])
             return out.cpu().numpy()  # the one host read
 
     def _unpack(self, packed):
-        n, n3 = len(self.combos), self.n_camera_combos
-        n_img = n - n3
-        ap = packed[: 2 * n].reshape(n, 2)
-        n_valid = packed[2 * n: 3 * n].astype(np.int64)
-        n_thr = packed[3 * n: 4 * n].astype(np.int64)
-        thr = packed[4 * n: 4 * n + n * SAMPLE_PTS].reshape(n, SAMPLE_PTS)
-        at = 4 * n + n * SAMPLE_PTS
-        counts = packed[at: at + n * SAMPLE_PTS * 3].reshape(n, SAMPLE_PTS, 3).astype(np.int64)
-        at += n * SAMPLE_PTS * 3
-        aos = packed[at: at + 2 * n_img].reshape(n_img, 2)
-        sim = packed[at + 2 * n_img:].reshape(n_img, SAMPLE_PTS)
+        out, at = {}, 0
+        for name, shape in self._layout():
+            size = int(np.prod(shape))
+            out[name] = packed[at: at + size].reshape(shape)
+            at += size
+        n_valid, n_thr, counts = out["n_valid"].astype(np.int64), out["n_thr"].astype(np.int64), out["counts"].astype(np.int64)
         result = {o: {c: {m: {"R11": [0.0] * 3, "R40": [0.0] * 3} for m in self.metrics} for c in self.classes}
                   for o in self.overlaps}
         self.details = {}
         for k, (o, c, m, d) in enumerate(self.combos):
             if m in self.metrics:
-                result[o][c][m]["R11"][d] = float(ap[k, 0])
-                result[o][c][m]["R40"][d] = float(ap[k, 1])
-            self.details[(o, c, m, d)] = dict(n_valid_gt=int(n_valid[k]), thresholds=thr[k, : n_thr[k]].copy(),
+                result[o][c][m]["R11"][d] = float(out["ap"][k, 0])
+                result[o][c][m]["R40"][d] = float(out["ap"][k, 1])
+            self.details[(o, c, m, d)] = dict(n_valid_gt=int(n_valid[k]), thresholds=out["thr"][k, : n_thr[k]].copy(),
                                               counts=counts[k, : n_thr[k]].copy())
-            if k >= n3:
-                self.details[(o, c, m, d)]["similarity"] = sim[k - n3, : n_thr[k]].copy()
+            if m == "bbox":
+                self.details[(o, c, m, d)]["similarity"] = out["similarity"][k, : n_thr[k]].copy()
                 if "aos" in self.metrics:
-                    result[o][c]["aos"]["R11"][d] = float(aos[k - n3, 0])
-                    result[o][c]["aos"]["R40"][d] = float(aos[k - n3, 1])
+                    result[o][c]["aos"]["R11"][d] = float(out["aos"][k, 0])
+                    result[o][c]["aos"]["R40"][d] = float(out["aos"][k, 1])
         self.result = result
 
     def summary(self, r11=False):
