@@ -676,13 +676,16 @@ int v3d_dense_train_backward_split(const void* bev_hi, const void* bev_lo, const
  *   MIN_HEIGHT[d].  Class codes: V3D_KITTI_CODE_*.
  *   gt_img (G, 5), dt_img (D, 5) f32 = image box (x1, y1, x2, y2) and alpha (read by bbox combos only).
  * A combo is one (class, difficulty, metric, minimum overlap); up to V3D_KITTI_MAX_COMBOS of them, on the HOST, in one array
- * whatever their metrics.  ov holds one overlap plane per metric, ov_plane (>= sum n_dt * n_gt) floats apart: a combo reads the
+ * whatever their metrics (beyond it V3D_EUNSUPPORTED).  The kernels take combos by value, V3D_KITTI_COMBO_CHUNK per table:
+ * pass 1 launches once per chunk of V3D_KITTI_COMBO_CHUNK combos, pass 2 once per chunk of the combos it runs generically and
+ * once per 16 level families (below); thresholds and AP launch once.  Launch counts never depend on the frame count.  ov holds one overlap plane per metric, ov_plane (>= sum n_dt * n_gt) floats apart: a combo reads the
  * plane ov + metric * ov_plane (BEV, 3-D, bbox), each frame-major, row = detection, column = ground truth.
  * max_dt / max_gt (host) are the largest per-frame counts: beyond V3D_KITTI_MAX_DT / V3D_KITTI_MAX_GT every entry point
  * returns V3D_EUNSUPPORTED.  Integer counters only: results are deterministic.  No host synchronisation. */
 #define V3D_KITTI_MAX_DT 1024
 #define V3D_KITTI_MAX_GT 256
-#define V3D_KITTI_MAX_COMBOS 64
+#define V3D_KITTI_MAX_COMBOS 1024
+#define V3D_KITTI_COMBO_CHUNK 64
 #define V3D_KITTI_SAMPLE_PTS 41
 #define V3D_KITTI_CODE_CAR 0
 #define V3D_KITTI_CODE_PEDESTRIAN 1
@@ -727,7 +730,12 @@ int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacity, const in
  * integer atomics: the total is deterministic and independent of frame order.  A frame adds < 2^40 (<= 256 true positives), so
  * the total is exact below 2^31 true positives per (combo, threshold): more than 8 million frames at the per-frame limit.
  * gt_img, dt_img and similarity may be NULL when no combo is a bbox combo; rows of other combos stay as they are.  counts and
- * similarity must be zero on entry.  V3D_EINVAL for a combo metric outside 0..2 or a bbox combo without the image arrays. */
+ * similarity must be zero on entry.  V3D_EINVAL for a combo metric outside 0..2 or a bbox combo without the image arrays.
+ * Level families -- combos equal in (cls, neighbour, difficulty, metric), differing in min_overlap only, grouped in combo order up
+ * to 12 per family -- of 3 or more combos (a COCO-style overlap sweep) run one workgroup per (frame, family) with one wave per
+ * level, reading the frame's flags, scores and (when it fits) overlap tile from LDS staged once; the rule and the data are
+ * those of the per-combo kernel, so counts and similarity are bit-identical either way.  Where the staging for max_dt / max_gt
+ * exceeds 64 KiB of LDS, every combo runs per combo.  max_dt / max_gt must bound every frame's counts. */
 int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_off, const float* gt_img, const float* dt, const int32_t* dt_meta,
                          const int32_t* dt_off, const float* dt_img, const int64_t* ov_off, const float* ov, int64_t ov_plane,
                          int n_frames, int max_dt, int max_gt, const v3d_kitti_combo* combos_host, int n_combos,

@@ -4,6 +4,9 @@ events).  With bbox or aos in --metrics every detection near a ground truth gets
 random alpha, so that the 2-D stages have matches to work on; the host restatement then covers BEV / 3-D only.
 
     python tools/mb_kitti_eval.py [--frames 3769] [--gt 20] [--dt 100] [--host-frames 3769] [--reps 5] [--metrics bev,3d]
+                                  [--overlaps strict,loose]
+
+With coco in --overlaps the ten-level sweep runs as well (the host restatement covers strict / loose only).
 
 For kernel times of record run it under `rocprofv3 --kernel-trace --stats` in a run of its own."""
 import argparse
@@ -62,17 +65,19 @@ def main():
     ap.add_argument("--host-frames", type=int, default=3769, help="frames given to the host restatement (timed separately)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--metrics", default="bev,3d", help="comma list of bbox, bev, 3d, aos (KittiEvaluator metrics)")
+    ap.add_argument("--overlaps", default="strict,loose", help="comma list of strict, loose, coco (KittiEvaluator overlap sets)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "mb_kitti_eval needs a GPU"
     t = time.perf_counter()
     metrics = tuple(m for m in args.metrics.split(",") if m)
+    overlaps = tuple(o for o in args.overlaps.split(",") if o)
     pairs = make_set(args.frames, args.gt, args.dt)
     if "bbox" in metrics or "aos" in metrics:
         pairs = with_image_boxes(pairs)
     n_gt = sum(len(g.names) for g, _ in pairs)
     n_dt = sum(len(d.names) for _, d in pairs)
     print(f"set: {len(pairs)} frames, {n_gt} ground truths, {n_dt} detections (generated in {time.perf_counter() - t:.1f} s)")
-    ev = KittiEvaluator(metrics=metrics)
+    ev = KittiEvaluator(metrics=metrics, overlaps=overlaps)
     for g, d in pairs:
         ev.add_frame(g, d)
     for _ in range(2):
@@ -84,7 +89,8 @@ def main():
         ev.compute()  # ends in its one host read
         times.append(time.perf_counter() - t)
     print(f"device compute(): median {np.median(times) * 1e3:.2f} ms, min {min(times) * 1e3:.2f} ms over {args.reps} calls "
-          f"(host packing + uploads + kernels + sort + one read; metrics {','.join(metrics)})")
+          f"(host packing + uploads + kernels + sort + one read; metrics {','.join(metrics)}; overlaps {','.join(overlaps)}; "
+          f"{len(ev.combos)} combos)")
     from torch.profiler import ProfilerActivity, profile
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         ev.compute()
@@ -100,12 +106,13 @@ def main():
         return
     t = time.perf_counter()
     frames = [R.make_frame(g, d) for g, d in pairs[:hf]]
-    want, _ = R.evaluate(frames, metrics=tuple(m for m in metrics if m in ("bev", "3d")))
+    official = tuple(o for o in overlaps if o != "coco")
+    want, _ = R.evaluate(frames, metrics=tuple(m for m in metrics if m in ("bev", "3d")), overlap_sets=official)
     host = time.perf_counter() - t
     print(f"host float64 restatement: {host:.1f} s for {hf} frames")
     if hf == len(pairs):
-        diff = max(abs(a - b) for o in want for c in want[o] for m in want[o][c] for k in ("R11", "R40")
-                   for a, b in zip(res[o][c][m][k], want[o][c][m][k]))
+        diff = max((abs(a - b) for o in want for c in want[o] for m in want[o][c] for k in ("R11", "R40")
+                    for a, b in zip(res[o][c][m][k], want[o][c][m][k])), default=0.0)
         print(f"largest |AP(device) - AP(host)|: {diff:.3g} (this set has no margin around the minimum overlaps)")
     print(ev.summary())
 

@@ -17,12 +17,23 @@
 //                      bbox combos add the DontCare step (unassigned counted detections whose inter / area_dt with a DontCare
 //                      region exceeds the minimum overlap are no false positives) and each lane's true-positive similarity sum
 //                      (1 + cos(alpha_gt - alpha_dt)) / 2 in double, added as 32.32 fixed point with 64-bit integer atomics;
+//      pass 2 family   (kitti_pass2_family_kernel) the combos that differ only in min_overlap (a "family": the levels of a COCO-style
+//                      sweep, with the official combos of the same class, neighbour, difficulty and metric) of KE_FAMILY_MIN or
+//                      more: one workgroup per (frame, family), one wave per level, one lane per threshold; the frame's scores,
+//                      ignored_dt and ignored_gt are staged into LDS once, and its overlap tile too when it fits.  The same rule
+//                      (ke_pass2_lane) on the same data: counts and similarity are bit-identical to the generic kernel's;
 //   5. ap              one lane per combo: precision (and with the similarity, similarity / (tp + fp)), its running maximum
 //                      from the right, R11 / R40 sums in definition order.
+// Combos reach the kernels by value, KE_CHUNK per launch: pass 1 and the generic pass 2 launch once per chunk of 64 combos, the
+// family pass 2 once per KE_FAM_CHUNK families; the thresholds and AP kernels take a grid of ceil(n / 64) waves.  Launch counts
+// depend on the combos, never on the frame count.
 // Limits: 1 024 detections (16 bitmask words per lane in pass 2, 16 register bits per lane in pass 1) and 256 ground truths
 // (one LDS slot per thread in stage 1) per frame.
 #include "v3d_common.h"
 #include "rotated_iou.h"
+
+#include <algorithm>
+#include <vector>
 
 using v3d::BoxPrep;
 
@@ -30,8 +41,27 @@ using v3d::BoxPrep;
 #define KE_WORDS (V3D_KITTI_MAX_DT / 64)
 #define KE_DONTCARE_BIT V3D_KITTI_DONTCARE_BIT  // gt_meta[1] (ignored_gt reads bits 0-2 only)
 
+#define KE_CHUNK V3D_KITTI_COMBO_CHUNK  // combos per by-value table (one pass-1 / generic pass-2 launch)
+#ifndef KE_FAMILY_MIN
+#define KE_FAMILY_MIN 3  // families of fewer combos (the official strict / loose pairs) stay on the generic pass 2
+#endif
+#define KE_FAM_LEVELS 12        // combos per family (one wave each): ten sweep levels + strict + loose
+#define KE_FAM_CHUNK 16         // families per by-value table (one family pass-2 launch)
+#define KE_FAM_LDS (64 * 1024)  // the family kernel's LDS budget: bitmasks, staged detections, ground truths, overlap tile
+
 struct KeCombos {
-  v3d_kitti_combo c[V3D_KITTI_MAX_COMBOS];
+  v3d_kitti_combo c[KE_CHUNK];
+};
+// One family: the shared (class, neighbour, difficulty, metric) in c (its min_overlap unused), and per level the combo index
+// (row of thresholds, n_thresholds, counts, similarity) and its min_overlap.
+struct KeFamily {
+  v3d_kitti_combo c;
+  int n;
+  int combo[KE_FAM_LEVELS];
+  float level[KE_FAM_LEVELS];
+};
+struct KeFamilies {
+  KeFamily f[KE_FAM_CHUNK];
 };
 
 // A rectified-camera box (x, y_bottom, z, h, w, l, ry): the BEV rectangle in the (x, z) plane -- the core's extent `w` (along
@@ -161,7 +191,7 @@ __global__ __launch_bounds__(V3D_WAVE) void kitti_thresholds_kernel(const float*
                                                                     const int* __restrict__ tp_count, const int* __restrict__ n_valid,
                                                                     int n_combos, float* __restrict__ thresholds,
                                                                     int* __restrict__ n_thresholds) {
-  const int combo = threadIdx.x;
+  const int combo = blockIdx.x * V3D_WAVE + threadIdx.x;
   if (combo >= n_combos) return;
   const int n = min(tp_count[combo], capacity), ngt = n_valid[combo];
   const float* s = sorted + (size_t)combo * capacity;
@@ -172,7 +202,7 @@ __global__ __launch_bounds__(V3D_WAVE) void kitti_thresholds_kernel(const float*
       const double l = (double)(i + 1) / ngt;
       const double r = i < n - 1 ? (double)(i + 2) / ngt : l;
       if ((r - current) < (current - l) && i < n - 1) continue;
-      thresholds[combo * KE_NT + k++] = s[i];
+      thresholds[(size_t)combo * KE_NT + k++] = s[i];
       current += 1.0 / (KE_NT - 1.0);
     }
   }
@@ -186,50 +216,65 @@ __device__ __forceinline__ double img_inter(double x1, double y1, double x2, dou
   return (iw > 0.0 && ih > 0.0) ? iw * ih : 0.0;
 }
 
-__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(
-    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
-    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
-    const int64_t* __restrict__ ov_off, const float* __restrict__ ov, int64_t ov_plane, KeCombos combos, int n_combos,
-    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
-    unsigned long long* __restrict__ similarity) {
-  __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
-  const int lane = threadIdx.x & 63;
-  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
-  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
-  const v3d_kitti_combo c = combos.c[combo];
-  const bool image = c.metric == V3D_KITTI_METRIC_BBOX;  // (wave-uniform) the DontCare step and the similarity sum
-  const int nt = n_thresholds[combo];
-  if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
-  const int f = blockIdx.x;
-  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
-  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
-  if (ng < 0 || nd < 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
-  const float thresh = thresholds[combo * KE_NT + lane];
-  unsigned long long* assigned = assigned_lds[threadIdx.x >> 6] + lane;
+// The frame as the generic pass 2 reads it: straight from the ragged global arrays, flags derived per access.
+struct KeGlobalFrame {
+  const int* gt_meta;
+  const int* dt_meta;
+  const float* dt;  // score in column 7
+  const float* ov;  // the frame's (n_dt, n_gt) matrix of the combo's metric
+  int g0, d0, ng;   // the frame's first rows
+  v3d_kitti_combo c;
+  __device__ __forceinline__ int ig(int i) const { return ignored_gt(gt_meta + 2 * (size_t)(g0 + i), c); }
+  __device__ __forceinline__ bool dontcare(int i) const { return (gt_meta[2 * (size_t)(g0 + i) + 1] >> KE_DONTCARE_BIT) & 1; }
+  __device__ __forceinline__ int igd(int j) const { return ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c); }
+  __device__ __forceinline__ float score(int j) const { return dt[8 * (size_t)(d0 + j) + 7]; }
+  __device__ __forceinline__ float overlap(int j, int i) const { return ov[(size_t)j * ng + i]; }
+};
+
+// The frame as the family pass 2 reads it: flags and scores staged in LDS once per (frame, family); `ov` is the LDS tile or,
+// for a frame whose tile does not fit, the global matrix.
+struct KeLdsFrame {
+  const unsigned char* gtf;  // per ground truth: ignored_gt + 1 in bits 0-1, DontCare in bit 2
+  const signed char* dtf;    // per detection: ignored_dt
+  const float* sc;           // per detection: score
+  const float* ov;
+  int ng;
+  __device__ __forceinline__ int ig(int i) const { return (gtf[i] & 3) - 1; }
+  __device__ __forceinline__ bool dontcare(int i) const { return (gtf[i] >> 2) & 1; }
+  __device__ __forceinline__ int igd(int j) const { return dtf[j]; }
+  __device__ __forceinline__ float score(int j) const { return sc[j]; }
+  __device__ __forceinline__ float overlap(int j, int i) const { return ov[(size_t)j * ng + i]; }
+};
+
+// Pass 2 of one lane (one threshold) on one frame, the rule written once for both pass-2 kernels: the greedy assignment with
+// false positives, then (image) the DontCare step and the true-positive similarity sum in ground-truth order.  `assigned` is
+// the lane's bitmask, word w at assigned[w * 64]; the frame's image rows start at g0 / d0 of gt_img / dt_img.
+template <class F>
+__device__ __forceinline__ void ke_pass2_lane(const F& fr, int ng, int nd, float thresh, float min_overlap, bool image,
+                                              unsigned long long* assigned, const float* gt_img, const float* dt_img, int g0,
+                                              int d0, int& tp, int& fp, int& fn, double& sim) {
   const int nw = (nd + 63) >> 6;
   for (int w = 0; w < nw; w++) assigned[w * 64] = 0ull;
-  const float* ovf = ov + c.metric * ov_plane + (ng ? ov_off[f] : 0);  // this frame's matrix of the combo's metric
-  int tp = 0, fp = 0, fn = 0;
+  tp = fp = fn = 0;
+  sim = 0.0;
   int dc_lo = ng, dc_hi = 0;  // (bbox) the DontCare regions lie in [dc_lo, dc_hi)
-  double sim = 0.0;           // (bbox) this frame's true-positive similarities, in ground-truth order
   for (int i = 0; i < ng; i++) {
-    const int* gm = gt_meta + 2 * (size_t)(g0 + i);
-    if (image && ((gm[1] >> KE_DONTCARE_BIT) & 1)) {
+    if (image && fr.dontcare(i)) {
       dc_lo = min(dc_lo, i);
       dc_hi = i + 1;
     }
-    const int ig = ignored_gt(gm, c);
+    const int ig = fr.ig(i);
     if (ig == -1) continue;
     int best = -1;
     bool best_ign = false;
     float best_ov = 0.f;
     for (int j = 0; j < nd; j++) {
-      const int igd = ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c);
+      const int igd = fr.igd(j);
       if (igd == -1) continue;
-      if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+      if (fr.score(j) < thresh) continue;
       if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
-      const float o = ovf[(size_t)j * ng + i];
-      if (!(o > c.min_overlap)) continue;
+      const float o = fr.overlap(j, i);
+      if (!(o > min_overlap)) continue;
       if (igd == 0) {  // a counted detection: the largest overlap wins (earliest on ties), and displaces an ignored pick
         if (best < 0 || best_ign || o > best_ov) {
           best = j;
@@ -256,8 +301,8 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(
   }
   // false positives; (bbox) an unassigned counted detection over a DontCare region (inter / area_dt > min overlap) is absorbed
   for (int j = 0; j < nd; j++) {
-    if (ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c) != 0) continue;
-    if (dt[8 * (size_t)(d0 + j) + 7] < thresh) continue;
+    if (fr.igd(j) != 0) continue;
+    if (fr.score(j) < thresh) continue;
     if ((assigned[(j >> 6) * 64] >> (j & 63)) & 1ull) continue;
     bool absorbed = false;
     if (image && dc_lo < dc_hi) {
@@ -265,20 +310,117 @@ __global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(
       const double x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
       const double area = (x2 - x1) * (y2 - y1);  // (positive wherever the intersection is)
       for (int i = dc_lo; i < dc_hi && !absorbed; i++) {
-        if (!((gt_meta[2 * (size_t)(g0 + i) + 1] >> KE_DONTCARE_BIT) & 1)) continue;
+        if (!fr.dontcare(i)) continue;
         const double inter = img_inter(x1, y1, x2, y2, gt_img + 5 * (size_t)(g0 + i));
-        absorbed = inter > 0.0 && inter / area > (double)c.min_overlap;
+        absorbed = inter > 0.0 && inter / area > (double)min_overlap;
       }
     }
     fp += !absorbed;
   }
-  const size_t at = (size_t)combo * KE_NT + lane;
+}
+
+// A lane's (tp, fp, fn) and (bbox) similarity into row `at` = combo * 41 + threshold
+__device__ __forceinline__ void ke_pass2_add(int* counts, unsigned long long* similarity, size_t at, bool image, int tp, int fp,
+                                             int fn, double sim) {
   int* out = counts + at * 3;
   if (tp) atomicAdd(out + 0, tp);
   if (fp) atomicAdd(out + 1, fp);
   if (fn) atomicAdd(out + 2, fn);
   // 32.32 fixed point: sim <= 256 per frame, so each add is < 2^40; integer adds make the total order-free and exact
   if (image && tp) atomicAdd(similarity + at, (unsigned long long)llrint(sim * 4294967296.0));
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void kitti_pass2_kernel(
+    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
+    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
+    const int64_t* __restrict__ ov_off, const float* __restrict__ ov, int64_t ov_plane, KeCombos combos, int n_combos,
+    const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
+    unsigned long long* __restrict__ similarity) {
+  __shared__ unsigned long long assigned_lds[V3D_BLOCK / V3D_WAVE][KE_WORDS * 64];  // word w of lane L at [w * 64 + L]
+  const int lane = threadIdx.x & 63;
+  const int combo = blockIdx.y * (V3D_BLOCK / V3D_WAVE) + (threadIdx.x >> 6);
+  if (combo >= n_combos) return;  // (wave-uniform: no block barrier below)
+  const v3d_kitti_combo c = combos.c[combo];
+  const bool image = c.metric == V3D_KITTI_METRIC_BBOX;  // (wave-uniform) the DontCare step and the similarity sum
+  const int nt = n_thresholds[combo];
+  if (lane >= nt) return;  // one lane per threshold; no cross-lane traffic below
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng < 0 || nd < 0 || ng > V3D_KITTI_MAX_GT || nd > V3D_KITTI_MAX_DT) return;
+  const float thresh = thresholds[combo * KE_NT + lane];
+  const float* ovf = ov + c.metric * ov_plane + (ng ? ov_off[f] : 0);  // this frame's matrix of the combo's metric
+  const KeGlobalFrame fr{gt_meta, dt_meta, dt, ovf, g0, d0, ng, c};
+  int tp, fp, fn;
+  double sim;
+  ke_pass2_lane(fr, ng, nd, thresh, c.min_overlap, image, assigned_lds[threadIdx.x >> 6] + lane, gt_img, dt_img, g0, d0, tp, fp,
+                fn, sim);
+  ke_pass2_add(counts, similarity, (size_t)combo * KE_NT + lane, image, tp, fp, fn, sim);
+}
+
+// Dynamic LDS of the family kernel, in bytes from the start (8-byte aligned pieces first): `waves` bitmask slabs of words * 64
+// u64, max_dt scores (f32), tile_cap overlaps (f32), max_dt ignored_dt (i8), max_gt ground-truth flags (u8).
+struct KeFamLds {
+  size_t scores, tile, dtf, gtf, bytes;
+};
+__host__ __device__ __forceinline__ KeFamLds ke_fam_lds(int waves, int words, int max_dt, int max_gt, int tile_cap) {
+  KeFamLds l;
+  l.scores = (size_t)waves * words * 64 * 8;
+  l.tile = l.scores + 4 * (size_t)max_dt;
+  l.dtf = l.tile + 4 * (size_t)tile_cap;
+  l.gtf = l.dtf + (size_t)max_dt;
+  l.bytes = (l.gtf + (size_t)max_gt + 15) & ~(size_t)15;
+  return l;
+}
+
+// Pass 2 over level families: one workgroup per (frame, family), wave w = the family's level w, lane = threshold.  The frame's
+// scores, ignored_dt, ignored_gt / DontCare flags and (when n_dt * n_gt <= tile_cap) its overlap tile go to LDS once; every
+// level then runs ke_pass2_lane on them.
+__global__ __launch_bounds__(KE_FAM_LEVELS * V3D_WAVE) void kitti_pass2_family_kernel(
+    const int* __restrict__ gt_meta, const int* __restrict__ gt_off, const float* __restrict__ gt_img, const float* __restrict__ dt,
+    const int* __restrict__ dt_meta, const int* __restrict__ dt_off, const float* __restrict__ dt_img,
+    const int64_t* __restrict__ ov_off, const float* __restrict__ ov, int64_t ov_plane, KeFamilies fams, int max_dt, int max_gt,
+    int words, int tile_cap, const float* __restrict__ thresholds, const int* __restrict__ n_thresholds, int* __restrict__ counts,
+    unsigned long long* __restrict__ similarity) {
+  extern __shared__ unsigned long long ke_fam_smem[];
+  const int f = blockIdx.x;
+  const int g0 = gt_off[f], ng = gt_off[f + 1] - g0;
+  const int d0 = dt_off[f], nd = dt_off[f + 1] - d0;
+  if (ng < 0 || nd < 0 || ng > max_gt || nd > max_dt) return;  // (block-uniform; the LDS carve holds max_dt / max_gt)
+  const KeFamily& fam = fams.f[blockIdx.y];
+  const v3d_kitti_combo c = fam.c;
+  const KeFamLds l = ke_fam_lds(blockDim.x >> 6, words, max_dt, max_gt, tile_cap);
+  unsigned char* base = (unsigned char*)ke_fam_smem;
+  float* sc = (float*)(base + l.scores);
+  float* tile = (float*)(base + l.tile);
+  signed char* dtf = (signed char*)(base + l.dtf);
+  unsigned char* gtf = base + l.gtf;
+  for (int j = threadIdx.x; j < nd; j += blockDim.x) {
+    sc[j] = dt[8 * (size_t)(d0 + j) + 7];
+    dtf[j] = (signed char)ignored_dt(dt_meta + 2 * (size_t)(d0 + j), c);
+  }
+  for (int i = threadIdx.x; i < ng; i += blockDim.x) {
+    const int* gm = gt_meta + 2 * (size_t)(g0 + i);
+    gtf[i] = (unsigned char)((ignored_gt(gm, c) + 1) | (((gm[1] >> KE_DONTCARE_BIT) & 1) << 2));
+  }
+  const float* ovf = ov + c.metric * ov_plane + (ng ? ov_off[f] : 0);
+  const int pairs = nd * ng;
+  const bool staged = pairs <= tile_cap;  // (block-uniform)
+  if (staged)
+    for (int k = threadIdx.x; k < pairs; k += blockDim.x) tile[k] = ovf[k];
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (wave >= fam.n) return;
+  const int combo = fam.combo[wave];
+  const bool image = c.metric == V3D_KITTI_METRIC_BBOX;
+  if (lane >= n_thresholds[combo]) return;
+  const float thresh = thresholds[combo * KE_NT + lane];
+  const KeLdsFrame fr{gtf, dtf, sc, staged ? tile : ovf, ng};
+  int tp, fp, fn;
+  double sim;
+  ke_pass2_lane(fr, ng, nd, thresh, fam.level[wave], image, ke_fam_smem + (size_t)wave * words * 64 + lane, gt_img, dt_img, g0,
+                d0, tp, fp, fn, sim);
+  ke_pass2_add(counts, similarity, (size_t)combo * KE_NT + lane, image, tp, fp, fn, sim);
 }
 
 // v (KE_NT ratios) -> its running maximum from the right, then out = (R11, R40) in percent, summed in definition order
@@ -298,7 +440,7 @@ __global__ __launch_bounds__(V3D_WAVE) void kitti_ap_kernel(const int* __restric
                                                             const unsigned long long* __restrict__ similarity,
                                                             const int* __restrict__ n_thresholds, int n_combos,
                                                             double* __restrict__ ap, double* __restrict__ aos) {
-  const int combo = threadIdx.x;
+  const int combo = blockIdx.x * V3D_WAVE + threadIdx.x;
   if (combo >= n_combos) return;
   const int nt = n_thresholds[combo];
   double v[KE_NT];
@@ -359,8 +501,12 @@ static int ke_check(int n_frames, int max_dt, int max_gt, int n_combos) {
 
 static KeCombos ke_combos(const v3d_kitti_combo* host, int n) {
   KeCombos k = {};
-  for (int i = 0; i < n; i++) k.c[i] = host[i];
+  for (int i = 0; i < n && i < KE_CHUNK; i++) k.c[i] = host[i];
   return k;
+}
+
+static bool ke_same_family(const v3d_kitti_combo& a, const v3d_kitti_combo& b) {
+  return a.cls == b.cls && a.neighbour == b.neighbour && a.difficulty == b.difficulty && a.metric == b.metric;
 }
 
 // The metrics the combos use as bits 1 << metric, or -1 for a metric outside 0..2 (it indexes the overlap planes)
@@ -397,10 +543,13 @@ extern "C" int v3d_kitti_eval_pass1(const int32_t* gt_meta, const int32_t* gt_of
   if (!gt_meta || !gt_off || !dt_off || !ov_off || !combos_host || !tp_count || !n_valid) return V3D_EINVAL;
   if (max_dt > 0 && (!dt || !dt_meta || !ov || !tp_scores)) return V3D_EINVAL;
   if (ke_metrics(combos_host, n_combos) < 0) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_pass1_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov, ov_plane,
-                     ke_combos(combos_host, n_combos), n_combos, capacity, tp_count, tp_scores, n_valid);
-  V3D_CHECK_LAUNCH();
+  for (int b = 0; b < n_combos; b += KE_CHUNK) {  // one launch per by-value table of KE_CHUNK combos
+    const int n = min(KE_CHUNK, n_combos - b);
+    hipLaunchKernelGGL(kitti_pass1_kernel, dim3(n_frames, v3d_ceil_div(n, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
+                       (hipStream_t)stream, gt_meta, gt_off, dt, dt_meta, dt_off, ov_off, ov, ov_plane, ke_combos(combos_host + b, n),
+                       n, capacity, tp_count + b, tp_scores ? tp_scores + (size_t)b * capacity : nullptr, n_valid + b);
+    V3D_CHECK_LAUNCH();
+  }
   return V3D_OK;
 }
 
@@ -411,7 +560,7 @@ extern "C" int v3d_kitti_eval_thresholds(const float* sorted_scores, int capacit
   if (capacity < 0) return V3D_EINVAL;
   if (n_combos == 0) return V3D_OK;
   if (!tp_count || !n_valid || !thresholds || !n_thresholds || (capacity > 0 && !sorted_scores)) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_thresholds_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, sorted_scores, capacity, tp_count,
+  hipLaunchKernelGGL(kitti_thresholds_kernel, dim3(v3d_ceil_div(n_combos, V3D_WAVE)), dim3(V3D_WAVE), 0, (hipStream_t)stream, sorted_scores, capacity, tp_count,
                      n_valid, n_combos, thresholds, n_thresholds);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
@@ -434,11 +583,62 @@ extern "C" int v3d_kitti_eval_pass2(const int32_t* gt_meta, const int32_t* gt_of
   if (metrics < 0) return V3D_EINVAL;
   const bool bbox = (metrics >> V3D_KITTI_METRIC_BBOX) & 1;  // the DontCare step and the similarity read these
   if (bbox && (!similarity || (max_gt > 0 && !gt_img) || (max_dt > 0 && !dt_img))) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_pass2_kernel, dim3(n_frames, v3d_ceil_div(n_combos, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, gt_meta, gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov, ov_plane,
-                     ke_combos(combos_host, n_combos), n_combos, thresholds, n_thresholds, counts,
-                     (unsigned long long*)similarity);
-  V3D_CHECK_LAUNCH();
+  unsigned long long* sim = (unsigned long long*)similarity;
+  // Level families (combos equal but for min_overlap, up to KE_FAM_LEVELS each, in combo order) of KE_FAMILY_MIN or more
+  // combos go to the family kernel when its LDS carve fits the budget; every other combo to the generic kernel, in runs of
+  // consecutive combos, KE_CHUNK per launch.
+  const int words = max(1, v3d_ceil_div(max_dt, 64));
+  const KeFamLds fixed = ke_fam_lds(KE_FAM_LEVELS, words, max_dt, max_gt, 0);
+  const bool family_fits = fixed.bytes <= KE_FAM_LDS;
+  std::vector<KeFamily> fams;
+  for (int i = 0; i < n_combos; i++) {
+    int k = (int)fams.size() - 1;
+    while (k >= 0 && !(ke_same_family(fams[k].c, combos_host[i]) && fams[k].n < KE_FAM_LEVELS)) k--;
+    if (k < 0) {
+      fams.push_back(KeFamily{});
+      k = (int)fams.size() - 1;
+      fams[k].c = combos_host[i];
+    }
+    fams[k].combo[fams[k].n] = i;
+    fams[k].level[fams[k].n++] = combos_host[i].min_overlap;
+  }
+  std::vector<KeFamily> big;
+  std::vector<char> generic(n_combos, 1);
+  for (const KeFamily& fm : fams) {
+    if (!family_fits || fm.n < KE_FAMILY_MIN) continue;
+    big.push_back(fm);
+    for (int w = 0; w < fm.n; w++) generic[fm.combo[w]] = 0;
+  }
+  for (int b = 0; b < n_combos;) {
+    if (!generic[b]) {
+      b++;
+      continue;
+    }
+    int n = 1;
+    while (n < KE_CHUNK && b + n < n_combos && generic[b + n]) n++;
+    hipLaunchKernelGGL(kitti_pass2_kernel, dim3(n_frames, v3d_ceil_div(n, V3D_BLOCK / V3D_WAVE)), dim3(V3D_BLOCK), 0,
+                       (hipStream_t)stream, gt_meta, gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov, ov_plane,
+                       ke_combos(combos_host + b, n), n, thresholds + (size_t)b * KE_NT, n_thresholds + b,
+                       counts + (size_t)b * KE_NT * 3, sim ? sim + (size_t)b * KE_NT : nullptr);
+    V3D_CHECK_LAUNCH();
+    b += n;
+  }
+  for (size_t b = 0; b < big.size(); b += KE_FAM_CHUNK) {
+    KeFamilies table = {};
+    const int n = (int)std::min<size_t>(KE_FAM_CHUNK, big.size() - b);
+    int waves = 0;
+    for (int k = 0; k < n; k++) {
+      table.f[k] = big[b + k];
+      waves = max(waves, table.f[k].n);
+    }
+    const KeFamLds lds = ke_fam_lds(waves, words, max_dt, max_gt, 0);
+    const int tile_cap = (int)((KE_FAM_LDS - lds.bytes) / 4) & ~3;  // (keeps the carve's total within the budget)
+    const KeFamLds all = ke_fam_lds(waves, words, max_dt, max_gt, tile_cap);
+    hipLaunchKernelGGL(kitti_pass2_family_kernel, dim3(n_frames, n), dim3(waves * V3D_WAVE), all.bytes, (hipStream_t)stream, gt_meta,
+                       gt_off, gt_img, dt, dt_meta, dt_off, dt_img, ov_off, ov, ov_plane, table, max_dt, max_gt, words, tile_cap,
+                       thresholds, n_thresholds, counts, sim);
+    V3D_CHECK_LAUNCH();
+  }
   return V3D_OK;
 }
 
@@ -448,7 +648,7 @@ extern "C" int v3d_kitti_eval_ap(const int32_t* counts, const int64_t* similarit
   if (e) return e;
   if (n_combos == 0) return V3D_OK;
   if (!counts || !n_thresholds || !ap || (similarity && !aos)) return V3D_EINVAL;
-  hipLaunchKernelGGL(kitti_ap_kernel, dim3(1), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts,
+  hipLaunchKernelGGL(kitti_ap_kernel, dim3(v3d_ceil_div(n_combos, V3D_WAVE)), dim3(V3D_WAVE), 0, (hipStream_t)stream, counts,
                      (const unsigned long long*)similarity, n_thresholds, n_combos, ap, aos);
   V3D_CHECK_LAUNCH();
   return V3D_OK;

@@ -51,6 +51,18 @@ Per class c, difficulty d (easy, moderate, hard), metric and minimum overlap t_m
     -atan2(-y_lidar, x_lidar) + ry (what write_kitti_results writes).  The devkit's -10 ("unknown") is not special-cased: a
     detection with alpha -10 simply scores its cosine.
 
+COCO-style AP (overlap set "coco"; the port's get_coco_eval_result / do_coco_style_eval): the same AP averaged over ten
+minimum overlaps.
+  Levels per class: Car np.linspace(0.5, 0.95, 10); Pedestrian and Cyclist np.linspace(0.25, 0.70, 10).  Computed in double,
+    each stored as the nearest float32 in v3d_kitti_combo.min_overlap and compared exactly as above (overlap > level).  The
+    same levels apply to bbox, BEV and 3-D; the strict / loose split does not apply to the sweep.
+  Per level: each (class, metric, difficulty, level) is an ordinary combo run through the protocol above unchanged -- pass 1,
+    the thresholds, pass 2, the R11 / R40 sums; for bbox the DontCare absorption at inter / area_dt > level; AOS from the bbox
+    combos' counts.
+  COCO value: the mean over the ten levels of AP_R11, AP_R40, AOS_R11 and AOS_R40, each summed in double in level order, then
+    divided by 10.
+  Summary: one line per class and AP kind, `Car coco AP_R40@0.50:0.05:0.95: bev: ...  3d: ...`.
+
 Limits: 1 024 detections and 256 ground truths per frame (RuntimeError beyond them).  No CPU fallback.
 """
 import math
@@ -68,6 +80,9 @@ DIFFICULTIES = ("easy", "moderate", "hard")
 MIN_OVERLAP = {"strict": {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5},
                "loose": {"Car": 0.5, "Pedestrian": 0.25, "Cyclist": 0.25}}  # BEV and 3-D
 MIN_OVERLAP_IMAGE = {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5}  # bbox and aos, in both overlap sets
+COCO_RANGE = {"Car": (0.5, 0.95), "Pedestrian": (0.25, 0.70), "Cyclist": (0.25, 0.70)}  # first and last level
+COCO_LEVELS = {c: np.linspace(lo, hi, 10).astype(np.float32) for c, (lo, hi) in COCO_RANGE.items()}  # every metric
+OVERLAP_SETS = ("strict", "loose", "coco")
 METRICS = ("bbox", "bev", "3d", "aos")
 METRIC_BEV, METRIC_3D, METRIC_BBOX = 0, 1, 2  # v3d_kitti_combo.metric (V3D_KITTI_METRIC_*): the overlap plane a combo reads
 METRIC_CODE = {"bev": METRIC_BEV, "3d": METRIC_3D, "bbox": METRIC_BBOX}
@@ -85,6 +100,12 @@ def class_code(name):
 def min_overlap(overlap_set, cls, metric):
     """t_min of one (overlap set, class, metric): MIN_OVERLAP for BEV / 3-D, MIN_OVERLAP_IMAGE for bbox / aos."""
     return MIN_OVERLAP_IMAGE[cls] if metric in ("bbox", "aos") else MIN_OVERLAP[overlap_set][cls]
+
+
+def coco_header(cls, kind="R40"):
+    """`coco AP_R40@0.50:0.05:0.95`: the summary's name of the COCO-style AP of a class (first level, step, last level)."""
+    lo, hi = COCO_RANGE[cls]
+    return f"coco AP_{kind}@{lo:.2f}:{(hi - lo) / 9:.2f}:{hi:.2f}"
 
 
 def calib_rows(calib):
@@ -211,8 +232,9 @@ def camera_box_overlaps(dt_boxes, gt_boxes):
 class KittiEvaluator:
     """Accumulates frames (`add_frame`) and evaluates them all at once on the GPU (`compute`): a fixed number of launches and one
     host read, whatever the frame count.  `metrics` is any of "bbox", "bev", "3d", "aos" (default BEV and 3-D); "aos" is computed
-    from the bbox combos, which run whenever "bbox" or "aos" is asked for.  `det_names[class_idx]` names model detections added
-    as tensors (default: the KITTI class order of dataset/kitti.py)."""
+    from the bbox combos, which run whenever "bbox" or "aos" is asked for.  `overlaps` is any of "strict", "loose" (default both)
+    and "coco", the COCO-style AP over ten minimum overlaps per class (COCO_LEVELS).  `det_names[class_idx]` names model
+    detections added as tensors (default: the KITTI class order of dataset/kitti.py)."""
 
     def __init__(self, classes=("Car", "Pedestrian", "Cyclist"), metrics=("bev", "3d"), overlaps=("strict", "loose"),
                  det_names=("Car", "Pedestrian", "Cyclist"), device=None):
@@ -223,17 +245,19 @@ class KittiEvaluator:
             if m not in METRICS:
                 raise ValueError(f"KittiEvaluator: unknown metric {m!r} (bbox, bev, 3d, aos)")
         for o in overlaps:
-            if o not in MIN_OVERLAP:
-                raise ValueError(f"KittiEvaluator: unknown overlap set {o!r} (strict, loose)")
+            if o not in OVERLAP_SETS:
+                raise ValueError(f"KittiEvaluator: unknown overlap set {o!r} (strict, loose, coco)")
         self.classes, self.metrics, self.overlaps = tuple(classes), tuple(metrics), tuple(overlaps)
         self.det_names = tuple(det_names)
         self.device = torch.device(device) if device is not None else None
-        # device combos: BEV / 3-D first, then the bbox combos (which also carry aos)
-        self.combos = [(o, c, m, d) for o in self.overlaps for c in self.classes for m in self.metrics if m in ("bev", "3d")
-                       for d in range(3)]
+        # device combos (overlap set, class, metric, difficulty, level: the sweep's index, None in strict / loose): BEV / 3-D
+        # first, then the bbox combos (which also carry aos)
+        levels = {o: range(len(COCO_LEVELS["Car"])) if o == "coco" else (None,) for o in self.overlaps}
+        self.combos = [(o, c, m, d, k) for o in self.overlaps for c in self.classes for m in self.metrics if m in ("bev", "3d")
+                       for d in range(3) for k in levels[o]]
         self.image = "bbox" in self.metrics or "aos" in self.metrics
         if self.image:
-            self.combos += [(o, c, "bbox", d) for o in self.overlaps for c in self.classes for d in range(3)]
+            self.combos += [(o, c, "bbox", d, k) for o in self.overlaps for c in self.classes for d in range(3) for k in levels[o]]
         self.frames = []
         self.details = {}
         self.result = None
@@ -324,7 +348,9 @@ class KittiEvaluator:
     def compute(self):
         """Evaluates every frame added so far -> result[overlap_set][class][metric]["R11" | "R40"] = [easy, moderate, hard] in
         percent.  Per-combo detail (n_valid_gt, thresholds, (tp, fp, fn) per threshold; bbox combos also the similarity sum
-        per threshold) lands in `self.details`, keyed (overlap_set, class, "bev" | "3d" | "bbox", difficulty)."""
+        per threshold) lands in `self.details`, keyed (overlap_set, class, "bev" | "3d" | "bbox", difficulty).  A "coco" key
+        holds `levels` (10,) float32, `ap` (10, 2) per-level (R11, R40), for bbox also `aos` (10, 2), and `per_level`, the ten
+        per-combo detail dicts."""
         n_gt = np.array([len(g[0]) for g, _ in self.frames], np.int64)
         n_dt = np.array([len(d[1]) if d[0] == "labels" else d[1].shape[0] for _, d in self.frames], np.int64)
         if self.frames:
@@ -355,7 +381,7 @@ class KittiEvaluator:
             ov = torch.empty((3 if self.image else 2, max(n_pairs, 1)), dtype=torch.float32, device=dev)
             combos = (L.KittiCombo * n_combos)(*[
                 L.KittiCombo(CLASS_CODE[c], CLASS_CODE.get(NEIGHBOUR[c]) if NEIGHBOUR[c] else -1, d, METRIC_CODE[m],
-                             min_overlap(o, c, m)) for o, c, m, d in self.combos])
+                             min_overlap(o, c, m) if k is None else COCO_LEVELS[c][k]) for o, c, m, d, k in self.combos])
             cap = max(G, 1)
             ints = torch.zeros(2 * n_combos + n_combos * SAMPLE_PTS * 3, dtype=torch.int32, device=dev)
             tp_count, n_valid, counts = ints[:n_combos], ints[n_combos:2 * n_combos], ints[2 * n_combos:]
@@ -401,17 +427,36 @@ class KittiEvaluator:
         result = {o: {c: {m: {"R11": [0.0] * 3, "R40": [0.0] * 3} for m in self.metrics} for c in self.classes}
                   for o in self.overlaps}
         self.details = {}
-        for k, (o, c, m, d) in enumerate(self.combos):
+        for k, (o, c, m, d, lvl) in enumerate(self.combos):
+            det = dict(n_valid_gt=int(n_valid[k]), thresholds=out["thr"][k, : n_thr[k]].copy(), counts=counts[k, : n_thr[k]].copy())
+            if m == "bbox":
+                det["similarity"] = out["similarity"][k, : n_thr[k]].copy()
+            if lvl is not None:  # a sweep level: gathered below
+                sweep = self.details.setdefault((o, c, m, d), dict(levels=COCO_LEVELS[c].copy(), ap=np.zeros((len(COCO_LEVELS[c]), 2)),
+                                                                    per_level=[None] * len(COCO_LEVELS[c])))
+                sweep["ap"][lvl] = out["ap"][k]
+                sweep["per_level"][lvl] = det
+                if m == "bbox":
+                    sweep.setdefault("aos", np.zeros((len(COCO_LEVELS[c]), 2)))[lvl] = out["aos"][k]
+                continue
             if m in self.metrics:
                 result[o][c][m]["R11"][d] = float(out["ap"][k, 0])
                 result[o][c][m]["R40"][d] = float(out["ap"][k, 1])
-            self.details[(o, c, m, d)] = dict(n_valid_gt=int(n_valid[k]), thresholds=out["thr"][k, : n_thr[k]].copy(),
-                                              counts=counts[k, : n_thr[k]].copy())
-            if m == "bbox":
-                self.details[(o, c, m, d)]["similarity"] = out["similarity"][k, : n_thr[k]].copy()
-                if "aos" in self.metrics:
-                    result[o][c]["aos"]["R11"][d] = float(out["aos"][k, 0])
-                    result[o][c]["aos"]["R40"][d] = float(out["aos"][k, 1])
+            self.details[(o, c, m, d)] = det
+            if m == "bbox" and "aos" in self.metrics:
+                result[o][c]["aos"]["R11"][d] = float(out["aos"][k, 0])
+                result[o][c]["aos"]["R40"][d] = float(out["aos"][k, 1])
+        if "coco" in self.overlaps:  # the mean over the levels, summed in double in level order
+            for c in self.classes:
+                for m in self.metrics:
+                    key, src = ("bbox", "aos") if m == "aos" else (m, "ap")
+                    for d in range(3):
+                        vals = self.details[("coco", c, key, d)][src]
+                        for col, kind in enumerate(("R11", "R40")):
+                            total = 0.0
+                            for v in vals[:, col]:
+                                total += float(v)
+                            result["coco"][c][m][kind][d] = total / len(vals)
         self.result = result
 
     def summary(self, r11=False):
@@ -424,7 +469,10 @@ class KittiEvaluator:
         for o in self.overlaps:
             for c in self.classes:
                 for kind in (("R11", "R40") if r11 else ("R40",)):
-                    t = ", ".join(f"{min_overlap(o, c, m):.2f}" for m in ([m for m in self.metrics if m != "aos"] or ["aos"]))
                     parts = "  ".join(f"{m}: " + ", ".join(f"{v:.4f}" for v in self.result[o][c][m][kind]) for m in self.metrics)
+                    if o == "coco":
+                        lines.append(f"{c} {coco_header(c, kind)}: {parts}")
+                        continue
+                    t = ", ".join(f"{min_overlap(o, c, m):.2f}" for m in ([m for m in self.metrics if m != "aos"] or ["aos"]))
                     lines.append(f"{c} AP_{kind}@{t}: {parts}")
         return "\n".join(lines)
