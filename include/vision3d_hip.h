@@ -144,6 +144,30 @@ int v3d_augment_frame(const float* points, int N, int C, const float* boxes, con
                       double factor, double cos_theta, double sin_theta, double theta, float* out_points, float* out_boxes,
                       int64_t* out_class_idx, void* work, size_t work_bytes, v3d_stream_t stream);
 
+/* ---- f2b: the GT-sampling database cut out of a batch of annotated frames (three launches per batch, no host read).
+ * Replaces DatabaseBuilder._process_item / _demean (vision3d/dataset/augmentation.py:201-243) with its PointsInCuboids call
+ * (vision3d/core/geometry.py:27-48; "~10 ms for each scene" in numpy).  points (n_points, C >= 3) f32 = the frames behind each
+ * other, point_offsets / box_offsets (n_frames + 1) i32 ON THE DEVICE = first point row / first box of each frame (they tile
+ * [0, n_points] / [0, n_boxes]).  box_prep (n_boxes, 8) f64 = (cos yaw, sin yaw, x, y, w, l, z - h / 2, z + h / 2), evaluated by the
+ * caller with numpy in the dtype of its boxes and widened (float64 annotation boxes, kitti_dataset.py:75-79: float64 cos / sin;
+ * float32 boxes: float32 values, which reproduces v3d_points_in_boxes); the corners are built from it with multiplies and adds.
+ * Inside test: geometry.py:37-48 in float64 (strict z limits, four strict cross products against the counter-clockwise corners).
+ * A box is kept iff it holds MORE than min_pts points (:232-234).  Outputs: counts (n_boxes) = points inside each box, kept or not;
+ * starts (n_boxes) = first output row of a kept box, -1 if dropped; out_points (cap, C) = the kept boxes' points behind each other
+ * -- frames in batch order, boxes in annotation order, a box's points in point order, a point inside two boxes in both -- with
+ * xy = float32((double)xy - (double)box xy) (:219-227) and the other columns copied; src_index (cap) = row in `points` of every output
+ * row.  totals[3] = {kept boxes, output rows, flags}: flags bit 0 = the rows do not fit cap (nothing is written behind cap; counts,
+ * starts and totals[1] are complete, so the caller can size and repeat), bit 1 = a frame broke a limit (below) and was skipped.
+ * Limits: at most V3D_DATABASE_MAX_BOXES boxes per frame (V3D_EUNSUPPORTED where n_boxes shows it, flags bit 1 otherwise: the
+ * per-frame counts are device data), n_points + 2048 n_frames < 2^31, any n_frames that fits `work`.  Deterministic: no workgroup
+ * waits on another, no atomic decides a row.  work must be 4-byte aligned; C == 4 with 16-byte aligned points / out_points reads
+ * and writes whole rows. */
+#define V3D_DATABASE_MAX_BOXES 256
+size_t v3d_database_work_bytes(int n_points, int n_boxes, int n_frames);
+int v3d_database_extract(const float* points, int n_points, int C, const int32_t* point_offsets, const double* box_prep, int n_boxes,
+                         const int32_t* box_offsets, int n_frames, int min_pts, int32_t* counts, int32_t* starts, int32_t* src_index,
+                         float* out_points, int64_t cap, int32_t* totals, void* work, size_t work_bytes, v3d_stream_t stream);
+
 /* ---- A11: points in cuboids / rectangles.
  * Replaces core/geometry.py:27-65 (PointsInCuboids._get_mask when use_z != 0,
  * PointsNotInRectangles._get_mask otherwise).  points (N,C>=3) f32, boxes (n,7) f32

@@ -1,7 +1,8 @@
 """Either side of the hot path in training: GT-sampling + global augmentation on the device
 (rank 2; reference vision3d/dataset/augmentation.py) and the KITTI file readers (rank 4; reference
-vision3d/dataset/kitti_utils.py, host numpy).  The dataset / annotation-cache classes are not part of this package.
-Resolved on first access."""
+vision3d/dataset/kitti_utils.py, host numpy), and the builder of the GT-sampling database (reference `DatabaseBuilder`,
+augmentation.py:201-243; `python -m vision3d_amd.dataset` writes database.pkl).  The dataset / annotation-cache classes are not
+part of this package.  Resolved on first access."""
 import importlib
 
 _EXPORTS = {
@@ -9,6 +10,7 @@ _EXPORTS = {
     "ScaleAugmentation": "augmentation", "RotateAugmentation": "augmentation", "SampleDatabase": "augmentation",
     "read_points": "kitti", "read_labels": "kitti", "read_calib": "kitti", "boxes_in_lidar_frame": "kitti",
     "crop_to_camera_view": "kitti", "load_frame": "kitti", "Calib": "kitti", "Labels": "kitti",
+    "DatabaseBuilder": "database", "build_annotations": "database", "extract_objects": "database", "box_prep": "database",
 }
 __all__ = sorted(_EXPORTS)
 

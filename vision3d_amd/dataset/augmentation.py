@@ -58,6 +58,13 @@ class SampleDatabase:
             self.points.append(torch.from_numpy(pts).cuda())
             self.boxes.append(torch.from_numpy(box).cuda())
 
+    @classmethod
+    def from_frames(cls, frames, num_classes, min_pts):
+        """Straight from annotated frames `dict(points, boxes, class_idx)`: the objects are cut out and grouped by class on the
+        device (dataset/database.py, csrc/database.hip); equal, tensor for tensor, to the constructor on the reference's pickle."""
+        from .database import sample_database_from_frames
+        return sample_database_from_frames(cls, frames, num_classes, min_pts)
+
     def __len__(self):
         return len(self.points)
 
