@@ -7,14 +7,15 @@
 //        f16x3u   same as f16x3 without scaling (what the lo piece loses to the f16 subnormal quantum)
 //        f32      v_mfma_f32_16x16x4_f32 (exact fp32 fma chain)
 //      reported: max and rms of |d - ref| / |ref| over outputs with |ref| > 1e-3 max|ref|, and max |d - ref| / max|ref|.
-// build: hipcc --offload-arch=gfx950 -O2 -o tools/mb_f16split tools/mb_f16split.hip
+// build: hipcc --offload-arch=gfx950 -O2 -o tools/mb_f16split tools/mb_f16split.hip   (includes csrc/split_prec.h: the shipped split)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "../vision3d_amd/csrc/split_prec.h"
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
@@ -50,16 +51,13 @@ __device__ __forceinline__ void split_f16(const float (&x)[8], float s, f16x8_t&
   lo = __builtin_bit_cast(f16x8_t, l);
 }
 
-// the four-instruction split of csrc/v3d_common.h against the plain expressions, bit for bit
+// the four-instruction split that ships (csrc/split_prec.h v3d_split_f16_pair) against the plain expressions, bit for bit
 __global__ void mix_probe(const float* __restrict__ x, int n, float s, unsigned* __restrict__ mism) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (2 * i + 1 >= n) return;
   const float x0 = x[2 * i], x1 = x[2 * i + 1];
-  unsigned h = 0u, l = 0u;
-  asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(h) : "v"(x0), "s"(s));
-  asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(h) : "v"(x1), "s"(s));
-  asm("v_fma_mixlo_f16 %0, %1, %2, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x0), "s"(s), "v"(h));
-  asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l) : "v"(x1), "s"(s), "v"(h));
+  unsigned h, l;
+  v3d_split_f16_pair(x0, x1, s, h, l);
   const float a = x0 * s, b = x1 * s;
   const f16x2_t hh = __builtin_convertvector(f32x2_t{a, b}, f16x2_t);
   const float r0 = a - (float)hh[0], r1 = b - (float)hh[1];

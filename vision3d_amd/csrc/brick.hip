@@ -258,12 +258,12 @@ __global__ __launch_bounds__(256) void spconv_fwd_brick(const unsigned char* __r
     store_w(0, wreg[0]);
     __syncthreads();
 
-    u32x4_t breg[2][KI][2][NB];  // [set][ki][hi, lo][j] fragments of W[k], set = k & 1
-    u32x4_t areg[2][KI][2];      // [set][ki][hi, lo] row fragments of one tile, set = (k * T + t) & 1
+    u32x4 breg[2][KI][2][NB];  // [set][ki][hi, lo][j] fragments of W[k], set = k & 1
+    u32x4 areg[2][KI][2];      // [set][ki][hi, lo] row fragments of one tile, set = (k * T + t) & 1
     // fragment f of W (order of first use: ki, then hi before lo, then j)
-    auto read_b1 = [&](int buf, int f, u32x4_t (&bq)[KI][2][NB]) {
+    auto read_b1 = [&](int buf, int f, u32x4 (&bq)[KI][2][NB]) {
       const int ki = f / (2 * NB), hl = (f / NB) & 1, j = f % NB;
-      bq[ki][hl][j] = *(reinterpret_cast<const u32x4_t*>(wbuf + buf * WBYTES) + lane + (size_t)((ki * NB + j) * 2 + hl) * 64);
+      bq[ki][hl][j] = *(reinterpret_cast<const u32x4*>(wbuf + buf * WBYTES) + lane + (size_t)((ki * NB + j) * 2 + hl) * 64);
     };
     int a_slot = 0;  // slot of the tile whose fragments are being read
     auto a_prepare = [&](const i32x2_t p, int t) {
@@ -271,9 +271,9 @@ __global__ __launch_bounds__(256) void spconv_fwd_brick(const unsigned char* __r
       a_slot = raw == (int)BRK_ABSENT ? BRK_UMAX : raw;
     };
     // fragment f of the prepared tile (order of first use: ki, then lo before hi)
-    auto read_a1 = [&](int f, u32x4_t (&aq)[KI][2]) {
+    auto read_a1 = [&](int f, u32x4 (&aq)[KI][2]) {
       const int ki = f >> 1, hl = (f & 1) ^ 1;
-      aq[ki][hl] = *reinterpret_cast<const u32x4_t*>(halo + a_slot * ROWB + (((hl ? CH / 2 : 0) + ki * 4 + kg + a_slot) & (CH - 1)) * 16);
+      aq[ki][hl] = *reinterpret_cast<const u32x4*>(halo + a_slot * ROWB + (((hl ? CH / 2 : 0) + ki * 4 + kg + a_slot) & (CH - 1)) * 16);
     };
 #pragma unroll
     for (int f = 0; f < NF; f++) read_b1(0, f, breg[0]);
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_brick(const unsigned char* __r
 #if BRK_DBG & 1
             asm volatile("" ::"v"(areg[aset][ki][term == 0 ? 1 : 0]), "v"(breg[cur][ki][term == 1 ? 1 : 0][j]));
 #else
-            acc[t][j] = sp_mfma<PREC>(areg[aset][ki][term == 0 ? 1 : 0], breg[cur][ki][term == 1 ? 1 : 0][j], acc[t][j]);
+            acc[t][j] = split_mfma<PREC>(areg[aset][ki][term == 0 ? 1 : 0], breg[cur][ki][term == 1 ? 1 : 0][j], acc[t][j]);
 #endif
           }
           // ---- the slot behind this group
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_brick(const unsigned char* __r
   } else {
     // ---- a neighbourhood beyond the LDS slots: plain direct gathers (fragments straight from global memory), same products, same order
     for (int k = 0; k < K; k++) {
-      const u32x4_t* bw = reinterpret_cast<const u32x4_t*>(wimg) + (size_t)k * NF * 64 + lane;
+      const u32x4* bw = reinterpret_cast<const u32x4*>(wimg) + (size_t)k * NF * 64 + lane;
 #pragma unroll
       for (int t = 0; t < T; t++) {
         const int row = row0 + t * 16 + r;
@@ -349,18 +349,18 @@ __global__ __launch_bounds__(256) void spconv_fwd_brick(const unsigned char* __r
         if (__ballot(src >= 0) == 0ull) continue;
 #pragma unroll
         for (int ki = 0; ki < KI; ki++) {
-          u32x4_t ah = u32x4_t{0u, 0u, 0u, 0u}, al = u32x4_t{0u, 0u, 0u, 0u};
+          u32x4 ah = u32x4{0u, 0u, 0u, 0u}, al = u32x4{0u, 0u, 0u, 0u};
           if (src >= 0) {
             const unsigned char* p = in_s + (size_t)src * ROWB + (ki * 4 + kg) * 16;
-            ah = *reinterpret_cast<const u32x4_t*>(p);
-            al = *reinterpret_cast<const u32x4_t*>(p + ROWB / 2);
+            ah = *reinterpret_cast<const u32x4*>(p);
+            al = *reinterpret_cast<const u32x4*>(p + ROWB / 2);
           }
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(al, bw[(size_t)((ki * NB + j) * 2) * 64], acc[t][j]);
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(al, bw[(size_t)((ki * NB + j) * 2) * 64], acc[t][j]);
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(ah, bw[(size_t)((ki * NB + j) * 2 + 1) * 64], acc[t][j]);
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(ah, bw[(size_t)((ki * NB + j) * 2 + 1) * 64], acc[t][j]);
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(ah, bw[(size_t)((ki * NB + j) * 2) * 64], acc[t][j]);
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(ah, bw[(size_t)((ki * NB + j) * 2) * 64], acc[t][j]);
         }
       }
     }

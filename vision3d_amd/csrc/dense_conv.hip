@@ -7,7 +7,7 @@
 // Precision: every fp32 operand is split once into 16-bit pieces hi = rne(x), lo = rne(x - hi) and the product is evaluated as
 // lo*hi + hi*lo + hi*hi with fp32 accumulation on the 16-bit matrix pipe.  Activations travel between layers ALREADY split (two
 // 16-bit NHWC planes = the bytes of one fp32 tensor), weights are split and packed once per model, so the inner loop has no
-// conversions.  Two arithmetics (template parameter PREC; spconv.hip "the split-precision product" has the measurements):
+// conversions.  Two arithmetics (template parameter PREC; split_prec.h states them, with the measurements, and holds every helper):
 //   PREC 0 "bf16x3"  bf16 pieces, 2^-17 per product, scale-free.
 //   PREC 1 "f16s"    f16 pieces of x * s under a power-of-two scale s per tensor (weights: per layer, chosen at pack time, inverse
 //                    in the image's trailer; activations: static per layer, a device entry {s, 1/s, limit, ..} set by calibration --
@@ -28,101 +28,27 @@
 //   epilogue   accumulators -> LDS (fp32) -> bias + ReLU -> either the next layer's split bf16 NHWC planes
 //              (16-byte stores) or fp32 NCHW for the consumer outside this file.
 #include "v3d_internal.h"
+#include "split_prec.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef unsigned short bf16_t;  // storage type of a 16-bit piece at the C ABI (bf16 or f16 by the arithmetic)
-// native vector type for the 16-byte staging registers: HIP's uint4 is a struct with a union inside and an
-// array of them is NOT promoted to registers (it round-tripped through scratch every k-step: 142 us/conv)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <int PREC>
-__device__ __forceinline__ f32x4 dc_mfma(const u32x4 a, const u32x4 b, const f32x4 c) {
-  if constexpr (PREC == 0)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 #define DC_BM 64
 #define DC_BN 128
 #define DC_KC 32  // input channels per k-step
 #define DC_THREADS 256
 
-__device__ __forceinline__ bf16_t f32_to_bf16_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7F800000u) == 0x7F800000u) return (bf16_t)(u >> 16);  // inf / nan: truncate
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (bf16_t)(u >> 16);
-}
-__device__ __forceinline__ float bf16_to_f32(bf16_t h) { return __uint_as_float(((unsigned)h) << 16); }
-// one value -> (hi, lo) pieces; PREC 1: of x * s
-template <int PREC>
-__device__ __forceinline__ void split_val(float x, float s, bf16_t& hi, bf16_t& lo) {
-  if constexpr (PREC == 0) {
-    hi = f32_to_bf16_rne(x);
-    lo = f32_to_bf16_rne(x - bf16_to_f32(hi));
-  } else {
-    const float a = x * s;
-    const _Float16 h = (_Float16)a;
-    const _Float16 l = (_Float16)(a - (float)h);
-    hi = __builtin_bit_cast(bf16_t, h);
-    lo = __builtin_bit_cast(bf16_t, l);
-  }
-}
-// trailer of a packed weight image: {max|w| bits, 1/s_w, s_w, precision}; bf16x3 images carry it unused
-#define DC_WIMG_TRAILER 256
-#define DC_F16S_WEIGHT_TARGET 13  // max|w| * s_w in [2^13, 2^14)
-__host__ __device__ static inline float dc_pow2_scale(unsigned amax_bits, int target) {
-  const int eb = (int)((amax_bits >> 23) & 0xFFu);
-  if (eb == 0 || eb == 255) return 1.f;
-  int sb = 127 + target - (eb - 127);
-  sb = sb < 2 ? 2 : (sb > 252 ? 252 : sb);
-  const unsigned bits = (unsigned)sb << 23;
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __uint_as_float(bits);
-#else
-  float f;
-  memcpy(&f, &bits, 4);
-  return f;
-#endif
-}
-
 // ------------------------------------------------------------------------------------------------
 // weights (Cout, Cin, kh, kw) fp32 [+ per-cout scale folded in] -> packed split image
 // image[s][plane][nf][kg][j][e]  with  s = tap*(Cin/32) + chunk, plane in {hi, lo}, nf = cout/16,
 // kg = (cin%32)/8, j = cout%16, e = cin%8   -- exactly the byte order of the B tile in LDS.
 // ------------------------------------------------------------------------------------------------
-// max |w * scale[co]| into word 0 of the trailer (zeroed by the caller)
-__global__ void dc_wmax_kernel(const float* __restrict__ w, const float* __restrict__ scale, int Cout, long long per_cout,
-                               unsigned* __restrict__ trailer) {
-  unsigned m = 0u;
-  const long long n = (long long)Cout * per_cout;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
-    float v = w[t];
-    if (scale) v *= scale[t / per_cout];
-    m = max(m, __float_as_uint(v) & 0x7FFFFFFFu);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(trailer, m);
-}
-
 template <int PREC>
 __global__ void dc_pack_weights_kernel(const float* __restrict__ w, const float* __restrict__ scale, int Cout, int Cin,
                                        int ks, int CoutPad, bf16_t* __restrict__ img) {
   const int taps = ks * ks, chunks = Cin / DC_KC;
   const long long total = (long long)taps * chunks * (CoutPad / 16) * 4 * 16 * 8;
   float sw = 1.f;
-  if constexpr (PREC == 1) {
-    unsigned* trailer = reinterpret_cast<unsigned*>(img + total * 2);
-    sw = dc_pow2_scale(trailer[0], DC_F16S_WEIGHT_TARGET);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      reinterpret_cast<float*>(trailer)[1] = 1.f / sw;
-      reinterpret_cast<float*>(trailer)[2] = sw;
-      trailer[3] = 1u;
-    }
-  }
+  if constexpr (PREC == 1) sw = v3d_wimg_weight_scale(reinterpret_cast<unsigned*>(img + total * 2));
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     long long r = t;
     const int e = (int)(r % 8); r /= 8;
@@ -138,7 +64,7 @@ __global__ void dc_pack_weights_kernel(const float* __restrict__ w, const float*
       if (scale) v *= scale[co];
     }
     bf16_t hi, lo;
-    split_val<PREC>(v, sw, hi, lo);
+    split_one<PREC>(v, sw, hi, lo);
     const size_t step = (size_t)tap * chunks + chunk;
     const size_t plane_elems = (size_t)(CoutPad / 16) * 4 * 16 * 8;
     const size_t off = ((size_t)(nf * 4 + kg) * 16 + j) * 8 + e;
@@ -152,7 +78,7 @@ static size_t dc_image_payload_bytes(int Cin, int Cout, int ksize) {
   return (size_t)ksize * ksize * (Cin / DC_KC) * 2 * (size_t)pad * DC_KC * sizeof(bf16_t);
 }
 extern "C" size_t v3d_conv2d_weight_image_bytes(int Cin, int Cout, int ksize) {
-  return dc_image_payload_bytes(Cin, Cout, ksize) + DC_WIMG_TRAILER;
+  return dc_image_payload_bytes(Cin, Cout, ksize) + V3D_WIMG_TRAILER;
 }
 
 extern "C" int v3d_conv2d_pack_weights(const float* weight, const float* scale, int Cout, int Cin, int ksize, int prec,
@@ -163,8 +89,9 @@ extern "C" int v3d_conv2d_pack_weights(const float* weight, const float* scale, 
   hipStream_t st = (hipStream_t)stream;
   if (prec == V3D_PREC_F16S) {
     unsigned* trailer = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(image) + dc_image_payload_bytes(Cin, Cout, ksize));
-    V3D_CHECK_HIP(v3d_fill_async(trailer, 0, DC_WIMG_TRAILER, st));
-    hipLaunchKernelGGL(dc_wmax_kernel, dim3(128), dim3(256), 0, st, weight, scale, Cout, (long long)Cin * ksize * ksize, trailer);
+    V3D_CHECK_HIP(v3d_fill_async(trailer, 0, V3D_WIMG_TRAILER, st));
+    const long long per_cout = (long long)Cin * ksize * ksize;
+    hipLaunchKernelGGL(v3d_wmax_kernel<>, dim3(128), dim3(256), 0, st, weight, scale, per_cout, Cout * per_cout, trailer);
     hipLaunchKernelGGL(dc_pack_weights_kernel<1>, dim3(512), dim3(256), 0, st, weight, scale, Cout, Cin, ksize, pad, (bf16_t*)image);
   } else {
     hipLaunchKernelGGL(dc_pack_weights_kernel<0>, dim3(512), dim3(256), 0, st, weight, scale, Cout, Cin, ksize, pad, (bf16_t*)image);
@@ -202,7 +129,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void densify_split_kernel(const float* _
     bf16_t h, l;
     const float v = feat[t];
     if constexpr (PREC == 1) vmax = fmaxf(vmax, fabsf(v));
-    split_val<PREC>(v, s_out, h, l);
+    split_one<PREC>(v, s_out, h, l);
     hi[o] = h;
     lo[o] = l;
   }
@@ -283,7 +210,7 @@ __global__ void nchw_to_split_nhwc_kernel(const float* __restrict__ x, int B, in
     const long long bp = t / C;  // b*HW + p
     const int b = (int)(bp / HW), p = (int)(bp % HW);
     bf16_t h, l;
-    split_val<PREC>(x[((size_t)b * C + c) * HW + p], s, h, l);
+    split_one<PREC>(x[((size_t)b * C + c) * HW + p], s, h, l);
     hi[t] = h;
     lo[t] = l;
   }
@@ -314,8 +241,8 @@ __global__ __launch_bounds__(256) void nchw_to_split_nhwc_tiled_kernel(const flo
       if (2 * cp < cn)
         for (int p = tid >> 6; p < NS_PX && p0 + p < HW; p += 4) {
           bf16_t h0, l0, h1, l1;
-          split_val<PREC>(tile[p][2 * cp], s, h0, l0);
-          split_val<PREC>(tile[p][2 * cp + 1], s, h1, l1);
+          split_one<PREC>(tile[p][2 * cp], s, h0, l0);
+          split_one<PREC>(tile[p][2 * cp + 1], s, h1, l1);
           const size_t o = ((size_t)b * HW + p0 + p) * C + c0 + 2 * cp;
           *reinterpret_cast<unsigned*>(hi + o) = (unsigned)h0 | ((unsigned)h1 << 16);
           *reinterpret_cast<unsigned*>(lo + o) = (unsigned)l0 | ((unsigned)l1 << 16);
@@ -554,15 +481,15 @@ __global__ __launch_bounds__(DC_THREADS, 2) void conv2d_bf16x3_kernel(const bf16
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = dc_mfma<PREC>(al[i], bh[j], acc[i][j]);
+      for (int j = 0; j < 4; j++) acc[i][j] = split_mfma<PREC>(al[i], bh[j], acc[i][j]);
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = dc_mfma<PREC>(ah[i], bl[j], acc[i][j]);
+      for (int j = 0; j < 4; j++) acc[i][j] = split_mfma<PREC>(ah[i], bl[j], acc[i][j]);
 #pragma unroll
     for (int i = 0; i < 2; i++)
 #pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = dc_mfma<PREC>(ah[i], bh[j], acc[i][j]);
+      for (int j = 0; j < 4; j++) acc[i][j] = split_mfma<PREC>(ah[i], bh[j], acc[i][j]);
   };
 
   // prologue: step 0 -> LDS buffer 0, step 1 in flight in R1
@@ -618,8 +545,8 @@ __global__ __launch_bounds__(DC_THREADS, 2) void conv2d_bf16x3_kernel(const bf16
           v1 = fmaxf(v1, 0.f);
         }
         if constexpr (PREC == 1) vmax = fmaxf(vmax, fmaxf(fabsf(v0), fabsf(v1)));
-        split_val<PREC>(v0, sc.s_out, h0, l0);
-        split_val<PREC>(v1, sc.s_out, h1, l1);
+        split_one<PREC>(v0, sc.s_out, h0, l0);
+        split_one<PREC>(v1, sc.s_out, h1, l1);
         vh[e2] = (unsigned)h0 | ((unsigned)h1 << 16);
         vl[e2] = (unsigned)l0 | ((unsigned)l1 << 16);
       }
@@ -690,22 +617,6 @@ extern "C" int v3d_debug_dense_timeline(unsigned long long* host_out) {
 #endif
 
 __device__ __attribute__((aligned(16))) const unsigned dl_zero16[4] = {0u, 0u, 0u, 0u};  // halo source of the LDS-DMA gather
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-// (v0, v1) -> packed hi pair and lo pair (hi = RNE(v), lo = RNE(v - hi)) on the hardware converters; PREC 1: f16 pieces of v * s
-template <int PREC>
-__device__ __forceinline__ void split_pair(float v0, float v1, float s, unsigned& hi, unsigned& lo) {
-  if constexpr (PREC == 0) {
-    const bf16x2_t h = __builtin_convertvector(f32x2_t{v0, v1}, bf16x2_t);
-    hi = __builtin_bit_cast(unsigned, h);
-    const float r0 = v0 - __uint_as_float(hi << 16), r1 = v1 - __uint_as_float(hi & 0xFFFF0000u);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{r0, r1}, bf16x2_t));
-  } else {
-    v3d_split_f16_pair(v0, v1, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s))), hi, lo);
-  }
-}
 
 // one tile (MT 16-pixel fragments x 128 couts) by the whole workgroup; returns with every thread past its last LDS access
 // except the epilogue reads (the caller separates tiles with a barrier)
@@ -888,20 +799,20 @@ __device__ __forceinline__ void dl_tile(unsigned char* smem_l, const bf16_t* __r
         const u32x4 b1h0 = cb[s1][0], b1l0 = cb[s1][1];
         const u32x4 b1h1 = cb[s1][2], b1l1 = cb[s1][3];
         const u32x4 a0h = fh[u % 3][0], a0l = fl[u % 3][0], a1h = fh[u % 3][1], a1l = fl[u % 3][1];
-        acc[i0][0] = dc_mfma<PREC>(a0l, b0h0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0l, b0h1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1l, b1h0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1l, b1h1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0l, b0h0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0l, b0h1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1l, b1h0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1l, b1h1, acc[i1][1]);
         __builtin_amdgcn_sched_barrier(0);
-        acc[i0][0] = dc_mfma<PREC>(a0h, b0l0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0h, b0l1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1h, b1l0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1h, b1l1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0h, b0l0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0h, b0l1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1h, b1l0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1h, b1l1, acc[i1][1]);
         __builtin_amdgcn_sched_barrier(0);
-        acc[i0][0] = dc_mfma<PREC>(a0h, b0h0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0h, b0h1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1h, b1h0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1h, b1h1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0h, b0h0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0h, b0h1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1h, b1h0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1h, b1h1, acc[i1][1]);
         // a substep's B registers are free once its last tile has issued: refill them for the next stage
         // (unconditionally -- the last stage re-reads its own fragments: a branch here makes the compiler's
         // s_waitcnt bookkeeping merge two histories and wait for vmcnt(0) in the middle of the stage, 1350 clocks)
@@ -1167,20 +1078,20 @@ __device__ __forceinline__ bool dl_tile2d(unsigned char* smem_l, const bf16_t* _
         const u32x4 b1h0 = cb[s1][0], b1l0 = cb[s1][1];
         const u32x4 b1h1 = cb[s1][2], b1l1 = cb[s1][3];
         const u32x4 a0h = fh[u % 3][0], a0l = fl[u % 3][0], a1h = fh[u % 3][1], a1l = fl[u % 3][1];
-        acc[i0][0] = dc_mfma<PREC>(a0l, b0h0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0l, b0h1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1l, b1h0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1l, b1h1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0l, b0h0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0l, b0h1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1l, b1h0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1l, b1h1, acc[i1][1]);
         __builtin_amdgcn_sched_barrier(0);
-        acc[i0][0] = dc_mfma<PREC>(a0h, b0l0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0h, b0l1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1h, b1l0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1h, b1l1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0h, b0l0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0h, b0l1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1h, b1l0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1h, b1l1, acc[i1][1]);
         __builtin_amdgcn_sched_barrier(0);
-        acc[i0][0] = dc_mfma<PREC>(a0h, b0h0, acc[i0][0]);
-        acc[i0][1] = dc_mfma<PREC>(a0h, b0h1, acc[i0][1]);
-        acc[i1][0] = dc_mfma<PREC>(a1h, b1h0, acc[i1][0]);
-        acc[i1][1] = dc_mfma<PREC>(a1h, b1h1, acc[i1][1]);
+        acc[i0][0] = split_mfma<PREC>(a0h, b0h0, acc[i0][0]);
+        acc[i0][1] = split_mfma<PREC>(a0h, b0h1, acc[i0][1]);
+        acc[i1][0] = split_mfma<PREC>(a1h, b1h0, acc[i1][0]);
+        acc[i1][1] = split_mfma<PREC>(a1h, b1h1, acc[i1][1]);
         // a substep's B registers are free once its last tile has issued: refill them for the next tap (unconditionally:
         // behind the last tap a re-read nobody uses -- see dl_tile)
         if constexpr (i0 == MT - 1) load_b(s0);
@@ -1369,9 +1280,9 @@ __global__ __launch_bounds__(256) void conv1x1_bf16x3_small_cout_kernel(const bf
   f32x4 c_lh = {0.f, 0.f, 0.f, 0.f}, c_hl = c_lh, c_hh = c_lh;
 #pragma unroll
   for (int s = 0; s < STEPS; s++) {
-      c_lh = dc_mfma<PREC>(al[s], bh[s], c_lh);
-      c_hl = dc_mfma<PREC>(ah[s], bl[s], c_hl);
-      c_hh = dc_mfma<PREC>(ah[s], bh[s], c_hh);
+      c_lh = split_mfma<PREC>(al[s], bh[s], c_lh);
+      c_hl = split_mfma<PREC>(ah[s], bl[s], c_hl);
+      c_hh = split_mfma<PREC>(ah[s], bh[s], c_hh);
     }
   const int co = lane & 15;
   if (co >= p.cout_store) return;
@@ -1471,11 +1382,11 @@ __global__ __launch_bounds__(FH_WAVES * 64) void conv1x1_head_fused_kernel(const
       }
       const u32x4 a_h = ah[s], a_l = al[s];
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = dc_mfma<PREC>(a_l, bh[nf], acc[nf]);
+      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_l, bh[nf], acc[nf]);
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = dc_mfma<PREC>(a_h, bl[nf], acc[nf]);
+      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_h, bl[nf], acc[nf]);
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = dc_mfma<PREC>(a_h, bh[nf], acc[nf]);
+      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_h, bh[nf], acc[nf]);
     }
     // bias + ReLU + split: D[pixel = kg * 4 + r][cout = nf * 16 + px_l] -> slab[plane][pixel][cout] (bf16)
 #pragma unroll
@@ -1504,9 +1415,9 @@ __global__ __launch_bounds__(FH_WAVES * 64) void conv1x1_head_fused_kernel(const
     for (int s = 0; s < 4; s++) {
       const u32x4 a2h = *reinterpret_cast<const u32x4*>(slab + px_l * FH_ROW + s * 64 + kg * 16);
       const u32x4 a2l = *reinterpret_cast<const u32x4*>(slab + 16 * FH_ROW + px_l * FH_ROW + s * 64 + kg * 16);
-      c_lh = dc_mfma<PREC>(a2l, h_bh[s], c_lh);
-      c_hl = dc_mfma<PREC>(a2h, h_bl[s], c_hl);
-      c_hh = dc_mfma<PREC>(a2h, h_bh[s], c_hh);
+      c_lh = split_mfma<PREC>(a2l, h_bh[s], c_lh);
+      c_hl = split_mfma<PREC>(a2h, h_bl[s], c_hl);
+      c_hh = split_mfma<PREC>(a2h, h_bh[s], c_hh);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the fragment reads are done before the next tile overwrites the slab
     const int co = px_l;
@@ -1549,8 +1460,8 @@ extern "C" int v3d_conv2d_1x1_head_fused(const void* x_hi, const void* x_lo, con
   if (f16s) {
     fs.in_entry = pr->in_entry;
     fs.mid_entry = pr->out_entry;
-    fs.w1_inv = pr->w_inv ? pr->w_inv : reinterpret_cast<const float*>(reinterpret_cast<const char*>(w1_image) + dc_image_payload_bytes(128, 128, 1)) + 1;
-    fs.w2_inv = pr->w_inv2 ? pr->w_inv2 : reinterpret_cast<const float*>(reinterpret_cast<const char*>(w2_image) + dc_image_payload_bytes(128, Cout2, 1)) + 1;
+    fs.w1_inv = pr->w_inv ? pr->w_inv : reinterpret_cast<const float*>(reinterpret_cast<const char*>(w1_image) + dc_image_payload_bytes(128, 128, 1)) + V3D_WIMG_INV_SCALE;
+    fs.w2_inv = pr->w_inv2 ? pr->w_inv2 : reinterpret_cast<const float*>(reinterpret_cast<const char*>(w2_image) + dc_image_payload_bytes(128, Cout2, 1)) + V3D_WIMG_INV_SCALE;
     fs.range_flag = pr->range_flag;
   }
   auto kern = f16s ? conv1x1_head_fused_kernel<1> : conv1x1_head_fused_kernel<0>;
@@ -1714,7 +1625,7 @@ extern "C" int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const v
   p.out_entry = (f16s && y_hi) ? pr->out_entry : nullptr;
   p.range_flag = f16s ? pr->range_flag : nullptr;
   p.w_inv = (f16s && pr->w_inv) ? pr->w_inv
-                                : reinterpret_cast<const float*>(reinterpret_cast<const char*>(weight_image) + dc_image_payload_bytes(Cin, Cout, ksize)) + 1;
+                                : reinterpret_cast<const float*>(reinterpret_cast<const char*>(weight_image) + dc_image_payload_bytes(Cin, Cout, ksize)) + V3D_WIMG_INV_SCALE;
   hipStream_t st = (hipStream_t)stream;
   if (f16s)
     return dc_launch<1>(x_hi, x_lo, weight_image, bias, p, ksize, y_hi, y_lo, y_nchw, occ, work, tile_state, reset_ptr, reset_words, st);

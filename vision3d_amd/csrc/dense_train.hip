@@ -3,7 +3,8 @@
 // Reference: RPN = 7 x [Conv2d(128 -> 128, 3x3 pad 1 | 1x1, no bias) + BatchNorm2d(batch statistics) + ReLU]
 // (vision3d/detector/second.py:58-94) + the two 1x1 heads (detector/proposal.py:19-22), forward and backward, which
 // train.py:58-66 runs under autograd through cuDNN.  Rounds 1-2 left this half to MIOpen (bf16 autocast, channels_last);
-// here it is hand-written, bf16 storage / fp32 accumulation -- the arithmetic of that autocast path:
+// here it is hand-written, bf16 storage / fp32 accumulation -- the arithmetic of that autocast path (bf16 pack / unpack and the
+// hi / lo split of the fp32-class planes: split_prec.h):
 //
 //   dt_conv_kernel        implicit-GEMM convolution, NHWC bf16 -> NHWC bf16 (the raw, pre-BatchNorm output) + per-tile channel
 //                         sums for the batch statistics.  The SAME kernel on a transposed / tap-flipped weight image is the
@@ -18,6 +19,7 @@
 // Every reduction (batch statistics, dgamma / dbeta, dW, head gradients) is two-level in a fixed order: results are
 // bit-repeatable, no atomics.
 #include "v3d_internal.h"
+#include "split_prec.h"
 
 // the inference head's convolution (dense_conv.hip v3d_conv2d_nhwc_split) on bf16x3 images, every tile convolved
 static inline int dt_conv2d_plain(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias, int relu, int B, int H, int W,
@@ -26,47 +28,25 @@ static inline int dt_conv2d_plain(const void* x_hi, const void* x_lo, const void
                                nullptr, nullptr, nullptr, 0, nullptr, stream);
 }
 
-typedef __attribute__((ext_vector_type(8))) __bf16 dt_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float dt_f32x4;
-typedef unsigned dt_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short dt_bf16;  // storage type at the C ABI
-typedef __bf16 dt_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float dt_f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float dt_to_f32(dt_bf16 h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned dt_pack2(float a, float b) {  // two fp32 -> packed bf16 pair (RNE, hardware converter)
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(dt_f32x2{a, b}, dt_bf16x2));
-}
-__device__ __forceinline__ dt_bf16 dt_from_f32(float a) { return (dt_bf16)(dt_pack2(a, 0.f) & 0xFFFFu); }
-__device__ __forceinline__ void dt_unpack8(const dt_u32x4 v, float (&x)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    x[2 * i] = __uint_as_float(v[i] << 16);
-    x[2 * i + 1] = __uint_as_float(v[i] & 0xFFFF0000u);
-  }
-}
 
 // Split storage (the fp32-class training path, "bf16x3"): a tensor is TWO bf16 planes, value = hi + lo (hi = RNE(v), lo = RNE(v - hi):
-// 16 significant bits, the operand format of the 3-term products of csrc/dense_conv.hip).  The elementwise / reduction kernels below
+// 16 significant bits, the operand format of the 3-term products of csrc/dense_conv.hip; the split itself: split_prec.h PREC 0).  The elementwise / reduction kernels below
 // take a nullable `lo` plane beside every bf16 tensor: null = the bf16-storage path, unchanged.
 __device__ __forceinline__ void dt_load8(const dt_bf16* __restrict__ hi, const dt_bf16* __restrict__ lo, long long off, float (&v)[8]) {
-  dt_unpack8(*reinterpret_cast<const dt_u32x4*>(hi + off), v);
+  bf16_unpack8(*reinterpret_cast<const u32x4*>(hi + off), v);
   if (lo) {
     float w[8];
-    dt_unpack8(*reinterpret_cast<const dt_u32x4*>(lo + off), w);
+    bf16_unpack8(*reinterpret_cast<const u32x4*>(lo + off), w);
 #pragma unroll
     for (int e = 0; e < 8; e++) v[e] += w[e];
   }
 }
 __device__ __forceinline__ void dt_store8(dt_bf16* __restrict__ hi, dt_bf16* __restrict__ lo, long long off, const float (&v)[8]) {
-  const dt_u32x4 h = dt_u32x4{dt_pack2(v[0], v[1]), dt_pack2(v[2], v[3]), dt_pack2(v[4], v[5]), dt_pack2(v[6], v[7])};
-  *reinterpret_cast<dt_u32x4*>(hi + off) = h;
-  if (lo) {
-    float hv[8];
-    dt_unpack8(h, hv);
-    *reinterpret_cast<dt_u32x4*>(lo + off) = dt_u32x4{dt_pack2(v[0] - hv[0], v[1] - hv[1]), dt_pack2(v[2] - hv[2], v[3] - hv[3]),
-                                                      dt_pack2(v[4] - hv[4], v[5] - hv[5]), dt_pack2(v[6] - hv[6], v[7] - hv[7])};
-  }
+  u32x4 h, l;
+  split_act<0>(v, 1.f, h, l);
+  *reinterpret_cast<u32x4*>(hi + off) = h;
+  if (lo) *reinterpret_cast<u32x4*>(lo + off) = l;
 }
 
 #define DT_C 128          // channels of every RPN convolution (Cin = Cout)
@@ -97,7 +77,7 @@ __global__ void dt_pack_weights_kernel(const float* __restrict__ w, int taps, in
     const int tap = r;
     const int k = ss * 32 + (lane >> 4) * 8 + e, n = nt * 16 + (lane & 15);
     const float v = transpose ? w[((size_t)k * DT_C + n) * taps + (taps - 1 - tap)] : w[((size_t)n * DT_C + k) * taps + tap];
-    img[t] = dt_from_f32(v);
+    img[t] = bf16_from_f32(v);
   }
 }
 
@@ -123,7 +103,7 @@ __global__ void dt_pack_all_kernel(DtPackJobs jobs, unsigned char* __restrict__ 
     const int tap = r;
     const int k = ss * 32 + (lane >> 4) * 8 + e, n = nt * 16 + (lane & 15);
     const float v = transpose ? w[((size_t)k * DT_C + n) * taps + (taps - 1 - tap)] : w[((size_t)n * DT_C + k) * taps + tap];
-    img[t] = dt_from_f32(v);
+    img[t] = bf16_from_f32(v);
   }
 }
 
@@ -219,28 +199,28 @@ __global__ __launch_bounds__(DT_THREADS) void dt_conv_kernel(const dt_bf16* __re
 #pragma unroll
     for (int e = 0; e < 8; e++) s1[e] = s2[e] = 0.f;
     float* tl = reinterpret_cast<float*>(dt_smem + DT_NSLOT * DT_SLOT);
-    dt_f32x4 acc[4][4];
+    f32x4 acc[4][4];
     for (int G = 0; G < nstage; G++) {
       const int s = G % SPT;
       if (s == 0) {
 #pragma unroll
         for (int i = 0; i < 4; i++)
 #pragma unroll
-          for (int j = 0; j < 4; j++) acc[i][j] = dt_f32x4{0.f, 0.f, 0.f, 0.f};
+          for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
       asm volatile("s_barrier" ::: "memory");  // (pairs with the loaders' barrier of stage G)
       const unsigned char* A = dt_smem + (G % DT_NSLOT) * DT_SLOT;
       const unsigned char* Bs = A + 16384;
       // two fragment sets: the 8 reads of substep 1 are in flight while the 16 MFMAs of substep 0 issue
-      dt_bf16x8 fa[2][4], fb[2][4];
-      auto frags = [&](int ss, dt_bf16x8 (&a)[4], dt_bf16x8 (&b)[4]) {
+      bf16x8 fa[2][4], fb[2][4];
+      auto frags = [&](int ss, bf16x8 (&a)[4], bf16x8 (&b)[4]) {
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const int px = (ph * 4 + i) * 16 + (lane & 15);
-          a[i] = *reinterpret_cast<const dt_bf16x8*>(A + px * 128 + (((ss * 4 + (lane >> 4)) ^ ((px >> 1) & 7)) << 4));
+          a[i] = *reinterpret_cast<const bf16x8*>(A + px * 128 + (((ss * 4 + (lane >> 4)) ^ ((px >> 1) & 7)) << 4));
         }
 #pragma unroll
-        for (int j = 0; j < 4; j++) b[j] = *reinterpret_cast<const dt_bf16x8*>(Bs + (ss * 8 + ch * 4 + j) * 1024 + lane * 16);
+        for (int j = 0; j < 4; j++) b[j] = *reinterpret_cast<const bf16x8*>(Bs + (ss * 8 + ch * 4 + j) * 1024 + lane * 16);
       };
       frags(0, fa[0], fb[0]);
       frags(1, fa[1], fb[1]);
@@ -272,13 +252,13 @@ __global__ __launch_bounds__(DT_THREADS) void dt_conv_kernel(const dt_bf16* __re
           for (int k = 0; k < 2; k++) {
             const int row = rg + 16 * k, m = m0 + q * 32 + row;
             if (m < M) {
-              const dt_f32x4 t0 = *reinterpret_cast<const dt_f32x4*>(tl + row * DT_TS + c8 * 8);
-              const dt_f32x4 t1 = *reinterpret_cast<const dt_f32x4*>(tl + row * DT_TS + c8 * 8 + 4);
-              const dt_u32x4 v = {dt_pack2(t0[0], t0[1]), dt_pack2(t0[2], t0[3]), dt_pack2(t1[0], t1[1]), dt_pack2(t1[2], t1[3])};
-              *reinterpret_cast<dt_u32x4*>(y + (size_t)m * DT_C + c8 * 8) = v;
+              const f32x4 t0 = *reinterpret_cast<const f32x4*>(tl + row * DT_TS + c8 * 8);
+              const f32x4 t1 = *reinterpret_cast<const f32x4*>(tl + row * DT_TS + c8 * 8 + 4);
+              const u32x4 v = {bf16_pack2(t0[0], t0[1]), bf16_pack2(t0[2], t0[3]), bf16_pack2(t1[0], t1[1]), bf16_pack2(t1[2], t1[3])};
+              *reinterpret_cast<u32x4*>(y + (size_t)m * DT_C + c8 * 8) = v;
               if (stats) {
                 float xr[8];
-                dt_unpack8(v, xr);
+                bf16_unpack8(v, xr);
 #pragma unroll
                 for (int e = 0; e < 8; e++) {
                   s1[e] += xr[e];
@@ -489,11 +469,11 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
     // ------------------------------------------------------------------ multipliers
     const int pq = wave & 3, ch = wave >> 2;
     const int kg = lane >> 4, pxl = lane & 15;
-    dt_f32x4 acc[4][4];   // [cout tile][pixel tile]
+    f32x4 acc[4][4];   // [cout tile][pixel tile]
     // batch statistics: after every tile the 16 pixel-column lanes of a cout group reduce-scatter their 16 (cout tile, r) sums in a
     // fixed tree (dt_rs16), so that lane (pxl, kg) carries ONE channel -- 64 ch + 16 (pxl >> 2) + 4 kg + (pxl & 3) -- over all tiles
     float st1 = 0.f, st2 = 0.f;
-    dt_bf16x8 wf[2][4], xf[2][4];  // [32-channel substep][tile]
+    bf16x8 wf[2][4], xf[2][4];  // [32-channel substep][tile]
     // Fragment addresses.  Pixel fragment of (tap (ty, tx), pixel tile pt, substep ss), lane (pxl, kg): pixel row hp = q + c with
     // q = 72 pq + pxl (the lane's part) and c = 18 (ty + pt) + tx (a constant of the unrolled stage); byte address
     // 128 hp + 16 ((4 ss + kg) ^ (hp & 7)).  (hp & 7) only depends on c through c & 7: eight per-lane bases pw[c & 7], everything
@@ -508,17 +488,17 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
       for (int jj = 0; jj < 8; jj++) pw[jj] = (unsigned)(q * 128 + ((kg ^ ((q + jj) & 7)) << 4));
     }
     const unsigned wlane = (unsigned)(2 * DC3_ABUF + ch * 4096 + lane * 16);
-    auto read_w = [&](unsigned wb, int ss, dt_bf16x8 (&w)[4]) {  // wb: wlane + 16 KB x ring slot
+    auto read_w = [&](unsigned wb, int ss, bf16x8 (&w)[4]) {  // wb: wlane + 16 KB x ring slot
 #pragma unroll
-      for (int ct = 0; ct < 4; ct++) w[ct] = *reinterpret_cast<const __attribute__((address_space(3))) dt_bf16x8*>(lds + wb + (ss * 8 + ct) * 1024);
+      for (int ct = 0; ct < 4; ct++) w[ct] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(lds + wb + (ss * 8 + ct) * 1024);
     };
-    auto read_x = [&](int s, int ss, dt_bf16x8 (&xv)[4]) {  // s = stage within the tile: a constant of the unrolled body
+    auto read_x = [&](int s, int ss, bf16x8 (&xv)[4]) {  // s = stage within the tile: a constant of the unrolled body
       const int h = s >= 9 ? 1 : 0, tap = s - 9 * h;
       const int ty = tap / 3, tx = tap - 3 * ty;
 #pragma unroll
       for (int pt = 0; pt < 4; pt++) {
         const int c = (ty + pt) * DC3_HW + tx;
-        xv[pt] = *reinterpret_cast<const __attribute__((address_space(3))) dt_bf16x8*>(lds + (pw[c & 7] ^ (unsigned)(ss << 6)) + (h * DC3_ABUF + c * 128));
+        xv[pt] = *reinterpret_cast<const __attribute__((address_space(3))) bf16x8*>(lds + (pw[c & 7] ^ (unsigned)(ss << 6)) + (h * DC3_ABUF + c * 128));
       }
     };
     if (nstage > 0) {
@@ -531,7 +511,7 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
 #pragma unroll
       for (int a = 0; a < 4; a++)
 #pragma unroll
-        for (int p = 0; p < 4; p++) acc[a][p] = dt_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int p = 0; p < 4; p++) acc[a][p] = f32x4{0.f, 0.f, 0.f, 0.f};
       const int slot0 = __builtin_amdgcn_readfirstlane((2 * t) & 3);  // 18 stages per tile: the ring position advances by 2 per tile
 #pragma unroll
       for (int s = 0; s < DC3_SPT; s++) {
@@ -566,9 +546,9 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
         DT_STAMP(0, 112 + 2 * t);
         tile_origin(t, b, y0, x0);
         const int xx = x0 + pxl;
-        dt_f32x2 u1[8], u2[8];  // this tile, this lane's pixels: [2 cout tile + r / 2][r & 1]
+        f32x2 u1[8], u2[8];  // this tile, this lane's pixels: [2 cout tile + r / 2][r & 1]
 #pragma unroll
-        for (int e = 0; e < 8; e++) u1[e] = u2[e] = dt_f32x2{0.f, 0.f};
+        for (int e = 0; e < 8; e++) u1[e] = u2[e] = f32x2{0.f, 0.f};
 #pragma unroll
         for (int p = 0; p < 4; p++) {
           const int yy = y0 + pq * 4 + p;
@@ -581,11 +561,11 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
           unsigned lo[4], hi[4];
 #pragma unroll
           for (int a = 0; a < 4; a++) {
-            lo[a] = valid ? dt_pack2(acc[a][p][0], acc[a][p][1]) : 0u;
-            hi[a] = valid ? dt_pack2(acc[a][p][2], acc[a][p][3]) : 0u;
+            lo[a] = valid ? bf16_pack2(acc[a][p][0], acc[a][p][1]) : 0u;
+            hi[a] = valid ? bf16_pack2(acc[a][p][2], acc[a][p][3]) : 0u;
             // statistics of the ROUNDED values: what the next kernel reads
-            const dt_f32x2 va = {__uint_as_float(lo[a] << 16), __uint_as_float(lo[a] & 0xFFFF0000u)};
-            const dt_f32x2 vb = {__uint_as_float(hi[a] << 16), __uint_as_float(hi[a] & 0xFFFF0000u)};
+            const f32x2 va = {__uint_as_float(lo[a] << 16), __uint_as_float(lo[a] & 0xFFFF0000u)};
+            const f32x2 vb = {__uint_as_float(hi[a] << 16), __uint_as_float(hi[a] & 0xFFFF0000u)};
             u1[a * 2] += va; u2[a * 2] = __builtin_elementwise_fma(va, va, u2[a * 2]);          // (packed fp32 instructions)
             u1[a * 2 + 1] += vb; u2[a * 2 + 1] = __builtin_elementwise_fma(vb, vb, u2[a * 2 + 1]);
           }
@@ -593,7 +573,7 @@ __global__ __launch_bounds__(DC3_THREADS) void dt_conv3_kernel(const dt_bf16* __
           for (int a = 0; a < 2; a++) {
             const auto s0 = __builtin_amdgcn_permlane16_swap(lo[a], lo[a + 2], false, false);
             const auto s1 = __builtin_amdgcn_permlane16_swap(hi[a], hi[a + 2], false, false);
-            if (valid) *reinterpret_cast<dt_u32x4*>(dst + a * 16) = dt_u32x4{s0[0], s1[0], s0[1], s1[1]};
+            if (valid) *reinterpret_cast<u32x4*>(dst + a * 16) = u32x4{s0[0], s1[0], s0[1], s1[1]};
           }
         }
         if (stats) {
@@ -976,9 +956,9 @@ __global__ __launch_bounds__(768) void dt_wgrad_kernel(const dt_bf16* __restrict
   }
   // -------------------------------------------------------------------- multipliers
   const int t = wave & 1, cp = wave >> 1;  // input-channel tile (16 of the block's 32), cout tiles 2 cp and 2 cp + 1
-  dt_f32x4 acc[TAPS][2];
+  f32x4 acc[TAPS][2];
 #pragma unroll
-  for (int a = 0; a < TAPS; a++) acc[a][0] = acc[a][1] = dt_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int a = 0; a < TAPS; a++) acc[a][0] = acc[a][1] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int kg = lane >> 4, s16 = lane & 15, c = s16 & 3, e4 = s16 >> 2;
   const unsigned lds0 = lds_addr_dt(dt_smem);
   for (int i = 0; i < my_tiles; i++) {
@@ -998,7 +978,7 @@ __global__ __launch_bounds__(768) void dt_wgrad_kernel(const dt_bf16* __restrict
         }
       typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
       constexpr int TG = TAPS == 9 ? 3 : 1;  // taps per batch of transpose reads (a batch = one kernel row)
-      dt_bf16x8 bfrag[2];
+      bf16x8 bfrag[2];
 #pragma unroll
       for (int a0 = 0; a0 < TAPS; a0 += TG) {
         unsigned long long fa[TG][2];
@@ -1020,14 +1000,14 @@ __global__ __launch_bounds__(768) void dt_wgrad_kernel(const dt_bf16* __restrict
           else
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fa[0][0]), "+v"(fa[0][1]) :: "memory");
 #pragma unroll
-          for (int n = 0; n < 2; n++) bfrag[n] = __builtin_bit_cast(dt_bf16x8, u64x2{fb[n][0], fb[n][1]});
+          for (int n = 0; n < 2; n++) bfrag[n] = __builtin_bit_cast(bf16x8, u64x2{fb[n][0], fb[n][1]});
         } else {
           if constexpr (TG == 3)
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[2][0]), "+v"(fa[2][1]) :: "memory");
         }
 #pragma unroll
         for (int a = 0; a < TG; a++) {
-          const dt_bf16x8 af = __builtin_bit_cast(dt_bf16x8, u64x2{fa[a][0], fa[a][1]});
+          const bf16x8 af = __builtin_bit_cast(bf16x8, u64x2{fa[a][0], fa[a][1]});
 #pragma unroll
           for (int n = 0; n < 2; n++) acc[a0 + a][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfrag[n], acc[a0 + a][n], 0, 0, 0);
         }
@@ -1110,7 +1090,7 @@ __global__ __launch_bounds__(256) void dt_head_fwd_kernel(const dt_bf16* __restr
 #pragma unroll 1
     for (int p = 0; p < 16; p++) {
       float v[8];
-      dt_unpack8(*reinterpret_cast<const dt_u32x4*>(feat + m * DT_C + p * 8), v);
+      bf16_unpack8(*reinterpret_cast<const u32x4*>(feat + m * DT_C + p * 8), v);
 #pragma unroll
       for (int o = 0; o < O; o++)
 #pragma unroll
@@ -1175,7 +1155,7 @@ __global__ __launch_bounds__(256) void dt_head_bwd_weight_kernel(const dt_bf16* 
     __syncthreads();
     const int npx = (int)min((long long)64, M - m0);
     for (int px = 0; px < npx; px++) {
-      const float fv = dt_to_f32(feat[(m0 + px) * DT_C + c]) + (feat_lo ? dt_to_f32(feat_lo[(m0 + px) * DT_C + c]) : 0.f);
+      const float fv = bf16_to_f32(feat[(m0 + px) * DT_C + c]) + (feat_lo ? bf16_to_f32(feat_lo[(m0 + px) * DT_C + c]) : 0.f);
 #pragma unroll
       for (int i = 0; i < O / 2; i++) acc[i] = fmaf(gs[px][o_lo + i], fv, acc[i]);
       if (oh == 0 && c < O) db += gs[px][c];

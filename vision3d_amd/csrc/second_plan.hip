@@ -17,6 +17,7 @@
 
 #include "v3d_internal.h"
 #include "rb_device.h"
+#include "split_prec.h"
 
 struct PlanLayer {
   v3d_layer_desc d;
@@ -298,8 +299,8 @@ extern "C" int v3d_backbone_set_layer(v3d_backbone* p, int layer, const float* w
     int rc = v3d_sparse_conv_pack_weights(L.weight, L.K, L.d.cin, L.d.cout, p->prec, L.wimg, stream);
     if (rc) return rc;
     if (p->prec == V3D_PREC_F16S) {  // the image's 1 / s_w (written by the pack kernel) into the plan's hot table
-      const char* trailer = (const char*)L.wimg + v3d_sparse_conv_weight_image_bytes(L.K, L.d.cin, L.d.cout) - 256;
-      V3D_CHECK_HIP(hipMemcpyAsync(p->w_inv_tab + layer, trailer + 4, sizeof(float), hipMemcpyDeviceToDevice, st));
+      const char* trailer = (const char*)L.wimg + v3d_sparse_conv_weight_image_bytes(L.K, L.d.cin, L.d.cout) - V3D_WIMG_TRAILER;
+      V3D_CHECK_HIP(hipMemcpyAsync(p->w_inv_tab + layer, trailer + V3D_WIMG_INV_SCALE * sizeof(float), sizeof(float), hipMemcpyDeviceToDevice, st));
     }
   }
   if (scale) {

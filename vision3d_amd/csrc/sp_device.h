@@ -1,106 +1,20 @@
-// sp_device.h -- device helpers shared by the packed sparse-convolution kernels (spconv.hip, brick.hip): the split-precision
-// product (bf16x3 / f16s pieces, three MFMA terms), scale entries, hand-issued loads with counted waits, LDS-DMA.
+// sp_device.h -- device helpers shared by the packed sparse-convolution kernels (spconv.hip, brick.hip): split-row epilogues on the
+// split-precision arithmetic of split_prec.h, scale entries, hand-issued loads with counted waits, LDS-DMA.
 #pragma once
 #include "v3d_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned bf16_rne_bits(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7F800000u) == 0x7F800000u) return u >> 16;
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-// ---- the split-precision product of the packed kernels, two arithmetics (template parameter PREC of every kernel below) ----
-// Both evaluate  a * w = al*Wh + ah*Wl + ah*Wh  (three MFMA terms, fp32 accumulation, smallest terms first) on operands split into
-// hi = rne(x), lo = rne(x - hi); they differ in the 16-bit format of the pieces:
-//   PREC 0 "bf16x3"  bf16 pieces: 8 + 8 significant bits, 2^-17 per product, any fp32 magnitude (no scale to choose): the arithmetic
-//                    of rounds 1-4, kept for the training plan (gradients span too many binades for a per-tensor scale) and as
-//                    the library's `fast` inference mode.  Strict elementwise error of a SECOND layer against float64 on entries
-//                    above 1e-3 of the layer maximum: 1.1e-3 ... 2.1e-3 (torch's fp32 conv3d: 2e-5 ... 1.1e-4).
-//   PREC 1 "f16s"    f16 pieces of x * s with a power-of-two scale s per tensor: 11 + 11 significant bits, 2^-22 per product --
-//                    the error of a 1 728-term dot product is then fp32's own accumulation noise (tools/mb_f16split.hip on MI355X:
-//                    strict relative error max 1.0e-4 / rms 2.2e-6 against 1.7e-4 / 2.5e-6 for the exact-fp32 MFMA and
-//                    2.1e-3 / 5.5e-5 for bf16x3), at the SAME three MFMAs.  v_mfma_f32_16x16x32_f16 keeps subnormal f16 inputs
-//                    (probed), so a piece below 2^-14 degrades to the 2^-24 quantum instead of vanishing: with the tensor's
-//                    maximum scaled to 2^8 ... 2^14 everything down to 2^-17 of the maximum keeps full precision.
-//                    The scales: activations -- V3dActScale: {s, 1/s, limit} in device memory, chosen by the caller from the
-//                    observed maximum of the tensor with headroom (runtime.py: calibration); an output beyond the CONSUMER's
-//                    limit raises a device flag (the frame is then re-run after recalibration, like a capacity overflow) --;
-//                    weights -- per layer from max|W| at pack time, its inverse in the image's trailer.  Scaling by powers of
-//                    two is exact, so the result does not depend on the scales as long as nothing leaves the f16 range.
-typedef _Float16 spr_f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 spr_f16x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 spr_bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float spr_f32x2_t __attribute__((ext_vector_type(2)));
-
-template <int PREC>
-__device__ __forceinline__ f32x4 sp_mfma(const u32x4_t a, const u32x4_t b, const f32x4 c) {
-#ifdef SP_EXP_F16S_BF16_MFMA  // experiment only (wrong results): the f16s kernels on the bf16 instruction -- is the f16 MFMA itself slower?
-  if constexpr (true)
-#else
-  if constexpr (PREC == 0)
-#endif
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(spr_f16x8_t, a), __builtin_bit_cast(spr_f16x8_t, b), c, 0, 0, 0);
-}
-
-// 8 fp32 activations -> packed hi / lo fragments (both RNE on the hardware converters: v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32).
-// PREC 1: of x * s (s: the tensor's power-of-two scale, exact).
-template <int PREC>
-__device__ __forceinline__ void split_act(const float (&x)[8], const float s, u32x4_t& hi, u32x4_t& lo) {
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    if constexpr (PREC == 0) {
-      const spr_bf16x2_t hh = __builtin_convertvector(spr_f32x2_t{x[2 * i], x[2 * i + 1]}, spr_bf16x2_t);
-      const unsigned hb = __builtin_bit_cast(unsigned, hh);
-      const float r0 = x[2 * i] - __uint_as_float(hb << 16), r1 = x[2 * i + 1] - __uint_as_float(hb & 0xFFFF0000u);
-      hi[i] = hb;
-      lo[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(spr_f32x2_t{r0, r1}, spr_bf16x2_t));
-#ifdef SP_EXP_F16S_BF16_SPLIT  // experiment only (wrong results): the f16s kernels with the bf16 split's instructions
-    } else if constexpr (true) {
-      const spr_bf16x2_t hh = __builtin_convertvector(spr_f32x2_t{x[2 * i], x[2 * i + 1]}, spr_bf16x2_t);
-      const unsigned hb = __builtin_bit_cast(unsigned, hh);
-      const float r0 = x[2 * i] - __uint_as_float(hb << 16), r1 = x[2 * i + 1] - __uint_as_float(hb & 0xFFFF0000u);
-      hi[i] = hb;
-      lo[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(spr_f32x2_t{r0, r1}, spr_bf16x2_t));
-#endif
-    } else {
-      unsigned h, l;  // (four mixed-precision fmas per pair: v3d_common.h)
-      v3d_split_f16_pair(x[2 * i], x[2 * i + 1], __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s))), h, l);
-      hi[i] = h;
-      lo[i] = l;
-    }
-  }
-}
+#include "split_prec.h"
 
 // INS = 1: the gathered rows are ALREADY split (row = [hi: C x 16 bit | lo: C x 16 bit], the bytes of the fp32 row): the producing layer
 // wrote them that way under THIS layer's scale entry (sp_store_split below), so the lane's two 16-byte loads return its hi and lo
 // fragments directly and the main loop has no conversion work at all.  The 8 dwords travel in the same `float[8]` registers the
 // fp32 path uses: [0..3] = hi, [4..7] = lo.
 template <int PREC, int INS>
-__device__ __forceinline__ void split_in(const float (&x)[8], const float s, u32x4_t& hi, u32x4_t& lo) {
+__device__ __forceinline__ void split_in(const float (&x)[8], const float s, u32x4& hi, u32x4& lo) {
   if constexpr (INS) {
-    hi = u32x4_t{__float_as_uint(x[0]), __float_as_uint(x[1]), __float_as_uint(x[2]), __float_as_uint(x[3])};
-    lo = u32x4_t{__float_as_uint(x[4]), __float_as_uint(x[5]), __float_as_uint(x[6]), __float_as_uint(x[7])};
+    hi = u32x4{__float_as_uint(x[0]), __float_as_uint(x[1]), __float_as_uint(x[2]), __float_as_uint(x[3])};
+    lo = u32x4{__float_as_uint(x[4]), __float_as_uint(x[5]), __float_as_uint(x[6]), __float_as_uint(x[7])};
   } else {
     split_act<PREC>(x, s, hi, lo);
-  }
-}
-
-// (v0, v1) -> packed hi pair and lo pair, PREC 1: of v * s
-template <int PREC>
-__device__ __forceinline__ void sp_split_pair(const float v0, const float v1, const float s, unsigned& hi, unsigned& lo) {
-  if constexpr (PREC == 0) {
-    const spr_bf16x2_t hh = __builtin_convertvector(spr_f32x2_t{v0, v1}, spr_bf16x2_t);
-    hi = __builtin_bit_cast(unsigned, hh);
-    const float r0 = v0 - __uint_as_float(hi << 16), r1 = v1 - __uint_as_float(hi & 0xFFFF0000u);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(spr_f32x2_t{r0, r1}, spr_bf16x2_t));
-  } else {
-    v3d_split_f16_pair(v0, v1, __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s))), hi, lo);
   }
 }
 
@@ -114,7 +28,7 @@ __device__ __forceinline__ void sp_store_split(unsigned short* __restrict__ out_
                                                const float s) {
   const float pv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1 /*quad_perm [1,0,3,2]*/, 0xF, 0xF, true));
   unsigned h, l;
-  sp_split_pair<PREC>((r & 1) ? pv : v, (r & 1) ? v : pv, s, h, l);
+  split_pair<PREC>((r & 1) ? pv : v, (r & 1) ? v : pv, s, h, l);
   *reinterpret_cast<unsigned*>(out_s + (size_t)row * (2 * COUT) + ((r & 1) ? COUT : 0) + (col & ~1)) = (r & 1) ? l : h;
 }
 
@@ -151,7 +65,7 @@ template <int PREC, int COUT>
 __device__ __forceinline__ void sp_stage_put_split(unsigned char* stage, const int rowi, const int col, const int r, const float v, const float s) {
   const float pv = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1 /*quad_perm [1,0,3,2]*/, 0xF, 0xF, true));
   unsigned h, l;
-  sp_split_pair<PREC>((r & 1) ? pv : v, (r & 1) ? v : pv, s, h, l);
+  split_pair<PREC>((r & 1) ? pv : v, (r & 1) ? v : pv, s, h, l);
   *reinterpret_cast<unsigned*>(stage + rowi * SP_STAGE_STRIDE(COUT) + ((r & 1) ? COUT * 2 : 0) + (col & ~1) * 2) = (r & 1) ? l : h;
 }
 // fp32 rows (cap, COUT): out_tile = first row of the tile
@@ -177,34 +91,16 @@ __device__ __forceinline__ void sp_tile_store_split(unsigned char* stage, unsign
   sp_stage_flush<COUT>(stage, reinterpret_cast<unsigned char*>(out_s_tile), nv, lane);
 }
 
-// one value -> (hi, lo) 16-bit patterns, PREC 1: of v * s
-template <int PREC>
-__device__ __forceinline__ void split_one(const float v, const float s, unsigned short& hi, unsigned short& lo) {
-  if constexpr (PREC == 0) {
-    const unsigned h = bf16_rne_bits(v);
-    hi = (unsigned short)h;
-    lo = (unsigned short)bf16_rne_bits(v - __uint_as_float(h << 16));
-  } else {
-    const float a = v * s;
-    const _Float16 h = (_Float16)a;
-    const _Float16 l = (_Float16)(a - (float)h);
-    hi = __builtin_bit_cast(unsigned short, h);
-    lo = __builtin_bit_cast(unsigned short, l);
-  }
-}
-
 // PREC 1: scale of the input rows, the factor that undoes input and weight scales, and the consumer's limit on this launch's output
 struct SpScales {
   float s_in, undo, limit;
 };
-// trailer of a packed weight image (all precisions allocate it; PREC 1 fills it): {max|W| bits, 1/s_w, s_w, precision}
-#define V3D_WIMG_TRAILER 256
 template <int PREC>
 __device__ __forceinline__ SpScales sp_scales(const V3dActScale& as, const unsigned short* wimg, size_t img_elems) {
   SpScales r{1.f, 1.f, 3.0e38f};
   if constexpr (PREC == 1) {
     r.s_in = as.in[0];
-    r.undo = as.in[1] * (as.w_inv ? *as.w_inv : reinterpret_cast<const float*>(wimg + img_elems)[1]);
+    r.undo = as.in[1] * (as.w_inv ? *as.w_inv : reinterpret_cast<const float*>(wimg + img_elems)[V3D_WIMG_INV_SCALE]);
     if (as.next) r.limit = as.next[2];
   }
   return r;

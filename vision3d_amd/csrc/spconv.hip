@@ -6,7 +6,7 @@
 // output-stationary: every output row is produced by exactly one workgroup, written once, in a fixed
 // summation order (deterministic, no atomics); BatchNorm(eval)+ReLU are fused into the epilogue.
 //
-// Kernels: `spconv_fwd_rows*` (algo 4: packed bf16x3 product, the default for Cin >= 16), `spconv_fwd_wave` (algo 3: exact
+// Kernels: `spconv_fwd_rows*` (algo 4: packed split-precision product -- split_prec.h --, the default for Cin >= 16), `spconv_fwd_wave` (algo 3: exact
 // fp32 MFMA, the 4-channel input layer), `spconv_fwd_scalar` (algo 1: the plain VALU statement of the same sum, the
 // on-device cross-check and the fallback for channel counts the MFMA tilings do not cover).  Earlier variants that lost
 // their measurements (an LDS-staged fp32 kernel "algo 2", register-tile variants of algo 4, a two-offsets-per-round ring)
@@ -282,55 +282,19 @@ static int launch_wave(const float* in, const float* W, const int* nbr, const in
 // in the loop, no atomics -- the ablation of algo 3 showed that machinery, not the MFMAs, was the cost.
 // Rows without a neighbour under offset k simply contribute a zero A row; the ~3x redundant matrix work
 // that causes is affordable because the products run on the 16-bit matrix pipe in split precision (operands = hi + lo
-// 16-bit pieces, 3 MFMAs per product tile, fp32 accumulate: see "the split-precision product" below).  Weights are split and
+// 16-bit pieces, 3 MFMAs per product tile, fp32 accumulate: split_prec.h).  Weights are split and
 // packed ONCE per layer into the exact fragment order (v3d_sparse_conv_pack_weights), activations are split in registers.
 // Per offset a lane issues 2*KI float4 loads of its gathered row slice and KI*NB*2 16-byte loads of packed
 // weights; operands of offset k+1 are in flight while offset k multiplies (two register sets).
 
-// power-of-two scale that puts a tensor whose largest magnitude has the fp32 bits `amax_bits` into [2^target, 2^(target + 1)):
-// only the exponent is used.  Zero / subnormal maxima give 1; the exponent is clamped so that the scale AND its inverse are normal.
-__host__ __device__ static inline float v3d_pow2_scale(unsigned amax_bits, int target) {
-  const int eb = (int)((amax_bits >> 23) & 0xFFu);
-  if (eb == 0 || eb == 255) return 1.f;
-  int sb = 127 + target - (eb - 127);
-  sb = sb < 2 ? 2 : (sb > 252 ? 252 : sb);
-  const unsigned bits = (unsigned)sb << 23;
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __uint_as_float(bits);
-#else
-  float f;
-  memcpy(&f, &bits, 4);
-  return f;
-#endif
-}
-#define V3D_F16S_WEIGHT_TARGET 13  // max|W| * s_w in [2^13, 2^14)
-
-// max |w| of a weight tensor into word 0 of the image's trailer (zeroed by the caller): non-negative floats order like their bits
-__global__ void spconv_wmax_kernel(const float* __restrict__ W, long long n, unsigned* __restrict__ trailer) {
-  unsigned m = 0u;
-  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
-    m = max(m, __float_as_uint(W[t]) & 0x7FFFFFFFu);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0 && m) atomicMax(trailer, m);
-}
-
 // packed weights: img[k][ki][nb][plane][lane][8]: lane (j = lane&15, kg = lane>>4) holds
-// W[k][cin = ki*32 + kg*8 + e][cout = nb*16 + j], e < 8 (zero beyond Cin); PREC 1: of W * s_w, trailer = {max bits, 1/s_w, s_w, 1}
+// W[k][cin = ki*32 + kg*8 + e][cout = nb*16 + j], e < 8 (zero beyond Cin); PREC 1: of W * s_w, trailer: split_prec.h
 template <int PREC>
 __global__ void spconv_pack_weights_kernel(const float* __restrict__ W, int K, int Cin, int Cout, unsigned short* __restrict__ img) {
   const int KI = (Cin + 31) / 32, NB = Cout / 16;
   const long long total = (long long)K * KI * NB * 64 * 8;
   float sw = 1.f;
-  if constexpr (PREC == 1) {
-    unsigned* trailer = reinterpret_cast<unsigned*>(img + total * 2);
-    sw = v3d_pow2_scale(trailer[0], V3D_F16S_WEIGHT_TARGET);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      reinterpret_cast<float*>(trailer)[1] = 1.f / sw;
-      reinterpret_cast<float*>(trailer)[2] = sw;
-      trailer[3] = 1u;
-    }
-  }
+  if constexpr (PREC == 1) sw = v3d_wimg_weight_scale(reinterpret_cast<unsigned*>(img + total * 2));
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     long long r = t;
     const int e = (int)(r % 8); r /= 8;
@@ -372,11 +336,11 @@ __global__ void spconv_pack_batch_kernel(V3dPackJobs jobs) {
       if (mode == 0) v = W[((size_t)k * Cin + cin) * Cout + cout];
       else v = W[((size_t)(mode == 2 ? K - 1 - k : k) * Cout + cout) * Cin + cin];  // the source layer is (K, Cout, Cin)
     }
-    const unsigned h = bf16_rne_bits(v);
-    const unsigned l = bf16_rne_bits(v - __uint_as_float(h << 16));
+    unsigned short h, l;
+    split_one<0>(v, 1.f, h, l);
     const size_t base = ((((size_t)k * KI + ki) * NB + nb) * 2) * 512 + (size_t)lane * 8 + e;
-    img[base] = (unsigned short)h;
-    img[base + 512] = (unsigned short)l;
+    img[base] = h;
+    img[base + 512] = l;
   }
 }
 
@@ -391,7 +355,6 @@ int v3d_i_sparse_conv_pack_batch(const V3dPackJobs& jobs, int n, hipStream_t str
 
 // f16s: scale entry {s, 1/s, limit, max} of a tensor from its own rows -- the exact maximum, so the entry needs no range flag.
 // One workgroup (the per-op path and calibration passes: not on the frame's critical path).
-#define V3D_F16S_ACT_TARGET 13  // max|x| * s in [2^(13 - headroom), 2^(14 - headroom))
 __global__ __launch_bounds__(1024) void act_scale_from_rows_kernel(const float* __restrict__ rows, const int* __restrict__ n_ptr, int cap,
                                                                     int C, int headroom, float* __restrict__ entry) {
   __shared__ unsigned wmax[16];
@@ -484,7 +447,7 @@ extern "C" int v3d_sparse_conv_pack_weights(const float* weight, int K, int Cin,
   if (prec == V3D_PREC_F16S) {
     unsigned* trailer = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(image) + v3d_sparse_conv_weight_image_bytes(K, Cin, Cout) - V3D_WIMG_TRAILER);
     V3D_CHECK_HIP(v3d_fill_async(trailer, 0, V3D_WIMG_TRAILER, st));
-    hipLaunchKernelGGL(spconv_wmax_kernel, dim3(64), dim3(256), 0, st, weight, (long long)K * Cin * Cout, trailer);
+    hipLaunchKernelGGL(v3d_wmax_kernel<>, dim3(64), dim3(256), 0, st, weight, (const float*)nullptr, 1ll, (long long)K * Cin * Cout, trailer);
     hipLaunchKernelGGL(spconv_pack_weights_kernel<1>, dim3(256), dim3(256), 0, st, weight, K, Cin, Cout, img);
   } else {
     hipLaunchKernelGGL(spconv_pack_weights_kernel<0>, dim3(256), dim3(256), 0, st, weight, K, Cin, Cout, img);
@@ -550,8 +513,8 @@ __global__ __launch_bounds__(V3D_BLOCK) void spconv_fwd_rows(const float* __rest
   SPR_STAMP(1);
 
   float araw[2][KI][8];
-  u32x4_t braw[2][NF];
-  auto load_ops = [&](int k, float (&a)[KI][8], u32x4_t (&b)[NF]) {
+  u32x4 braw[2][NF];
+  auto load_ops = [&](int k, float (&a)[KI][8], u32x4 (&b)[NF]) {
     const int src = nbr_s[k * 16 + r];
 #pragma unroll
     for (int ki = 0; ki < KI; ki++) {
@@ -577,7 +540,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void spconv_fwd_rows(const float* __rest
         for (int e = 0; e < 8; e++) a[ki][e] = 0.f;
       }
     }
-    const u32x4_t* wp = reinterpret_cast<const u32x4_t*>(wimg) + (size_t)k * NF * 64 + lane;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(wimg) + (size_t)k * NF * 64 + lane;
 #pragma unroll
     for (int f = 0; f < NF; f++) b[f] = wp[(size_t)f * 64];
   };
@@ -585,17 +548,17 @@ __global__ __launch_bounds__(V3D_BLOCK) void spconv_fwd_rows(const float* __rest
   f32x4 acc[NB];
 #pragma unroll
   for (int j = 0; j < NB; j++) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto multiply = [&](const float (&a)[KI][8], const u32x4_t (&b)[NF]) {
+  auto multiply = [&](const float (&a)[KI][8], const u32x4 (&b)[NF]) {
 #pragma unroll
     for (int ki = 0; ki < KI; ki++) {
-      u32x4_t ah, al;
+      u32x4 ah, al;
       split_in<PREC, INS>(a[ki], ss.s_in, ah, al);
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(al, b[(ki * NB + j) * 2], acc[j]);  // smallest terms first
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(al, b[(ki * NB + j) * 2], acc[j]);  // smallest terms first
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(ah, b[(ki * NB + j) * 2 + 1], acc[j]);
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(ah, b[(ki * NB + j) * 2 + 1], acc[j]);
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(ah, b[(ki * NB + j) * 2], acc[j]);
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(ah, b[(ki * NB + j) * 2], acc[j]);
     }
   };
 
@@ -710,14 +673,14 @@ __global__ __launch_bounds__(V3D_BLOCK) void spconv_fwd_rows_big(const float* __
     const int k = t >> 6, rr = t & 63;
     nbr_s[t] = (row0 + rr < n) ? nbr[(size_t)k * cap + row0 + rr] : -1;
   }
-  u32x4_t wreg[WLOADS];
+  u32x4 wreg[WLOADS];
   auto load_w = [&](int k) {
-    const u32x4_t* wp = reinterpret_cast<const u32x4_t*>(wimg) + (size_t)k * NF * 64 + tid;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(wimg) + (size_t)k * NF * 64 + tid;
 #pragma unroll
     for (int i = 0; i < WLOADS; i++) wreg[i] = wp[(size_t)i * V3D_BLOCK];
   };
   auto store_w = [&](int buf) {
-    u32x4_t* dst = reinterpret_cast<u32x4_t*>(wbuf + buf * WBYTES) + tid;
+    u32x4* dst = reinterpret_cast<u32x4*>(wbuf + buf * WBYTES) + tid;
 #pragma unroll
     for (int i = 0; i < WLOADS; i++) dst[(size_t)i * V3D_BLOCK] = wreg[i];
   };
@@ -742,17 +705,17 @@ __global__ __launch_bounds__(V3D_BLOCK) void spconv_fwd_rows_big(const float* __
 #pragma unroll
   for (int j = 0; j < NB; j++) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto multiply = [&](const float (&a)[KI][8], int buf) {
-    const u32x4_t* bw = reinterpret_cast<const u32x4_t*>(wbuf + buf * WBYTES) + lane;
+    const u32x4* bw = reinterpret_cast<const u32x4*>(wbuf + buf * WBYTES) + lane;
 #pragma unroll
     for (int ki = 0; ki < KI; ki++) {
-      u32x4_t ah, al;
+      u32x4 ah, al;
       split_in<PREC, INS>(a[ki], ss.s_in, ah, al);
 #pragma unroll
       for (int j = 0; j < NB; j++) {
-        const u32x4_t bh = bw[(size_t)((ki * NB + j) * 2) * 64], bl = bw[(size_t)((ki * NB + j) * 2 + 1) * 64];
-        acc[j] = sp_mfma<PREC>(al, bh, acc[j]);  // smallest terms first
-        acc[j] = sp_mfma<PREC>(ah, bl, acc[j]);
-        acc[j] = sp_mfma<PREC>(ah, bh, acc[j]);
+        const u32x4 bh = bw[(size_t)((ki * NB + j) * 2) * 64], bl = bw[(size_t)((ki * NB + j) * 2 + 1) * 64];
+        acc[j] = split_mfma<PREC>(al, bh, acc[j]);  // smallest terms first
+        acc[j] = split_mfma<PREC>(ah, bl, acc[j]);
+        acc[j] = split_mfma<PREC>(ah, bh, acc[j]);
       }
     }
   };
@@ -950,8 +913,8 @@ __device__ __forceinline__ void spconv_kouter_body(const float* __restrict__ in,
                   INS ? *reinterpret_cast<const f32x4*>(sl + t * (CIN * 64) + (v * KI + ki) * 1024)
                       : *reinterpret_cast<const f32x4*>(sl + t * (CIN * 64) + ki * 2048 + ((((kg & 1) * 2 + v) ^ sw) * 16));
       }
-      const u32x4_t* bw = reinterpret_cast<const u32x4_t*>(wbuf0 + cur * WBYTES) + lane;
-      u32x4_t bh[KI][NB], bl[KI][NB];
+      const u32x4* bw = reinterpret_cast<const u32x4*>(wbuf0 + cur * WBYTES) + lane;
+      u32x4 bh[KI][NB], bl[KI][NB];
 #pragma unroll
       for (int ki = 0; ki < KI; ki++)
 #pragma unroll
@@ -965,14 +928,14 @@ __device__ __forceinline__ void spconv_kouter_body(const float* __restrict__ in,
         for (int ki = 0; ki < KI; ki++) {
           const f32x4 v0 = araw[STAGE ? 0 : cur][(t * KI + ki) * 2], v1 = araw[STAGE ? 0 : cur][(t * KI + ki) * 2 + 1];
           const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-          u32x4_t ah, al;
+          u32x4 ah, al;
           split_in<PREC, INS>(x, ss.s_in, ah, al);
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(al, bh[ki][j], acc[t][j]);  // smallest terms first
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(al, bh[ki][j], acc[t][j]);  // smallest terms first
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(ah, bl[ki][j], acc[t][j]);
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(ah, bl[ki][j], acc[t][j]);
 #pragma unroll
-          for (int j = 0; j < NB; j++) acc[t][j] = sp_mfma<PREC>(ah, bh[ki][j], acc[t][j]);
+          for (int j = 0; j < NB; j++) acc[t][j] = split_mfma<PREC>(ah, bh[ki][j], acc[t][j]);
           __builtin_amdgcn_sched_barrier(0);
           issue_chunk(t, ki, araw[STAGE ? 0 : cur ^ 1]);   // [2]  (STAGE: overwrites the slot piece this MFMA group consumed)
           __builtin_amdgcn_sched_barrier(0);
@@ -1295,8 +1258,8 @@ __device__ __forceinline__ void spconv_ring_body(const float* __restrict__ in, c
         else vm_wait_tie<16>(ar);
       }
     }
-    const u32x4_t* bw = reinterpret_cast<const u32x4_t*>(SPR_RING(R) + g * WBYTES) + lane;
-    u32x4_t ah[KI], al[KI], bh[KI][NB], bl[KI][NB];
+    const u32x4* bw = reinterpret_cast<const u32x4*>(SPR_RING(R) + g * WBYTES) + lane;
+    u32x4 ah[KI], al[KI], bh[KI][NB], bl[KI][NB];
 #pragma unroll
     for (int ki = 0; ki < KI; ki++)
 #pragma unroll
@@ -1313,11 +1276,11 @@ __device__ __forceinline__ void spconv_ring_body(const float* __restrict__ in, c
 #pragma unroll
     for (int ki = 0; ki < KI; ki++) {
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(al[ki], bh[ki][j], acc[j]);  // smallest terms first
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(al[ki], bh[ki][j], acc[j]);  // smallest terms first
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(ah[ki], bl[ki][j], acc[j]);
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(ah[ki], bl[ki][j], acc[j]);
 #pragma unroll
-      for (int j = 0; j < NB; j++) acc[j] = sp_mfma<PREC>(ah[ki], bh[ki][j], acc[j]);
+      for (int j = 0; j < NB; j++) acc[j] = split_mfma<PREC>(ah[ki], bh[ki][j], acc[j]);
       if (R + ALOOK < ROUNDS) {  // (STAGE: overwrites the slot piece this MFMA group consumed)
         __builtin_amdgcn_sched_barrier(0);
         issue_chunk(ki, R + ALOOK);

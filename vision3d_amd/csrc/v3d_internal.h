@@ -75,7 +75,7 @@ int v3d_i_nms_sorted(const void* prep_sorted, const int* order, int N, float iou
 
 int v3d_i_nms_mask_sorted(const void* prep_sorted, int N, float iou_threshold, unsigned long long* mask, hipStream_t st);
 
-// Arithmetic of the packed sparse kernels and of the dense head (spconv.hip, "the split-precision product"): bf16 pieces (2^-17 per
+// Arithmetic of the packed sparse kernels and of the dense head (split_prec.h, "the split-precision product"): bf16 pieces (2^-17 per
 // product, scale-free) or f16 pieces under per-tensor power-of-two scales (2^-22: fp32-class at the same three MFMAs).
 // (V3D_PREC_BF16X3 = 0 / V3D_PREC_F16S = 1: include/vision3d_hip.h)
 // values of a frame's summary flag word (reset to -1 by the plan's per-frame 0xFF fill; raised with atomicMax)

@@ -34,7 +34,7 @@ CALIB_HEADROOM_BITS = 5  # a later frame may exceed the calibration frame's maxi
 
 def scale_entry_from_max(amax, headroom_bits, out=None):
     """(4,) float32 device entry {s, 1/s, 2^15 / s, max} for a tensor whose largest magnitude is the 0-dim tensor `amax`: s = the
-    power of two that puts it into [2^(13 - h), 2^(14 - h)) -- csrc/spconv.hip v3d_pow2_scale, here as device-side torch ops (no
+    power of two that puts it into [2^(13 - h), 2^(14 - h)) -- csrc/split_prec.h v3d_pow2_scale, here as device-side torch ops (no
     host synchronisation)."""
     amax = amax.detach().to(torch.float32).reshape(())
     _, e = torch.frexp(amax)  # amax = m * 2^e, m in [0.5, 1)
@@ -800,6 +800,7 @@ class DenseHeadPlan(object):
                 self.w_inv = torch.ones(len(layers), dtype=torch.float32, device=dev)
             # the images' 1 / s_w (float 1 of each 256-byte trailer, written by the pack kernels) gathered into ONE hot line: the
             # kernels would otherwise open every launch on a cold miss of a line nothing else reads
+            # (csrc/split_prec.h: V3D_WIMG_TRAILER bytes, word V3D_WIMG_INV_SCALE)
             for i, ly in enumerate(layers):
                 if ly is not None:
                     self.w_inv[i:i + 1].copy_(ly["img"][-256:].view(torch.float32)[1:2])
