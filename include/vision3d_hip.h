@@ -127,6 +127,26 @@ int v3d_assign_targets(const float* gt_boxes, const int64_t* gt_class, int n_gt,
                        float* G_reg, uint8_t* M_reg, int64_t* matches, void* workspace, size_t workspace_bytes,
                        v3d_stream_t stream);
 
+/* ---- Stage-2 (RoI) targets of PV-RCNN in ONE launch, a workgroup per frame; upstream's core/refinement_targets.py raises
+ * (SURVEY.md H11), so the definition is this repository's (tests/refine_targets_ref.py).  No (n x g) matrix, no workspace.
+ * proposals (B, n, 7) f32, proposal_class (n) i64; the ground truth of all frames flat -- gt_boxes (n_gt, 7) f32, gt_class
+ * (n_gt) i64 --, frame b owning rows [gt_offsets[b], gt_offsets[b + 1]) (gt_offsets: (B + 1) i32 on the DEVICE); draws (B, n) f32.
+ * n <= 2 048 (else V3D_EUNSUPPORTED).  Unlike v3d_assign_targets there is no _workspace query: everything is staged in LDS.
+ * LIMIT THE CALLER MUST CHECK: a frame may hold at most 128 ground truths.  The frame sizes live on the device (gt_offsets), so
+ * the call cannot refuse a larger frame without a host synchronisation: it reads the first 128 of it and returns V3D_OK.  A
+ * caller knows its frame sizes on the host (vision3d_amd.core.RefinementTargetAssigner routes such batches to its torch
+ * statement).  Per RoI:
+ *   iou / match  best box_iou_rotated_3d(roi, gt) over the frame's ground truths of the RoI's class (the bits of
+ *                v3d_box_iou_rotated_3d) and the flat index of the first maximal one; no positive overlap: 0 and -1
+ *   conf         clamp((iou - conf_lo) / (conf_hi - conf_lo), 0, 1)
+ *   G_reg        box_encode.encode(gt[match], roi), yaw residual wrapped to [-pi/2, pi/2), where iou >= reg_iou; else 0
+ *   M_cls        sampled: of the foreground (iou >= fg_iou) min(#fg, fg_quota), of the rest min(#bg, rois_per_frame - that), each
+ *                by smallest (draw, index); rois_per_frame <= 0: every RoI.  M_reg = M_cls and a box target. */
+int v3d_refine_targets(const float* proposals, const int64_t* proposal_class, int B, int n, const float* gt_boxes,
+                       const int64_t* gt_class, const int32_t* gt_offsets, int n_gt, const float* draws, float conf_lo, float conf_hi,
+                       float reg_iou, float fg_iou, int rois_per_frame, int fg_quota, float* iou, int64_t* match, float* conf,
+                       float* G_reg, uint8_t* M_cls, uint8_t* M_reg, v3d_stream_t stream);
+
 /* ---- f2: GT-sampling + global augmentation of one training frame, fused (two launches with sampling, one without).
  * Replaces the chain vision3d/dataset/augmentation.py:31-48 -- SampleAugmentation :117-198 (paste at float64 positions :162-166,
  * collision filter IoU > 1e-2 :140-149, scene points under the pasted rectangles removed :195), FlipAugmentation :78-95,
@@ -578,6 +598,19 @@ int v3d_proposal_loss_fwd_bwd(const float* maps, const int8_t* g_cls, const uint
                               void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 int v3d_proposal_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
                             v3d_stream_t stream);
+
+/* ---- RefinementLoss (PV-RCNN stage 2; this repository's definition, tests/refine_targets_ref.py) and its gradient in ONE launch.
+ * rows = B * n RoIs.  R_reg: 7 residuals per row, row stride ld_reg floats; R_cls: one confidence logit per row, stride ld_cls
+ * (the two halves of the head's (rows, 8) output are read in place).  G_conf (rows) soft targets, G_reg (rows, 7), M_cls / M_reg
+ * (rows) u8.  losses[4] = {cls, reg, #M_cls, #M_reg}: cls = sum over M_cls of BCE-with-logits(R_cls, G_conf) / max(#M_cls, 1),
+ * reg = sum over M_reg and the 7 components of smooth-L1 (beta 1) / max(#M_reg, 1).  dR_reg (rows, 7), dR_cls (rows): contiguous
+ * gradients of reg / cls; _scale multiplies them with the upstream gradients (device scalars).  Double sums in a fixed order:
+ * bit-repeatable.  Unlike v3d_proposal_loss_* there is no _workspace query: one workgroup reduces in LDS, nothing is staged in
+ * global memory. */
+int v3d_refine_loss_fwd_bwd(const float* R_reg, int ld_reg, const float* R_cls, int ld_cls, const float* G_conf, const float* G_reg,
+                            const uint8_t* M_cls, const uint8_t* M_reg, int rows, float* losses, float* dR_reg, float* dR_cls,
+                            v3d_stream_t stream);
+int v3d_refine_loss_scale(float* dR_reg, float* dR_cls, int rows, const float* g_cls, const float* g_reg, v3d_stream_t stream);
 
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.

@@ -1,5 +1,5 @@
 """The part of `vision3d.core` that sits on the hot path (reference: vision3d/core/__init__.py; its visdom plotter
-and the unused refinement-target assigner are out of scope).  Resolved on first access."""
+is out of scope; its refinement-target assigner raises upstream and is defined here).  Resolved on first access."""
 import importlib
 
 _EXPORTS = {
@@ -7,6 +7,7 @@ _EXPORTS = {
     "AnchorGenerator": "anchor_generator",
     "Preprocessor": "preprocess", "TrainPreprocessor": "preprocess",
     "ProposalTargetAssigner": "proposal_targets",
+    "RefinementTargetAssigner": "refinement_targets",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -299,6 +299,32 @@ V3D_HD float iou_prepped_lds(const BoxPrep& a, const BoxPrep& b, P2* pts, float*
   return inter / (a.area + b.area - inter);
 }
 
+// A 3-D box (x, y, z, w, l, h, yaw; z = centre) prepared once: its BEV rectangle (columns 0, 1, 3, 4, 6), z extent, volume.
+struct Box3Prep {
+  BoxPrep bev;
+  float zlo, zhi, vol;
+};
+
+V3D_HD Box3Prep prep_box3(const float* b) {
+  const float bev[5] = {b[0], b[1], b[3], b[4], b[6]};
+  Box3Prep r;
+  r.bev = prep_box(bev);
+  r.zlo = b[2] - b[5] / 2.f;
+  r.zhi = b[2] + b[5] / 2.f;
+  r.vol = b[3] * b[4] * b[5];
+  return r;
+}
+
+// box_iou_rotated_3d(a, b): BEV intersection area x overlap of the z extents / union of the volumes (the one statement of the
+// operator: v3d_box_iou_rotated_3d and the stage-2 target assigner both evaluate THIS, so they agree bit for bit).
+V3D_HD float iou3_prepped_lds(const Box3Prep& a, const Box3Prep& b, P2* pts, float* dist) {
+  const float inter_bev = inter_prepped_lds(a.bev, b.bev, pts, dist);
+  const float oh = fmaxf(fminf(a.zhi, b.zhi) - fmaxf(a.zlo, b.zlo), 0.f);
+  const float inter = inter_bev * oh;
+  const float den = a.vol + b.vol - inter;
+  return den > 0.f ? inter / den : 0.f;
+}
+
 V3D_HD float single_box_iou_rotated(const float* b1, const float* b2) {
   const BoxPrep a = prep_box(b1), b = prep_box(b2);
   return iou_prepped(a, b);

@@ -8,6 +8,7 @@ _EXPORTS = {
     "Second": "second",
     "ProposalLoss": "proposal",
     "ProposalLayer": "proposal",
+    "RefinementLoss": "refinement",
 }
 __all__ = sorted(_EXPORTS)
 

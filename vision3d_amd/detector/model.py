@@ -361,6 +361,34 @@ class PV_RCNN(nn.Module):
             item["boxes_refined"] = self.refinement_layer.apply_refinements(deltas, boxes)
         return item
 
+    # ---- training of both stages (no upstream counterpart: its `forward` raises and its stage-2 target assigner is dead code).
+    def refinement_targets(self):
+        """The model's RefinementTargetAssigner (built on first use: it holds no parameters; set its `generator` to seed the
+        sampling draws, or hand `refine_draws` in with the item)."""
+        assigner = self.__dict__.get("_refinement_targets")
+        if assigner is None:
+            from ..core.refinement_targets import RefinementTargetAssigner
+            assigner = self.__dict__["_refinement_targets"] = RefinementTargetAssigner(self.cfg)
+        return assigner
+
+    def train_forward(self, item, samples=None):
+        """Stage 1 + stage 2 under autograd.  The stage-1 proposals are taken without gradient (the refinement trains on them as
+        constants: RoI pooling and the stage-2 targets see detached boxes, so the stage-1 head learns from the stage-1 loss alone;
+        the backbone and the set-abstraction modules learn from both), stage-2 targets are assigned against the item's per-frame
+        `boxes` / `class_idx` lists (draws: `refine_draws`, else the assigner's generator).  Leaves in `item`: what `forward` leaves
+        except `boxes_refined` (P_cls, P_reg for ProposalLoss; proposals, R_reg, R_cls, ...) and R_iou, R_match, G_conf, G_rreg,
+        M_rcls, M_rreg for RefinementLoss."""
+        item = self.proposal(item)
+        features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
+        with torch.no_grad():
+            boxes, scores, class_idx = self.stage1_proposals(item)
+        boxes = boxes.detach()
+        pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
+        deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
+        item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,
+                    pooled_features=pooled, R_reg=deltas, R_cls=conf)
+        return self.refinement_targets()(item)
+
     # ---- two frames in flight from ONE host thread (round 6).  `inference` enqueues stage 1, WAITS for its row counts (the level views
     # are sized by them), enqueues stage 2 and waits again for the result: the GPU idles while the host enqueues, the host while the
     # GPU drains.  Split in three, stage 1 of frame i + 1 is queued BEFORE frame i's counts are read, and frame i's result is read

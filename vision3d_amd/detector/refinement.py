@@ -2,12 +2,28 @@
 is meaningful: `apply_refinements` raises and `forward` splits with `split(1)` on dim 0, which works
 only for batch size 2.  The evident intent -- 7 box deltas + 1 confidence on the last
 dim -- is what `forward` returns here; `apply_refinements` is defined as the VoxelNet decoding the rest of the
-reference uses for every box residual (core/box_encode.py:13-23), with the proposal in the anchor's role."""
+reference uses for every box residual (core/box_encode.py:13-23), with the proposal in the anchor's role.
+
+Training (no upstream counterpart; the definition is this repository's, restated in tests/refine_targets_ref.py):
+`encode_refinements` inverts `apply_refinements`, `RefinementLoss` is the stage-2 loss over the targets of
+core/refinement_targets.py -- one native pass (csrc/refine_targets.hip) with the torch expressions kept beside it."""
+import math
+
 import torch
+import torch.nn.functional as F
 from torch import nn
 
-from ..core.box_encode import decode
+from ..core.box_encode import decode, encode
 from .layers import MLP
+
+
+def encode_refinements(boxes, proposals):
+    """(…, 7) boxes + (…, 7) proposals -> residuals that `apply_refinements` turns back into the boxes: components 0-5 of
+    core/box_encode.encode, the yaw residual wrapped to [-pi/2, pi/2) (a perfect proposal gets 0, small errors on either side stay
+    small; stage 1 keeps upstream's [0, pi) wrap).  The decoded yaw equals the box's modulo pi."""
+    out = encode(boxes, proposals)
+    out[..., 6] = torch.remainder((boxes[..., 6] - proposals[..., 6]) + math.pi / 2, math.pi) - math.pi / 2
+    return out
 
 
 class RefinementLayer(nn.Module):
@@ -31,3 +47,96 @@ class RefinementLayer(nn.Module):
         """features (B, N, C) pooled RoI features -> (box_deltas (B,N,7), scores (B,N,1))."""
         out = self.mlp(features)
         return out.split([self.cfg.BOX_DOF, 1], dim=-1)
+
+
+def _rows(t, width):
+    """(..., width) float32 -> (tensor to read, row stride in floats): views whose rows are evenly spaced (the two halves of the
+    head's (B, n, 8) output) are read in place, anything else through a contiguous copy."""
+    t = t.detach()
+    if t.dim() >= 2 and (width == 1 or t.stride(-1) == 1) and t.stride(-2) >= width \
+            and all(t.stride(i) == t.stride(i + 1) * t.shape[i + 1] for i in range(t.dim() - 2)):
+        return t, t.stride(-2)
+    return t.contiguous(), width
+
+
+class FusedRefinementLossFunction(torch.autograd.Function):
+    """RefinementLoss.forward_torch and its gradient in one native pass (csrc/refine_targets.hip): (R_reg (..., 7), R_cls (..., 1),
+    G_conf, G_rreg, M_rcls u8, M_rreg u8) -> (cls_loss, reg_loss); the kernel's (#M_rcls, #M_rreg) stay on the node as
+    `loss.grad_fn.counts`.  The gradient is computed with the forward; backward scales it with the upstream gradients."""
+
+    @staticmethod
+    def forward(ctx, r_reg, r_cls, g_conf, g_reg, m_cls, m_reg):
+        from .. import _lib as L
+        rows = g_conf.numel()
+        reg, ld_reg = _rows(r_reg, 7)
+        cls, ld_cls = _rows(r_cls, 1)
+        dev = r_reg.device
+        losses = torch.empty(4, dtype=torch.float32, device=dev)
+        d_reg = torch.empty(r_reg.shape, dtype=torch.float32, device=dev)
+        d_cls = torch.empty(r_cls.shape, dtype=torch.float32, device=dev)
+        with L.device_guard(dev):
+            L.check(L.lib().v3d_refine_loss_fwd_bwd(L.ptr(reg), ld_reg, L.ptr(cls), ld_cls, L.ptr(g_conf), L.ptr(g_reg), L.ptr(m_cls),
+                                                    L.ptr(m_reg), rows, L.ptr(losses), L.ptr(d_reg), L.ptr(d_cls), L.stream_ptr()),
+                    "refine_loss_fwd_bwd")
+        ctx.grads, ctx.rows = (d_reg, d_cls), rows
+        ctx.counts = losses[2:4]  # (#M_rcls, #M_rreg) as the kernel counted them
+        return losses[0], losses[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls_loss, g_reg_loss):
+        from .. import _lib as L
+        grads, ctx.grads = ctx.grads, None
+        if grads is None:
+            raise RuntimeError("fused refinement loss: backward called twice (the gradient buffers are consumed by the first call)")
+        d_reg, d_cls = grads
+        gc = g_cls_loss.to(torch.float32).contiguous()
+        gr = g_reg_loss.to(torch.float32).contiguous()
+        with L.device_guard(d_reg.device):
+            L.check(L.lib().v3d_refine_loss_scale(L.ptr(d_reg), L.ptr(d_cls), ctx.rows, L.ptr(gc), L.ptr(gr), L.stream_ptr()),
+                    "refine_loss_scale")
+        return d_reg, d_cls, None, None, None, None
+
+
+class RefinementLoss(nn.Module):
+    """Stage-2 loss over (R_reg, R_cls) and the targets of RefinementTargetAssigner (G_conf, G_rreg, M_rcls, M_rreg):
+    refine_cls_loss = sum over M_rcls of BCE-with-logits(R_cls, G_conf) / max(#M_rcls, 1) (PV-RCNN's IoU-guided confidence),
+    refine_reg_loss = sum over M_rreg and the 7 components of smooth-L1 (beta 1) / max(#M_rreg, 1),
+    loss = refine_cls_loss + TRAIN.LAMBDA * refine_reg_loss."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+
+    def _result(self, cls_loss, reg_loss):
+        return dict(loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss, refine_cls_loss=cls_loss, refine_reg_loss=reg_loss)
+
+    def _fused(self, item):
+        """The native pass applies to float32 predictions on the GPU with targets in the assigner's layout; else None."""
+        R_reg, R_cls, G_conf, G_rreg, M_rcls, M_rreg = (item[k] for k in ("R_reg", "R_cls", "G_conf", "G_rreg", "M_rcls", "M_rreg"))
+        lead = tuple(G_conf.shape)
+        if not R_reg.is_cuda or R_reg.dtype != torch.float32 or R_cls.dtype != torch.float32 or G_conf.dtype != torch.float32 \
+                or G_rreg.dtype != torch.float32 or tuple(R_reg.shape) != lead + (7,) or tuple(G_rreg.shape) != lead + (7,) \
+                or tuple(M_rcls.shape) != lead or tuple(M_rreg.shape) != lead or R_cls.numel() != G_conf.numel():
+            return None
+        if any(t.device != R_reg.device for t in (R_cls, G_conf, G_rreg, M_rcls, M_rreg)):
+            return None
+        as_u8 = lambda m: (m if m.dtype in (torch.bool, torch.uint8) else m.ne(0)).contiguous().view(torch.uint8)
+        cls_loss, reg_loss = FusedRefinementLossFunction.apply(R_reg, R_cls.reshape(lead + (1,)), G_conf.contiguous(),
+                                                              G_rreg.contiguous(), as_u8(M_rcls), as_u8(M_rreg))
+        return self._result(cls_loss, reg_loss)
+
+    def forward_torch(self, item):
+        """The same loss op by op in torch (any device / dtype): the fallback and the cross-check of the native pass."""
+        R_reg, R_cls, G_conf, G_rreg, M_rcls, M_rreg = (item[k] for k in ("R_reg", "R_cls", "G_conf", "G_rreg", "M_rcls", "M_rreg"))
+        M_rcls, M_rreg = M_rcls.ne(0), M_rreg.ne(0)
+        zero = R_reg.new_zeros(())
+        bce = F.binary_cross_entropy_with_logits(R_cls.reshape(G_conf.shape), G_conf.type_as(R_cls), reduction="none")
+        cls_loss = torch.where(M_rcls, bce, zero).sum() / M_rcls.sum().clamp(min=1).type_as(R_reg)
+        sl1 = F.smooth_l1_loss(R_reg, G_rreg.type_as(R_reg), reduction="none")
+        reg_loss = torch.where(M_rreg.unsqueeze(-1), sl1, zero).sum() / M_rreg.sum().clamp(min=1).type_as(R_reg)
+        return self._result(cls_loss, reg_loss)
+
+    def forward(self, item):
+        fused = self._fused(item)
+        return fused if fused is not None else self.forward_torch(item)

@@ -21,9 +21,13 @@ def furthest_point_sample(xyz, npoint):
 
 def _scatter_add_backward(grad_out, idx_flat, n):
     """grad_out (B, C, J), idx_flat (B, J) -> (B, C, N): gradient of a gather along the last axis."""
-    b, c, _ = grad_out.shape
-    grad = grad_out.new_zeros((b, c, n))
-    return grad.scatter_add_(2, idx_flat.long().unsqueeze(1).expand(-1, c, -1), grad_out)
+    # rows accumulated through index_put_ (sorted: a fixed summation order) instead of scatter_add_ (atomics): a train step's
+    # gradients then repeat from run to run as far as these two operators go
+    b, c, j = grad_out.shape
+    rows = grad_out.transpose(1, 2).reshape(b * j, c)
+    flat = (idx_flat.long() + torch.arange(b, device=idx_flat.device).unsqueeze(1) * n).reshape(-1)
+    grad = grad_out.new_zeros((b * n, c)).index_put_((flat,), rows, accumulate=True)
+    return grad.view(b, n, c).transpose(1, 2).contiguous()
 
 
 class _GatherFunction(torch.autograd.Function):

@@ -115,6 +115,58 @@ def make_waymo_cloud(seed=0, n_points=180000, order="shuffled"):
     return make_cloud(seed, n_points, WAYMO_BOUNDS, fov_deg=180.0, az_steps=3000, n_beams=64, n_cars=40, order=order)
 
 
+CLASS_WLH = (CAR_WLH, (0.6, 0.8, 1.73), (0.6, 1.76, 1.73))  # the default anchors' sizes (core/config.py)
+
+
+ROI_LEVELS_FG = (0, 0, 0, 0, 0, 0, 0, 1, 2, 3)  # per ten RoIs: seven at the small noise level, one medium, one large, one far away
+ROI_LEVELS_BG = (0, 0, 1, 1, 2, 2, 2, 3, 3, 3)
+
+
+def jitter_rois(gt, topk, rng, levels=ROI_LEVELS_FG):
+    """`topk` RoIs made from the ground truths `gt` (g, 7), walking through them in turn: offsets and size changes of ~2 %, ~10 %
+    and ~25 % of the box dimensions (levels 0, 1, 2), or moved hundreds of metres away (level 3: overlaps nothing); RoI i of ten
+    is at `levels[i % 10]`.  Each ground truth is the source of some RoI once topk >= 10 g."""
+    base = np.array([0.02, 0.10, 0.25])
+    out = np.zeros((topk, 7), np.float32)
+    for i in range(topk):
+        src, lvl = gt[(i // len(levels)) % len(gt)], levels[i % len(levels)]
+        roi = np.array(src, np.float64)
+        if lvl == 3:
+            roi[:2] += rng.choice([-1.0, 1.0], 2) * rng.uniform(200, 300, 2)
+        else:
+            amp = base[lvl] * rng.uniform(0.5, 1.5, 7) * rng.choice([-1.0, 1.0], 7)
+            roi[0:3] += amp[0:3] * src[3:6]
+            roi[3:6] *= np.exp(amp[3:6])
+            roi[6] += amp[6]
+        out[i] = roi
+    return out
+
+
+def make_refine_case(seed=0, n_cls=1, batch=1, topk=100, gt_per_class=8):
+    """Inputs of the stage-2 target assignment: per frame `gt_per_class` ground truths of every class, and RoIs in the
+    (n_cls, topk) group-major layout of PV_RCNN.stage1_proposals made by `jitter_rois` from the ground truths of the group's class.
+    Even frames are mostly foreground, odd frames mostly background.
+    -> proposals (batch, n_cls * topk, 7) f32, proposal_class (n_cls * topk,) i64, boxes / class_idx per-frame lists, draws
+    (batch, n_cls * topk) f32 in [0, 1).  Deterministic in `seed`."""
+    rng = np.random.default_rng(70_000 + seed)
+    proposals = np.zeros((batch, n_cls * topk, 7), np.float32)
+    boxes, class_idx = [], []
+    for b in range(batch):
+        g = n_cls * gt_per_class
+        gt = np.zeros((g, 7))
+        cls = np.repeat(np.arange(n_cls), gt_per_class)
+        gt[:, 0], gt[:, 1], gt[:, 2] = rng.uniform(5, 65, g), rng.uniform(-30, 30, g), rng.uniform(-1.2, -0.7, g)
+        gt[:, 3:6] = np.asarray(CLASS_WLH)[cls % 3] * rng.uniform(0.9, 1.1, (g, 3))
+        gt[:, 6] = rng.uniform(-np.pi, np.pi, g)
+        for c in range(n_cls):
+            proposals[b, c * topk:(c + 1) * topk] = jitter_rois(gt[cls == c], topk, rng, ROI_LEVELS_FG if b % 2 == 0 else ROI_LEVELS_BG)
+        boxes.append(gt.astype(np.float32))
+        class_idx.append(cls.astype(np.int64))
+    proposal_class = np.repeat(np.arange(n_cls), topk).astype(np.int64)
+    draws = rng.random((batch, n_cls * topk)).astype(np.float32)
+    return proposals, proposal_class, boxes, class_idx, draws
+
+
 def make_gt_boxes(seed=0, n_extra=15):
     """GT boxes (n,7) for the train configuration: the scene's cars + `n_extra` sampled ones
     (configs/second/car.yaml:18 AUG.NUM_SAMPLE_OBJECTS)."""
