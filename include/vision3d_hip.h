@@ -321,6 +321,18 @@ int v3d_densify(const float* feat, const int32_t* coords, const int32_t* n, int 
 size_t v3d_fps_workspace(int B, int N);
 int v3d_furthest_point_sample(const float* xyz, int B, int N, int K, int32_t* idx, void* workspace,
                               size_t workspace_bytes, v3d_stream_t stream);
+/* Sectorized proposal-centric keypoint sampling (csrc/keypoints.hip; definition: vision3d_amd/pointnet2/pointnet2_utils.py).  Per frame
+ * the finite points within 0.5 max(w, l, h) + radius of some proposal (x, y, z, w, l, h, yaw) -- all finite points if that leaves none,
+ * or with proposals == NULL / P == 0 -- are split into S azimuth sectors; sector k gets a quota proportional to its size and an
+ * independent farthest-point chain (first pick = lowest index, ties -> lowest index); idx (B, K) = the sectors' picks in sector
+ * order, short frames padded by idx[i] = idx[i mod filled].  points: B frames of N rows of `point_stride` >= 3 floats (x, y, z first).
+ * sector_counts (B, S), optional: candidates per sector.  Five launches, no host read, capturable; any N (a sector of up to
+ * 24 576 points keeps its chain in registers -- what 1 024 lanes x 128 VGPRs hold without a spill --, a larger one streams its
+ * running distances through the workspace: same indices, slower steps).  workspace: 16-byte aligned scratch of v3d_keypoints_sector_workspace bytes.
+ * V3D_EINVAL: S outside 1-64, P > 1024, K < 1, N < 1, point_stride < 3, short workspace. */
+size_t v3d_keypoints_sector_workspace(int B, int N, int S);
+int v3d_keypoints_sector(const float* points, int point_stride, int B, int N, int K, int S, const float* proposals, int P, float radius,
+                         int32_t* idx, int32_t* sector_counts, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 int v3d_gather_points(const float* feat, const int32_t* idx, int B, int C, int N, int K, float* out,
                       v3d_stream_t stream);
 /* idx_b == NULL: one radius (radius_b / nsample_b ignored).  idx_b != NULL: two radii around the same queries in ONE scan of the

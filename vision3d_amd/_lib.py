@@ -63,6 +63,8 @@ _SIGNATURES = {
     "v3d_densify": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "v3d_fps_workspace": (_sz, [_i, _i]),
     "v3d_furthest_point_sample": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "v3d_keypoints_sector_workspace": (_sz, [_i, _i, _i]),
+    "v3d_keypoints_sector": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "v3d_gather_points": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "v3d_ball_query": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _f, _i, _vp, _vp]),
     "v3d_ball_query_grid_workspace": (_sz, [_i, _i]),

@@ -62,6 +62,9 @@ def _defaults():
     ]
     return Node(dict(
         C_IN=4, NUM_KEYPOINTS=2048, STRIDES=[1, 2, 4, 8], SAMPLES_PN=[16, 32],
+        # keypoint sampler of PV-RCNN: "fps" (one farthest-point chain per cloud), "sector" (a chain per azimuth sector) or "spc"
+        # (sectorized AND proposal-centric: only points within RADIUS of a stage-1 proposal) -- pointnet2_utils.sector_point_sample
+        KEYPOINTS=dict(SAMPLER="fps", NUM_SECTORS=6, RADIUS=1.6),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",

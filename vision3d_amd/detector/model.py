@@ -3,7 +3,9 @@
 Data flow of the pieces that exist upstream (its `forward` raises: stage 2 was never wired, model.py:84-85; here `forward` /
 `inference` wire them the evident way -- SURVEY.md 8(f) rank 3 -- and say so, this is the repository's definition):
 
-    points --FPS--> keypoints --------------------------------------------+
+    points --FPS--> keypoints --------------------------------------------+      (KEYPOINTS.SAMPLER "sector": a chain per azimuth
+                                                                          |       sector; "spc": behind stage 1, among the points near
+                                                                          |       its proposals -- pointnet2_utils.sector_point_sample)
     voxels --sparse CNN--> 4 levels of (xyz, features) + BEV map          |
     [raw points, level 0..3] --set abstraction around the keypoints--> per-keypoint features, + bilinear BEV lookup
     BEV map --ProposalLayer--> (P_cls, P_reg)
@@ -50,12 +52,38 @@ class PV_RCNN(nn.Module):
         return nn.Sequential(*(_set_abstraction(radii, mlps, cfg.SAMPLES_PN)
                                for radii, mlps in zip(cfg.PSA.RADII, cfg.PSA.MLPS)))
 
-    def sample_keypoints(self, points):
-        """points (B, N, >=3) -> (B, NUM_KEYPOINTS, 3): farthest-point sample of the xyz columns."""
+    def keypoint_sampler(self):
+        """-> (SAMPLER, NUM_SECTORS, RADIUS) of cfg.KEYPOINTS (a config written before the key existed samples by plain FPS)."""
+        kp = self.cfg.get("KEYPOINTS") or {}
+        sampler = kp.get("SAMPLER", "fps")
+        if sampler not in ("fps", "sector", "spc"):
+            raise ValueError(f"KEYPOINTS.SAMPLER must be 'fps', 'sector' or 'spc', not {sampler!r}")
+        return sampler, int(kp.get("NUM_SECTORS", 6)), float(kp.get("RADIUS", 1.6))
+
+    def sample_keypoints(self, points, proposals=None):
+        """points (B, N, >=3) -> (B, NUM_KEYPOINTS, 3) of the xyz columns: a farthest-point sample (KEYPOINTS.SAMPLER "fps"), one
+        chain per azimuth sector ("sector"), or that among the points near the stage-1 `proposals` (B, n, 7) ("spc")."""
+        sampler, sectors, radius = self.keypoint_sampler()
         xyz = points[..., :3].contiguous()
-        picked = pn2.furthest_point_sample(xyz, self.cfg.NUM_KEYPOINTS)           # (B, K) int32
+        if sampler == "fps":
+            picked = pn2.furthest_point_sample(xyz, self.cfg.NUM_KEYPOINTS)       # (B, K) int32
+        else:
+            if sampler == "spc" and proposals is None:
+                raise RuntimeError("sample_keypoints: KEYPOINTS.SAMPLER 'spc' samples around the stage-1 proposals; pass them")
+            picked = pn2.sector_point_sample(points, self.cfg.NUM_KEYPOINTS, sectors, proposals.detach() if sampler == "spc" else None,
+                                             radius)
         planes = pn2.gather_operation(xyz.transpose(1, 2).contiguous(), picked)   # (B, 3, K)
         return planes.transpose(1, 2).contiguous()
+
+    def _proposals_then_keypoints(self, item):
+        """KEYPOINTS.SAMPLER "spc" (and no keypoints handed in): stage 1's proposals first, the keypoints sampled around them on the
+        main stream.  -> what stage1_proposals returned, or None when the keypoints do not wait for stage 1."""
+        if self.keypoint_sampler()[0] != "spc" or "keypoints" in item:
+            return None
+        out = self.stage1_proposals(item)  # (in the caller's autograd mode: what `forward` leaves in the item is the same in every mode)
+        with torch.no_grad():
+            item["keypoints"] = self.sample_keypoints(item["points"], out[0].detach())
+        return out
 
     def _pointnets(self, sources, keypoint_xyz):
         """sources: [(xyz (B, N, 3), features (B, N, C))] -> [(B, C_out, K)], one per source."""
@@ -128,7 +156,7 @@ class PV_RCNN(nn.Module):
         # voxel CNN and the proposal head, and joins before the first consumer (the set abstraction of stage 2).  A caller that
         # already knows the next frame can start its sampling earlier still (`prefetch_keypoints`).
         main = torch.cuda.current_stream(item["points"].device)
-        if "keypoints" not in item:
+        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc":  # ("spc": sampled behind stage 1, _proposals_then_keypoints)
             self.prefetch_keypoints(item)
         native = self._native_item(item)
         if native:                    # eval, no autograd, voxels of the device Preprocessor: the sparse CNN as one native plan
@@ -272,6 +300,7 @@ class PV_RCNN(nn.Module):
         (2.48 ms for 2 048 of 16 384 points), so the samplings of frames i + 1, i + 2, ... run side by side on different compute
         units when the caller looks that far ahead (measured in round 6, two ahead: no gain while the main stream is bound by its eager
         launches)."""
+        self._refuse_prefetch_under_spc()
         points = item["points"]
         lane = self.__dict__.get("_prefetch_lane", 0)
         self.__dict__["_prefetch_lane"] = (lane + 1) % self.PREFETCH_LANES
@@ -287,6 +316,7 @@ class PV_RCNN(nn.Module):
         """The same for SEVERAL frames at once: farthest-point sampling takes a batch -- one workgroup (one compute unit) per cloud in
         ONE launch, 2.48 ms for all of them instead of 2.48 ms each (side streams of their own do not buy that: five streams are
         more than the four hardware queues).  Frames of one size only; else frame by frame."""
+        self._refuse_prefetch_under_spc()
         pts = [it["points"] for it in items]
         if len(items) < 2 or any(p.shape[1:] != pts[0].shape[1:] for p in pts):
             return [self.prefetch_keypoints(it) for it in items]
@@ -305,6 +335,11 @@ class PV_RCNN(nn.Module):
                 it["_keypoints_ready"] = ready
                 k += p.shape[0]
         return items
+
+    def _refuse_prefetch_under_spc(self):
+        if self.keypoint_sampler()[0] == "spc":
+            raise RuntimeError("prefetch_keypoints: KEYPOINTS.SAMPLER 'spc' samples around the frame's stage-1 proposals, so the "
+                               "keypoints cannot be started before stage 1 (use 'sector' or 'fps' to prefetch)")
 
     @staticmethod
     def _side_stream(device, lane=0):
@@ -351,8 +386,9 @@ class PV_RCNN(nn.Module):
         (B, n, NUM_GRIDPOINTS, 3) in [0, 1) fixes the RoI grid points (the reference draws them with an unseeded torch.rand,
         roi_grid_pool.py:59)."""
         item = self.proposal(item)
+        early = self._proposals_then_keypoints(item)
         features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
-        boxes, scores, class_idx = self.stage1_proposals(item)
+        boxes, scores, class_idx = early or self.stage1_proposals(item)
         pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
         deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
         item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,
@@ -379,9 +415,11 @@ class PV_RCNN(nn.Module):
         except `boxes_refined` (P_cls, P_reg for ProposalLoss; proposals, R_reg, R_cls, ...) and R_iou, R_match, G_conf, G_rreg,
         M_rcls, M_rreg for RefinementLoss."""
         item = self.proposal(item)
+        with torch.no_grad():
+            early = self._proposals_then_keypoints(item)
         features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
         with torch.no_grad():
-            boxes, scores, class_idx = self.stage1_proposals(item)
+            boxes, scores, class_idx = early or self.stage1_proposals(item)
         boxes = boxes.detach()
         pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
         deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
@@ -401,7 +439,7 @@ class PV_RCNN(nn.Module):
         nothing is waited for."""
         if not (self._native_item(item) and self.native_tail):
             raise RuntimeError("inference_begin: frames of the device Preprocessor in eval mode without autograd")
-        if "keypoints" not in item:
+        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc":
             self.prefetch_keypoints(item)
         st = self._native_cnn_launch(item, slot)
         item["_head_maps"] = self.proposal_layer.native_head(st["bev_map"])
@@ -421,8 +459,9 @@ class PV_RCNN(nn.Module):
         if ready is not None:
             main.wait_event(ready)
             item["keypoints"].record_stream(main)
+        early = self._proposals_then_keypoints(item)
         features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
-        boxes, scores, class_idx = self.stage1_proposals(item)
+        boxes, scores, class_idx = early or self.stage1_proposals(item)
         pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
         deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
         item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,

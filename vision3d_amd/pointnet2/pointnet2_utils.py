@@ -1,6 +1,23 @@
 """furthest_point_sample / gather_operation / ball_query / grouping_operation / QueryAndGroup
 (csrc/pointops.hip, csrc/sa_mlp.hip).  gather_operation and grouping_operation are differentiable in `features`
-(upstream pointnet2 implements both backward passes: a scatter-add of the output gradient)."""
+(upstream pointnet2 implements both backward passes: a scatter-add of the output gradient).
+
+sector_point_sample (csrc/keypoints.hip) has no upstream counterpart -- it is the sectorized proposal-centric sampling of PV-RCNN++
+-- so this is the repository's definition.  Per frame: points (N, C >= 3) float32 of which x, y, z are read, a target count K, a
+sector count S (1..64), optionally proposals (P <= 1024, 7) = (x, y, z, w, l, h, yaw) and a radius r_s.  All arithmetic is fp32
+without contraction, in exactly the written order.
+ 1. Candidates: the points whose x, y, z are all finite and, with proposals, that pass (dx*dx + dy*dy) + dz*dz < R_j*R_j for some
+    proposal j, d = p - centre_j, R_j = 0.5f * fmaxf(fmaxf(w, l), h) + r_s.  A frame whose filtered set is empty (P = 0 included)
+    uses all its finite points; one without finite points returns K zeros.
+ 2. Sector of a candidate: t = (atan2f(y, x) + 3.14159274f) * ((float)S * 0.159154937f), sector = min(S - 1, max(0, (int)t)).
+ 3. Quotas: n_k candidates in sector k, n = sum n_k.  n >= K: q_k = (K n_k) / n in 64-bit integers, and the K - sum q_k slots
+    left go one each to the sectors by decreasing (K n_k) mod n, the lower sector first among equals.  n < K: q_k = n_k.
+ 4. Per sector a farthest-point chain over its candidates in increasing original index: first pick = the lowest index, running
+    distances start at 1e10f, each step takes min(td, (dx*dx + dy*dy) + dz*dz) against the last pick, the next pick is the largest
+    running distance, the lowest original index among equals (the rules of furthest_point_sample); q_k picks.
+ 5. idx (K,) int32 into the frame's original order: the sectors in ascending order, each in pick order; when only n' < K slots
+    are filled, slot i >= n' repeats slot i mod n'.
+With S = 1 and no proposals this is furthest_point_sample on a cloud of finite points."""
 import torch
 from torch import nn
 
@@ -17,6 +34,32 @@ def furthest_point_sample(xyz, npoint):
         L.check(L.lib().v3d_furthest_point_sample(L.ptr(p), b, n, int(npoint), L.ptr(idx), 0, 0, L.stream_ptr()),
                 "furthest_point_sample")
     return idx
+
+
+def sector_point_sample(points, npoint, num_sectors, proposals=None, radius=1.6, return_counts=False):
+    """points (B, N, C >= 3) float32 -- contiguous, or a column view such as cloud[..., :3] of a contiguous (B, N, 4) cloud, read
+    through its row stride without a copy --, proposals (B, P, 7) float32 or None -> idx (B, npoint) int32 by the definition in the
+    module docstring [, counts (B, num_sectors) int32: candidates per sector]."""
+    L.require_gpu("sector_point_sample", points, proposals)
+    if points.dtype != torch.float32 or points.dim() != 3 or points.shape[2] < 3:
+        raise RuntimeError("sector_point_sample: points must be float32 (B, N, >= 3)")
+    b, n, _ = points.shape
+    if b * n > 0 and not (points.stride(2) == 1 and points.stride(1) >= 3 and (b == 1 or points.stride(0) == n * points.stride(1))):
+        points = points.contiguous()
+    stride = points.stride(1) if b * n > 0 and n > 1 else max(points.stride(1), 3)
+    p = 0
+    if proposals is not None:
+        if proposals.dtype != torch.float32 or proposals.dim() != 3 or proposals.shape[0] != b or proposals.shape[2] != 7:
+            raise RuntimeError("sector_point_sample: proposals must be float32 (B, P, 7)")
+        proposals, p = proposals.contiguous(), proposals.shape[1]
+    s = int(num_sectors)
+    idx = torch.empty((b, int(npoint)), dtype=torch.int32, device=points.device)
+    counts = torch.empty((b, s), dtype=torch.int32, device=points.device) if return_counts else None
+    ws = L.workspace(max(int(L.lib().v3d_keypoints_sector_workspace(b, n, s)), 16), points.device)
+    with L.device_guard(points.device):
+        L.check(L.lib().v3d_keypoints_sector(L.ptr(points), stride, b, n, int(npoint), s, L.ptr(proposals) if p else 0, p, float(radius),
+                                             L.ptr(idx), L.ptr(counts), L.ptr(ws), ws.numel(), L.stream_ptr()), "sector_point_sample")
+    return (idx, counts) if return_counts else idx
 
 
 def _scatter_add_backward(grad_out, idx_flat, n):

@@ -179,3 +179,41 @@ def make_gt_boxes(seed=0, n_extra=15):
     extra[:, 3:6] = np.asarray(CAR_WLH, np.float32) * rng.uniform(0.9, 1.1, (n_extra, 3))
     extra[:, 6] = rng.uniform(-np.pi, np.pi, n_extra)
     return np.concatenate([boxes, extra], 0).astype(np.float32)
+
+
+def make_keypoint_case(seed=0, batch=2, n_points=1500, n_sectors=6, n_proposals=5, counts=None, r_range=(5.0, 25.0), margin=1e-3):
+    """Inputs of the sectorized keypoint sampling (pointnet2_utils.sector_point_sample): -> points (batch, n_points, 4) f32,
+    proposals (batch, n_proposals, 7) f32.  Points are drawn in polar form -- a sector, a position inside it, a range from
+    `r_range`, z in [-2, 1) -- and shuffled; `counts` (n_sectors ints summing to n_points) fixes how many fall into each sector
+    (default: a random share each).  Every point's azimuth * n_sectors / 2 pi, evaluated in float64 on the float32 coordinates,
+    stays at least `margin` away from an integer (offenders are drawn again), so that two fp32 atan2 implementations agree on every
+    sector.  Proposals: car-sized boxes centred on points of the frame.  Deterministic in `seed`."""
+    rng = np.random.default_rng(90_000 + seed)
+    S = int(n_sectors)
+    points = np.zeros((batch, n_points, 4), np.float32)
+    proposals = np.zeros((batch, n_proposals, 7), np.float32)
+    for b in range(batch):
+        if counts is None:
+            sec = rng.choice(S, n_points, p=rng.dirichlet(np.full(S, 2.0)))
+        else:
+            assert len(counts) == S and sum(counts) == n_points
+            sec = np.repeat(np.arange(S), counts)
+        rng.shuffle(sec)
+        xyz = np.zeros((n_points, 3), np.float32)
+        todo = np.arange(n_points)
+        while len(todo):
+            t = sec[todo] + rng.uniform(0.02, 0.98, len(todo))
+            az = t / S * 2 * np.pi - np.pi
+            r = rng.uniform(r_range[0], r_range[1], len(todo))
+            xyz[todo] = np.stack([r * np.cos(az), r * np.sin(az), rng.uniform(-2.0, 1.0, len(todo))], 1).astype(np.float32)
+            got = (np.arctan2(xyz[todo, 1].astype(np.float64), xyz[todo, 0].astype(np.float64)) + np.pi) * (S / (2 * np.pi))
+            bad = (np.abs(got - np.round(got)) < 10 * margin) | (np.floor(got) != sec[todo])
+            todo = todo[bad]
+        points[b, :, :3] = xyz
+        points[b, :, 3] = rng.uniform(0.0, 1.0, n_points)
+        if n_proposals:
+            centre = xyz[rng.integers(0, n_points, n_proposals)] + rng.normal(0.0, 0.3, (n_proposals, 3))
+            proposals[b, :, :3] = centre
+            proposals[b, :, 3:6] = np.asarray(CAR_WLH) * rng.uniform(0.8, 1.25, (n_proposals, 3))
+            proposals[b, :, 6] = rng.uniform(-np.pi, np.pi, n_proposals)
+    return points, proposals
