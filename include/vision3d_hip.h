@@ -624,6 +624,33 @@ int v3d_refine_loss_fwd_bwd(const float* R_reg, int ld_reg, const float* R_cls, 
                             v3d_stream_t stream);
 int v3d_refine_loss_scale(float* dR_reg, float* dR_cls, int rows, const float* g_cls, const float* g_reg, v3d_stream_t stream);
 
+/* ---- Predicted Keypoint Weighting of PV-RCNN (arXiv 1912.13192 section 3.3; no upstream counterpart: model.py:72-74 hands every
+ * keypoint to RoI-grid pooling with weight 1).  The definition is this repository's (detector/keypoint_weighting.py,
+ * tests/keypoint_weighting_ref.py).  Replaces the last nn.Linear (H -> 1) of the head, the sigmoid and the broadcast multiply of
+ * KeypointWeighting.forward_torch by ONE launch, a wave per row:
+ *   logits[row] = hidden[row * ldh + 0..H) . w2 + b2[0]      (b2: device scalar, nullable = 0)
+ *   feats[row * ldf + 0..C) *= sigmoid(logits[row])          in place: a column block of the (B * K, C_total) point-major matrix
+ * H % 4 == 0, C % 4 == 0, ldh % 4 == 0, ldf % 4 == 0, hidden / w2 / feats 16-byte aligned (else V3D_EINVAL); any rows >= 0.
+ * Fixed summation order (bit-repeatable); no workspace, no host synchronisation. */
+int v3d_keypoint_weight(const float* hidden, int ldh, int H, const float* w2, const float* b2, float* feats, int ldf, int C,
+                        int rows, float* logits, v3d_stream_t stream);
+
+/* ---- KeypointSegLoss (the supervision of that head; this repository's definition) and its gradient in ONE launch of one
+ * workgroup; replaces KeypointSegLoss.forward_torch (per frame a points-in-boxes test against the boxes and the grown boxes + the
+ * focal loss of ops/focal_loss.py under autograd).  keypoints (B, K, 3) f32, logits (B, K) f32; the ground truth of all frames
+ * flat -- gt_boxes (n_gt, 7) f32, gt_class (n_gt) i64, entries < 0 are skipped --, frame b owning rows [gt_offsets[b],
+ * gt_offsets[b + 1]) (gt_offsets: (B + 1) i32 on the DEVICE, the convention of v3d_refine_targets; not read when n_gt == 0).
+ *   labels (B, K) u8   1: inside a box of the keypoint's frame -- the test of v3d_points_in_boxes with use_z = 1, bit for bit;
+ *                      255 (ignored): not 1, but inside a box whose (w, l, h) had extra_host[3] added in float32; else 0
+ *   losses[3]          {sum over labels != 255 of sigmoid_focal_loss(logit, label, alpha, gamma) / max(#1, 1), #1, #255}
+ *   d_logits (B, K)    gradient of losses[0]; _scale multiplies it with the upstream gradient (a device scalar)
+ * logits == NULL: labels (and, when given, the counts in losses) alone.  B * K <= 2^24.  Counts in int, the loss in double, both
+ * summed in a fixed order: bit-repeatable.  No _workspace query: the boxes are staged in LDS, 64 at a time, any number per frame. */
+int v3d_keypoint_seg_loss_fwd_bwd(const float* keypoints, const float* logits, int B, int K, const float* gt_boxes,
+                                  const int64_t* gt_class, const int32_t* gt_offsets, int n_gt, const float* extra_host, float alpha,
+                                  float gamma, uint8_t* labels, float* losses, float* d_logits, v3d_stream_t stream);
+int v3d_keypoint_seg_loss_scale(float* d_logits, int rows, const float* g, v3d_stream_t stream);
+
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.
  * Every layer must be conv + BatchNorm1d (training mode: batch statistics) [+ ReLU] with a power-of-two Cout in [4, 256].

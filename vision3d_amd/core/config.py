@@ -65,6 +65,10 @@ def _defaults():
         # keypoint sampler of PV-RCNN: "fps" (one farthest-point chain per cloud), "sector" (a chain per azimuth sector) or "spc"
         # (sectorized AND proposal-centric: only points within RADIUS of a stage-1 proposal) -- pointnet2_utils.sector_point_sample
         KEYPOINTS=dict(SAMPLER="fps", NUM_SECTORS=6, RADIUS=1.6),
+        # Predicted Keypoint Weighting of PV-RCNN (detector/keypoint_weighting.py), opt-in: a foreground head over the keypoint features
+        # (hidden widths MLPS) whose sigmoid scales every keypoint's row before RoI-grid pooling; supervised by a focal loss on
+        # "inside a ground-truth box", keypoints inside a box grown by GT_EXTRA_WIDTH (w, l, h) only are ignored
+        PKW=dict(ENABLED=False, MLPS=[256], GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], FOCAL_ALPHA=0.25, FOCAL_GAMMA=2.0, LOSS_WEIGHT=1.0),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",

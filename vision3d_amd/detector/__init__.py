@@ -9,6 +9,8 @@ _EXPORTS = {
     "ProposalLoss": "proposal",
     "ProposalLayer": "proposal",
     "RefinementLoss": "refinement",
+    "KeypointWeighting": "keypoint_weighting",
+    "KeypointSegLoss": "keypoint_weighting",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -21,7 +21,7 @@ from torch import nn
 
 from ..pointnet2 import pointnet2_utils as pn2
 from ..pointnet2.pointnet2_modules import PointnetSAModuleMSG
-from . import layers, proposal, refinement, roi_grid_pool, sparse_cnn
+from . import keypoint_weighting, layers, proposal, refinement, roi_grid_pool, sparse_cnn
 
 
 from ..runtime import PlanCache as _PlanCache  # (a dict a deep copy of the model starts empty: events, pinned words, device clones)
@@ -46,6 +46,9 @@ class PV_RCNN(nn.Module):
         self.bev = layers.BEVFeatureGatherer(cfg, self.cnn.voxel_offset, self.cnn.base_voxel_size)
         self.proposal_layer = proposal.ProposalLayer(cfg)
         self.refinement_layer = refinement.RefinementLayer(cfg)
+        if keypoint_weighting.pkw_config(cfg)["ENABLED"]:  # (the attribute, and with it its state_dict keys, exist only then)
+            c_total = sum(sum(p.out_channels()) for p in self.pnets) + cfg.PROPOSAL.C_IN  # (+ the BEV map the proposal head reads)
+            self.keypoint_weighting = keypoint_weighting.KeypointWeighting(cfg, c_total)
 
     def build_pointnets(self, cfg):
         """One multi-scale set-abstraction module per feature source (raw points, then the CNN levels)."""
@@ -94,7 +97,28 @@ class PV_RCNN(nn.Module):
         return pooled
 
     def point_feature_extract(self, item, cnn_features, bev_map):
-        """Keypoint features: set abstraction over every source concatenated with the BEV lookup (B, C_total, K)."""
+        """Keypoint features: set abstraction over every source concatenated with the BEV lookup (B, C_total, K); with cfg.PKW
+        enabled each keypoint's features multiplied with its predicted foreground score (the logits stay in item["K_cls"])."""
+        features = self._keypoint_features(item, cnn_features, bev_map)
+        if "keypoint_weighting" in self._modules:
+            features = self._weight_keypoints(item, features)
+        return features
+
+    def _weight_keypoints(self, item, features):
+        """Predicted Keypoint Weighting as the last step of the feature extraction: in place on the point-major matrix of the fused
+        extraction (one linear_rows launch + one of csrc/keypoint_weight.hip), else the torch statements."""
+        pkw = self.keypoint_weighting
+        pm = features.transpose(1, 2)
+        if not features.requires_grad and pkw.native_ok(pm):
+            item["K_cls"] = pkw.weight_point_major(pm)
+            return features  # (the same view, now weighted; it keeps its _v3d_keypoint_grid)
+        weighted, item["K_cls"] = pkw.forward_torch(features)
+        grid = getattr(features, "_v3d_keypoint_grid", None)
+        if grid is not None:
+            weighted._v3d_keypoint_grid = grid
+        return weighted
+
+    def _keypoint_features(self, item, cnn_features, bev_map):
         keypoints = item["keypoints"]
         xyz, reflectance = item["points"].split([3, 1], dim=-1)
         sources = [(xyz, reflectance), *cnn_features]
@@ -380,7 +404,8 @@ class PV_RCNN(nn.Module):
         return boxes.reshape(b, -1, head.DOF), scores.reshape(b, -1), class_idx
 
     def forward(self, item, samples=None, decode=True):
-        """Stage 1 + stage 2.  Adds to `item`: keypoints, P_cls, P_reg, keypoint_features (B, 512, K), proposals (B, n, 7),
+        """Stage 1 + stage 2.  Adds to `item`: keypoints, P_cls, P_reg, keypoint_features (B, 512, K) [cfg.PKW: weighted with the
+        sigmoid of K_cls (B, K), which is added too], proposals (B, n, 7),
         proposal_scores (B, n), proposal_class (n,), pooled_features (B, n, 256), R_reg (B, n, 7), R_cls (B, n, 1) and
         boxes_refined (B, n, 7) [decode=False: left to the caller -- `inference` gets them from the native tail].  `samples`
         (B, n, NUM_GRIDPOINTS, 3) in [0, 1) fixes the RoI grid points (the reference draws them with an unseeded torch.rand,
@@ -413,7 +438,8 @@ class PV_RCNN(nn.Module):
         the backbone and the set-abstraction modules learn from both), stage-2 targets are assigned against the item's per-frame
         `boxes` / `class_idx` lists (draws: `refine_draws`, else the assigner's generator).  Leaves in `item`: what `forward` leaves
         except `boxes_refined` (P_cls, P_reg for ProposalLoss; proposals, R_reg, R_cls, ...) and R_iou, R_match, G_conf, G_rreg,
-        M_rcls, M_rreg for RefinementLoss."""
+        M_rcls, M_rreg for RefinementLoss; with cfg.PKW enabled also K_cls (B, K) and K_label (B, K) for KeypointSegLoss, which the
+        caller adds to ProposalLoss + RefinementLoss."""
         item = self.proposal(item)
         with torch.no_grad():
             early = self._proposals_then_keypoints(item)
@@ -425,6 +451,9 @@ class PV_RCNN(nn.Module):
         deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
         item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,
                     pooled_features=pooled, R_reg=deltas, R_cls=conf)
+        if "K_cls" in item and "boxes" in item and "class_idx" in item:  # cfg.PKW: the keypoint labels KeypointSegLoss trains K_cls on
+            item["K_label"] = keypoint_weighting.keypoint_labels(item["keypoints"], item["boxes"], item["class_idx"],
+                                                                 keypoint_weighting.pkw_config(self.cfg)["GT_EXTRA_WIDTH"])
         return self.refinement_targets()(item)
 
     # ---- two frames in flight from ONE host thread (round 6).  `inference` enqueues stage 1, WAITS for its row counts (the level views
