@@ -6,8 +6,8 @@
 // here it is hand-written, bf16 storage / fp32 accumulation -- the arithmetic of that autocast path (bf16 pack / unpack and the
 // hi / lo split of the fp32-class planes: split_prec.h):
 //
-//   dt_conv_kernel        implicit-GEMM convolution, NHWC bf16 -> NHWC bf16 (the raw, pre-BatchNorm output) + per-tile channel
-//                         sums for the batch statistics.  The SAME kernel on a transposed / tap-flipped weight image is the
+//   dt_conv3_kernel,      implicit-GEMM convolution (3x3 | 1x1), NHWC bf16 -> NHWC bf16 (the raw, pre-BatchNorm output) + per-workgroup
+//   dt_conv_kernel        channel sums for the batch statistics.  The SAME kernel on a transposed / tap-flipped weight image is the
 //                         data gradient.
 //   dt_bn_*               batch statistics (fixed-order reduction of the per-tile sums, running statistics), normalise + ReLU,
 //                         and the backward pair (channel sums of dy and dy * x_hat, then the input gradient).
@@ -18,6 +18,10 @@
 //
 // Every reduction (batch statistics, dgamma / dbeta, dW, head gradients) is two-level in a fixed order: results are
 // bit-repeatable, no atomics.
+//
+// The step runs in two arithmetics -- bf16 storage, and the fp32-class split storage ("bf16x3": every tensor a hi + lo pair of bf16
+// planes, DtT) -- through ONE pair of drivers at the end of this file (dt_forward / dt_backward, "one call per direction"): the
+// element-wise and reduction kernels serve both (a nullable lo plane), the few steps that differ are the dt_step_* helpers.
 #include "v3d_internal.h"
 #include "split_prec.h"
 
@@ -48,6 +52,13 @@ __device__ __forceinline__ void dt_store8(dt_bf16* __restrict__ hi, dt_bf16* __r
   *reinterpret_cast<u32x4*>(hi + off) = h;
   if (lo) *reinterpret_cast<u32x4*>(lo + off) = l;
 }
+// the host side's handle of such a tensor (NHWC bf16 planes); lo == nullptr: bf16 storage
+struct DtT {
+  unsigned char* hi;
+  unsigned char* lo;
+};
+static inline DtT dt_t(const void* hi, const void* lo = nullptr) { return DtT{(unsigned char*)hi, (unsigned char*)lo}; }
+#define DT_TRY(call) do { const int rc_ = (call); if (rc_ != V3D_OK) return rc_; } while (0)
 
 #define DT_C 128          // channels of every RPN convolution (Cin = Cout)
 #define DT_BM 128         // pixels per tile
@@ -66,19 +77,20 @@ __device__ __forceinline__ unsigned lds_addr_dt(const void* p) { return (unsigne
 // (Cout, Cin, k, k) fp32 -> bf16 fragment image img[tap][ss = ci/32][nt = co/16][lane][8]: lane (j = lane & 15, kg = lane >> 4)
 // holds B[k = ss*32 + kg*8 + e][n = nt*16 + j].  transpose = 0: B[ci][co] = W[co][ci][tap] (forward).  transpose = 1: the data
 // gradient as a convolution of dY: B[k = co][n = ci] = W[co][ci][taps - 1 - tap] (taps flipped, channels swapped).
+__device__ __forceinline__ float dt_pack_value(const float* __restrict__ w, int taps, int transpose, int t) {  // element t of the image
+  int r = t;
+  const int e = r % 8; r /= 8;
+  const int lane = r % 64; r /= 64;
+  const int nt = r % 8; r /= 8;
+  const int ss = r % 4; r /= 4;
+  const int tap = r;
+  const int k = ss * 32 + (lane >> 4) * 8 + e, n = nt * 16 + (lane & 15);
+  return transpose ? w[((size_t)k * DT_C + n) * taps + (taps - 1 - tap)] : w[((size_t)n * DT_C + k) * taps + tap];
+}
 __global__ void dt_pack_weights_kernel(const float* __restrict__ w, int taps, int transpose, dt_bf16* __restrict__ img) {
   const int total = taps * 4 * 8 * 64 * 8;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    int r = t;
-    const int e = r % 8; r /= 8;
-    const int lane = r % 64; r /= 64;
-    const int nt = r % 8; r /= 8;
-    const int ss = r % 4; r /= 4;
-    const int tap = r;
-    const int k = ss * 32 + (lane >> 4) * 8 + e, n = nt * 16 + (lane & 15);
-    const float v = transpose ? w[((size_t)k * DT_C + n) * taps + (taps - 1 - tap)] : w[((size_t)n * DT_C + k) * taps + tap];
-    img[t] = bf16_from_f32(v);
-  }
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x)
+    img[t] = bf16_from_f32(dt_pack_value(w, taps, transpose, t));
 }
 
 extern "C" size_t v3d_dense_train_weight_image_bytes(int ksize) { return (size_t)ksize * ksize * DT_B_BYTES; }
@@ -94,17 +106,8 @@ __global__ void dt_pack_all_kernel(DtPackJobs jobs, unsigned char* __restrict__ 
   const float* __restrict__ w = jobs.w[l];
   dt_bf16* __restrict__ img = reinterpret_cast<dt_bf16*>(images + (size_t)blockIdx.y * stride);
   const int total = taps * 4 * 8 * 64 * 8;
-  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) {
-    int r = t;
-    const int e = r % 8; r /= 8;
-    const int lane = r % 64; r /= 64;
-    const int nt = r % 8; r /= 8;
-    const int ss = r % 4; r /= 4;
-    const int tap = r;
-    const int k = ss * 32 + (lane >> 4) * 8 + e, n = nt * 16 + (lane & 15);
-    const float v = transpose ? w[((size_t)k * DT_C + n) * taps + (taps - 1 - tap)] : w[((size_t)n * DT_C + k) * taps + tap];
-    img[t] = bf16_from_f32(v);
-  }
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x)
+    img[t] = bf16_from_f32(dt_pack_value(w, taps, transpose, t));
 }
 
 extern "C" int v3d_dense_train_pack_weights(const float* weight, int ksize, int transpose, void* image, v3d_stream_t stream) {
@@ -116,8 +119,9 @@ extern "C" int v3d_dense_train_pack_weights(const float* weight, int ksize, int 
 }
 
 // ------------------------------------------------------------------------------------------------ convolution
-// (The general form, templated on the kernel size; since the 2-D tile kernel below took over the 3x3 layers only KS = 1 is
-// instantiated -- the RPN's 1x1 layer and its data gradient.)
+// The general form, templated on the kernel size.  Only KS = 1 is instantiated -- the RPN's 1x1 layer and its data gradient; the 3x3
+// layers are the 2-D tile kernel's, below.  (The parameter stays: written out for one tap, the loaders compile to other code --
+// the compiler does not fold the tap index of a stage, (G % 2) >> 1, to zero -- and a rewrite of this kernel wants a measurement.)
 // Tile = 128 pixels x 128 couts; stage = 64 input channels of one tap (A: 128 pixel rows x 128 B = 16 KB, B: 2 k-substeps x 8 cout
 // tiles x 1 KB = 16 KB); the stages of ALL tiles of a (persistent) workgroup stream through a ring of 4 LDS slots.
 // Waves 4-7 LOAD, three stages ahead (LDS-DMA, hand-counted vmcnt, raw barriers): 8 consecutive lanes fetch the 128 bytes of one
@@ -729,14 +733,19 @@ __global__ __launch_bounds__(256) void dt_bn_relu_apply_kernel(const dt_bf16* __
   }
 }
 
-extern "C" int v3d_dense_train_bn_relu_apply(const void* x, long long M, const float* mean, const float* invstd, const float* gamma,
-                                             const float* beta, int relu, void* y, v3d_stream_t stream) {
-  if (!x || !y || M < 1 || !mean || !invstd || !gamma || !beta) return V3D_EINVAL;
+static int dt_bn_relu_apply(DtT x, long long M, const float* mean, const float* invstd, const float* gamma, const float* beta, int relu, DtT y,
+                            v3d_stream_t stream) {
+  if (!x.hi || !y.hi || M < 1 || !mean || !invstd || !gamma || !beta) return V3D_EINVAL;
   const long long blocks = (M + 15) / 16;
   hipLaunchKernelGGL(dt_bn_relu_apply_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream,
-                     (const dt_bf16*)x, (const dt_bf16*)nullptr, M, mean, invstd, gamma, beta, relu, (dt_bf16*)y, (dt_bf16*)nullptr);
+                     (const dt_bf16*)x.hi, (const dt_bf16*)x.lo, M, mean, invstd, gamma, beta, relu, (dt_bf16*)y.hi, (dt_bf16*)y.lo);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
+}
+
+extern "C" int v3d_dense_train_bn_relu_apply(const void* x, long long M, const float* mean, const float* invstd, const float* gamma,
+                                             const float* beta, int relu, void* y, v3d_stream_t stream) {
+  return dt_bn_relu_apply(dt_t(x), M, mean, invstd, gamma, beta, relu, dt_t(y), stream);
 }
 
 // Backward of y = relu(x_hat * gamma + beta), x_hat = (x - mean) * invstd, batch statistics:
@@ -744,12 +753,28 @@ extern "C" int v3d_dense_train_bn_relu_apply(const void* x, long long M, const f
 // Pass 1 (this kernel): per-block partial (sum g, sum g * x_hat) per channel, blocks in a fixed grid, thread = 8 channels of a pixel,
 // the 16 pixel rows of a block reduced through LDS in row order.
 #define DT_RED_BLOCKS 512
+// tail of a 256-thread block whose thread (c8, rg) holds two sums for channels 8 c8 .. 8 c8 + 7 over the pixel rows of row group rg:
+// the 16 row groups are added through LDS in row-group order -> partial[block][2][128]
+__device__ __forceinline__ void dt_rowgroup_sums(const float (&s1)[8], const float (&s2)[8], float* __restrict__ partial) {
+  __shared__ float red[16][2][DT_C];
+  const int c8 = threadIdx.x & 15, rg = threadIdx.x >> 4;
+#pragma unroll
+  for (int e = 0; e < 8; e++) {
+    red[rg][0][c8 * 8 + e] = s1[e];
+    red[rg][1][c8 * 8 + e] = s2[e];
+  }
+  __syncthreads();
+  const int which = threadIdx.x / DT_C, c = threadIdx.x % DT_C;
+  float a = 0.f;
+  for (int g = 0; g < 16; g++) a += red[g][which][c];
+  partial[((size_t)blockIdx.x * 2 + which) * DT_C + c] = a;
+}
+
 __global__ __launch_bounds__(256) void dt_bn_bwd_reduce_kernel(const dt_bf16* __restrict__ x, const dt_bf16* __restrict__ x_lo,
                                                                const dt_bf16* __restrict__ dy, const dt_bf16* __restrict__ dy_lo, long long M,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                int relu, float* __restrict__ partial /*[blocks][2][128]*/) {
-  __shared__ float red[16][2][DT_C];
   const int c8 = threadIdx.x & 15, rg = threadIdx.x >> 4;
   float mu[8], is[8], ga[8], be[8], s1[8], s2[8];
 #pragma unroll
@@ -770,16 +795,7 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_reduce_kernel(const dt_bf16* __
       s2[e] = fmaf(g, xh, s2[e]);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
-    red[rg][0][c8 * 8 + e] = s1[e];
-    red[rg][1][c8 * 8 + e] = s2[e];
-  }
-  __syncthreads();
-  const int which = threadIdx.x / DT_C, c = threadIdx.x % DT_C;
-  float a = 0.f;
-  for (int g = 0; g < 16; g++) a += red[g][which][c];
-  partial[((size_t)blockIdx.x * 2 + which) * DT_C + c] = a;
+  dt_rowgroup_sums(s1, s2, partial);
 }
 
 // blocks partials (blocks, 2, 128) -> dbeta, dgamma: 8 workgroups x 32 columns of the (blocks, 256) matrix
@@ -857,7 +873,6 @@ extern "C" int v3d_dense_train_bn_relu_bwd(const void* x, const void* dy, long l
 // (the bf16-storage path gets them from the convolution's epilogue; the split path's convolutions are csrc/dense_conv.hip's).
 __global__ __launch_bounds__(256) void dt_bn_stats_kernel(const dt_bf16* __restrict__ x, const dt_bf16* __restrict__ x_lo, long long M,
                                                           float* __restrict__ partial /*[blocks][2][128]*/) {
-  __shared__ float red[16][2][DT_C];
   const int c8 = threadIdx.x & 15, rg = threadIdx.x >> 4;
   float s1[8], s2[8];
 #pragma unroll
@@ -871,16 +886,7 @@ __global__ __launch_bounds__(256) void dt_bn_stats_kernel(const dt_bf16* __restr
       s2[e] = fmaf(xv[e], xv[e], s2[e]);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; e++) {
-    red[rg][0][c8 * 8 + e] = s1[e];
-    red[rg][1][c8 * 8 + e] = s2[e];
-  }
-  __syncthreads();
-  const int which = threadIdx.x / DT_C, c = threadIdx.x % DT_C;
-  float a = 0.f;
-  for (int g = 0; g < 16; g++) a += red[g][which][c];
-  partial[((size_t)blockIdx.x * 2 + which) * DT_C + c] = a;
+  dt_rowgroup_sums(s1, s2, partial);
 }
 
 #define DT_WG_SLABS 64
@@ -1028,17 +1034,26 @@ __global__ __launch_bounds__(768) void dt_wgrad_kernel(const dt_bf16* __restrict
 }
 
 // partial (slabs, taps, ci, co) -> dW (co, ci, taps) fp32.  One workgroup per (input channel, group of <= 3 taps): thread (co, g) sums
-// slabs 8 g .. 8 g + 7 in slab order (coalesced 512-byte rows), the eight group sums are combined in a fixed tree.  Bit-repeatable.
+// its slabs in slab order (coalesced 512-byte rows), the eight group sums are combined in a fixed tree.  Bit-repeatable.
+// Which slabs are group g's is the only difference between the two arithmetics, and it decides the result's bits:
+//   INTERLEAVED = false  8 g .. 8 g + 7       (bf16 storage: at most DT_WG_SLABS = 64 partials)
+//   INTERLEAVED = true   g, g + 8, g + 16 ... (split storage: the partials of three terms, any number)
+template <bool INTERLEAVED>
 __global__ __launch_bounds__(1024) void dt_wgrad_reduce_kernel(const float* __restrict__ partial, int slabs, int taps, float* __restrict__ dw) {
   __shared__ float grp[8][3][DT_C];
   const int ci = blockIdx.x, a0 = blockIdx.y * 3, na = taps - a0 < 3 ? taps - a0 : 3;
   const int co = threadIdx.x & (DT_C - 1), g = threadIdx.x >> 7;
   const size_t total = (size_t)taps * DT_C * DT_C;
   for (int a = 0; a < na; a++) {
+    const size_t at = ((size_t)(a0 + a) * DT_C + ci) * DT_C + co;
     float v = 0.f;
+    if constexpr (INTERLEAVED) {
+      for (int s = g; s < slabs; s += 8) v += partial[(size_t)s * total + at];
+    } else {
 #pragma unroll
-    for (int s = 0; s < 8; s++)
-      if (8 * g + s < slabs) v += partial[(size_t)(8 * g + s) * total + ((size_t)(a0 + a) * DT_C + ci) * DT_C + co];
+      for (int s = 0; s < 8; s++)
+        if (8 * g + s < slabs) v += partial[(size_t)(8 * g + s) * total + at];
+    }
     grp[g][a][co] = v;
   }
   __syncthreads();
@@ -1051,15 +1066,8 @@ __global__ __launch_bounds__(1024) void dt_wgrad_reduce_kernel(const float* __re
 
 extern "C" size_t v3d_dense_train_wgrad_workspace(int ksize) { return (size_t)DT_WG_SLABS * ksize * ksize * DT_C * DT_C * sizeof(float); }
 
-// x: bf16 NHWC input of the layer, dy: bf16 NHWC gradient of its raw output -> dw (128, 128, k, k) fp32.  No planar operands.
-extern "C" int v3d_dense_train_wgrad(const void* x, const void* dy, int B, int H, int W, int ksize, float* dw, void* workspace,
-                                          size_t workspace_bytes, v3d_stream_t stream) {
-  if (!x || !dy || !dw || !workspace || B < 1 || H < 1 || W < 1 || (ksize != 1 && ksize != 3)) return V3D_EINVAL;
-  if (workspace_bytes < v3d_dense_train_wgrad_workspace(ksize)) return V3D_EWORKSPACE;
-  const long long tiles = (long long)B * ((H + DT3_TH - 1) / DT3_TH) * ((W + DT3_TW - 1) / DT3_TW);
-  const int slabs = (int)(tiles < DT_WG_SLABS ? tiles : DT_WG_SLABS);
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace;
+// one product term: the slab partials of x (*) dy
+static int dt_wgrad_launch(int ksize, const void* x, const void* dy, int B, int H, int W, int slabs, float* partial, hipStream_t st) {
   static V3dPerDeviceFlag attr9, attr1;
   V3D_CHECK_HIP(v3d_set_max_lds(attr9, (const void*)dt_wgrad_kernel<9>, DT_W2_SMEM));
   V3D_CHECK_HIP(v3d_set_max_lds(attr1, (const void*)dt_wgrad_kernel<1>, DT_W2_SMEM));
@@ -1067,9 +1075,37 @@ extern "C" int v3d_dense_train_wgrad(const void* x, const void* dy, int B, int H
     hipLaunchKernelGGL(dt_wgrad_kernel<9>, dim3(4 * slabs), dim3(768), DT_W2_SMEM, st, (const dt_bf16*)x, (const dt_bf16*)dy, B, H, W, slabs, partial);
   else
     hipLaunchKernelGGL(dt_wgrad_kernel<1>, dim3(4 * slabs), dim3(768), DT_W2_SMEM, st, (const dt_bf16*)x, (const dt_bf16*)dy, B, H, W, slabs, partial);
-  hipLaunchKernelGGL(dt_wgrad_reduce_kernel, dim3(DT_C, (ksize * ksize + 2) / 3), dim3(1024), 0, st, partial, slabs, ksize * ksize, dw);
+  return V3D_OK;
+}
+
+// bf16 storage: one term.  Split storage: (x_hi, dy_hi), (x_hi, dy_lo), (x_lo, dy_hi) into three sets of slab partials, summed by one
+// fixed-order reduction.  workspace: v3d_dense_train_wgrad_workspace per term.
+static int dt_wgrad(DtT x, DtT dy, int B, int H, int W, int ksize, float* dw, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
+  const bool split = x.lo != nullptr;
+  if (workspace_bytes < (split ? 3 : 1) * v3d_dense_train_wgrad_workspace(ksize)) return V3D_EWORKSPACE;
+  const long long tiles = (long long)B * ((H + DT3_TH - 1) / DT3_TH) * ((W + DT3_TW - 1) / DT3_TW);
+  const int slabs = (int)(tiles < DT_WG_SLABS ? tiles : DT_WG_SLABS), taps = ksize * ksize;
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = (float*)workspace;
+  const size_t term = (size_t)slabs * taps * DT_C * DT_C;
+  const dim3 grid(DT_C, (taps + 2) / 3);
+  DT_TRY(dt_wgrad_launch(ksize, x.hi, dy.hi, B, H, W, slabs, partial, st));
+  if (split) {
+    DT_TRY(dt_wgrad_launch(ksize, x.hi, dy.lo, B, H, W, slabs, partial + term, st));
+    DT_TRY(dt_wgrad_launch(ksize, x.lo, dy.hi, B, H, W, slabs, partial + 2 * term, st));
+    hipLaunchKernelGGL(dt_wgrad_reduce_kernel<true>, grid, dim3(1024), 0, st, partial, 3 * slabs, taps, dw);
+  } else {
+    hipLaunchKernelGGL(dt_wgrad_reduce_kernel<false>, grid, dim3(1024), 0, st, partial, slabs, taps, dw);
+  }
   V3D_CHECK_LAUNCH();
   return V3D_OK;
+}
+
+// x: bf16 NHWC input of the layer, dy: bf16 NHWC gradient of its raw output -> dw (128, 128, k, k) fp32.  No planar operands.
+extern "C" int v3d_dense_train_wgrad(const void* x, const void* dy, int B, int H, int W, int ksize, float* dw, void* workspace,
+                                          size_t workspace_bytes, v3d_stream_t stream) {
+  if (!x || !dy || !dw || !workspace || B < 1 || H < 1 || W < 1 || (ksize != 1 && ksize != 3)) return V3D_EINVAL;
+  return dt_wgrad(dt_t(x), dt_t(dy), B, H, W, ksize, dw, workspace, workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ 1x1 head (<= 64 outputs, bias)
@@ -1199,12 +1235,6 @@ extern "C" int v3d_dense_train_head_fwd(const void* feat, int B, int H, int W, c
 
 // dmaps fp32 (B, O, H, W) -> dfeat bf16 NHWC, dweight (O, 128), dbias (O)
 static int dt_head_bwd(const void* feat, const void* feat_lo, const float* dmaps, int B, int H, int W, const float* weight, int O, void* dfeat,
-                       void* dfeat_lo, float* dweight, float* dbias, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
-extern "C" int v3d_dense_train_head_bwd(const void* feat, const float* dmaps, int B, int H, int W, const float* weight, int O, void* dfeat,
-                                        float* dweight, float* dbias, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
-  return dt_head_bwd(feat, nullptr, dmaps, B, H, W, weight, O, dfeat, nullptr, dweight, dbias, workspace, workspace_bytes, stream);
-}
-static int dt_head_bwd(const void* feat, const void* feat_lo, const float* dmaps, int B, int H, int W, const float* weight, int O, void* dfeat,
                        void* dfeat_lo, float* dweight, float* dbias, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
   if (!feat || !dmaps || !weight || !dfeat || !dweight || !dbias || !workspace || B < 1 || H < 1 || W < 1 || O < 1 || O > DT_HEAD_MAX)
     return V3D_EINVAL;
@@ -1227,30 +1257,62 @@ static int dt_head_bwd(const void* feat, const void* feat_lo, const float* dmaps
   return V3D_OK;
 }
 
+extern "C" int v3d_dense_train_head_bwd(const void* feat, const float* dmaps, int B, int H, int W, const float* weight, int O, void* dfeat,
+                                        float* dweight, float* dbias, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
+  return dt_head_bwd(feat, nullptr, dmaps, B, H, W, weight, O, dfeat, nullptr, dweight, dbias, workspace, workspace_bytes, stream);
+}
+
 // ------------------------------------------------------------------------------------------------ one call per direction
 // The whole dense half of a train step enqueued by ONE native call each way (the host side of ~120 kernel launches: as for the
 // sparse training plan, a Python-level operator chain would leave the step host-bound).  The caller owns the arena (a plain
-// device buffer of v3d_dense_train_arena_bytes, zero-filled once by v3d_dense_train_arena_init) -- it carries what the backward
-// needs from the forward: every layer's raw convolution output and post-ReLU activation, the batch statistics.
+// device buffer of v3d_dense_train_arena_bytes[_split]; nothing in it is read before it is written) -- it carries what the backward
+// needs from the forward: every layer's raw convolution output and post-ReLU activation, the batch statistics, the weight images.
+//
+// ONE driver (dt_forward, dt_backward) runs the step in both arithmetics; `split` picks the primitive of a step (dt_step_*, dt_wgrad):
+//   bf16 storage                              the kernels of this file; one plane per tensor
+//   split ("bf16x3", the fp32-class step of   every tensor a pair of planes (16 significant bits), every product three MFMA terms
+//   the reference's train.py:58-66)           (hi*hi + hi*lo + lo*hi, fp32 accumulation: 2^-17 per product, scale-free):
+//     convolutions, forward and data gradient   csrc/dense_conv.hip's bf16x3 kernels (the inference RPN's), raw output, no epilogue;
+//                                               the data gradient is the same convolution on the channel-swapped, tap-flipped weights
+//     weight gradient                           dt_wgrad_kernel three times into three sets of slab partials, one reduction
+//     batch statistics, BN + ReLU, their        the kernels above on hi + lo (fp32 arithmetic; statistics from the stored values:
+//     backward, the head's gradients            dt_bn_stats_kernel; fixed-order two-level reductions as before)
+//     head forward                              dense_conv.hip's 1x1 stream kernel (bias, fp32 NCHW maps)
+//   About 2.4x the traffic and 3x the matrix work of the bf16-storage step; no tensor of it ever exists in reduced precision.
 struct DtArena {
-  size_t act_bytes;
-  size_t off_raw, off_act, off_stat, off_partial, off_img, off_g0, off_g1, off_ws, total;
-  int tiles;
+  bool split;
+  int B, H, W, stat_rows;  // stat_rows: rows of the statistics partials (bf16: workgroups of the convolution; split: of dt_bn_stats_kernel)
+  long long M;
+  size_t plane, slot, img;  // bytes of one bf16 plane of a tensor, of a tensor (1 or 2 planes), of a weight image
+  size_t off_raw, off_act, off_stat, off_partial, off_img, off_himg, off_wt, off_g0, off_g1, off_ws, total;  // himg, wt: split only
+  unsigned char* base;
+  DtT at(size_t off, int l = 0) const {
+    unsigned char* p = base + off + (size_t)l * slot;
+    return DtT{p, split ? p + plane : nullptr};
+  }
+  void* image(int i) const { return base + off_img + (size_t)i * img; }  // 2 l: layer l forward, 2 l + 1: its data gradient
 };
-static DtArena dt_arena_layout(int B, int H, int W, int n_layers, int O) {
+static DtArena dt_arena_layout(int B, int H, int W, int n_layers, int O, bool split, void* arena = nullptr) {
   DtArena a;
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  a.tiles = v3d_dense_train_conv_tiles(B, H, W);
-  a.act_bytes = up((size_t)B * H * W * DT_C * 2);
+  a.split = split; a.B = B; a.H = H; a.W = W; a.base = (unsigned char*)arena;
+  a.M = (long long)B * H * W;
+  const long long want = (a.M + 15) / 16;
+  a.stat_rows = split ? (int)(want < DT_RED_BLOCKS ? want : DT_RED_BLOCKS) : v3d_dense_train_conv_tiles(B, H, W);
+  a.plane = up((size_t)B * H * W * DT_C * 2);
+  a.slot = (split ? 2 : 1) * a.plane;
+  a.img = up(split ? v3d_conv2d_weight_image_bytes(DT_C, DT_C, 3) : (size_t)9 * DT_B_BYTES);
   size_t o = 0;
-  a.off_raw = o; o += (size_t)n_layers * a.act_bytes;
-  a.off_act = o; o += (size_t)n_layers * a.act_bytes;
+  a.off_raw = o; o += (size_t)n_layers * a.slot;
+  a.off_act = o; o += (size_t)n_layers * a.slot;
   a.off_stat = o; o += up((size_t)n_layers * 2 * DT_C * 4);
-  a.off_partial = o; o += up((size_t)a.tiles * 2 * DT_C * 4);
-  a.off_img = o; o += (size_t)n_layers * 2 * up(9 * DT_B_BYTES);
-  a.off_g0 = o; o += a.act_bytes;
-  a.off_g1 = o; o += a.act_bytes;
-  size_t ws = v3d_dense_train_wgrad_workspace(3);
+  a.off_partial = o; o += up((size_t)(split ? DT_RED_BLOCKS : a.stat_rows) * 2 * DT_C * 4);
+  a.off_img = o; o += (size_t)n_layers * 2 * a.img;
+  a.off_himg = o; o += split ? up(v3d_conv2d_weight_image_bytes(DT_C, O, 1)) : 0;  // the head's image
+  a.off_wt = o; o += split ? up((size_t)9 * DT_C * DT_C * 4) : 0;                  // a layer's flipped fp32 weights
+  a.off_g0 = o; o += a.slot;
+  a.off_g1 = o; o += a.slot;
+  size_t ws = (split ? 3 : 1) * v3d_dense_train_wgrad_workspace(3);
   if (v3d_dense_train_head_workspace(O) > ws) ws = v3d_dense_train_head_workspace(O);
   if (v3d_dense_train_bn_bwd_workspace() > ws) ws = v3d_dense_train_bn_bwd_workspace();
   a.off_ws = o; o += up(ws);
@@ -1259,53 +1321,114 @@ static DtArena dt_arena_layout(int B, int H, int W, int n_layers, int O) {
 }
 
 extern "C" size_t v3d_dense_train_arena_bytes(int B, int H, int W, int n_layers, int O) {
-  if (B < 1 || H < 1 || W < 1 || n_layers < 1 || O < 1) return 0;
-  return dt_arena_layout(B, H, W, n_layers, O).total;
+  return B < 1 || H < 1 || W < 1 || n_layers < 1 || O < 1 ? 0 : dt_arena_layout(B, H, W, n_layers, O, false).total;
+}
+extern "C" size_t v3d_dense_train_arena_bytes_split(int B, int H, int W, int n_layers, int O) {
+  return B < 1 || H < 1 || W < 1 || n_layers < 1 || O < 1 ? 0 : dt_arena_layout(B, H, W, n_layers, O, true).total;
 }
 
-extern "C" int v3d_dense_train_arena_init(void* arena, int B, int H, int W, int n_layers, int O, v3d_stream_t stream) {
-  if (!arena) return V3D_EINVAL;
-  const DtArena a = dt_arena_layout(B, H, W, n_layers, O);
-  (void)a; (void)stream;  // nothing in the arena is read before it is written (kept: the caller's allocation protocol)
+// (kept for the C ABI: nothing in the arena is read before it is written)
+extern "C" int v3d_dense_train_arena_init(void* arena, int, int, int, int, int, v3d_stream_t) { return arena ? V3D_OK : V3D_EINVAL; }
+
+// wt[ci][co][t] = w[co][ci][taps - 1 - t]: the data gradient's weights of the split path, before dense_conv.hip packs them
+__global__ __launch_bounds__(256) void dt_wt_flip_kernel(const float* __restrict__ w, int taps, float* __restrict__ wt) {
+  const int total = DT_C * DT_C * taps;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int t = i % taps, co = (i / taps) % DT_C, ci = i / (taps * DT_C);
+    wt[i] = w[((size_t)co * DT_C + ci) * taps + (taps - 1 - t)];
+  }
+}
+
+// the step's weight images (read again by the backward call: the weights do not change between the two calls of a step)
+static int dt_step_pack(const DtArena& a, const v3d_dense_train_layer* layers, int n_layers, const float* head_weight, int O, v3d_stream_t stream) {
+  if (!a.split) {
+    DtPackJobs jobs;
+    for (int l = 0; l < n_layers; l++) {
+      jobs.w[l] = layers[l].weight;
+      jobs.taps[l] = layers[l].ksize * layers[l].ksize;
+    }
+    hipLaunchKernelGGL(dt_pack_all_kernel, dim3(32, 2 * n_layers), dim3(256), 0, (hipStream_t)stream, jobs, a.base + a.off_img, a.img);
+    return V3D_OK;
+  }
+  float* wt = (float*)(a.base + a.off_wt);
+  for (int l = 0; l < n_layers; l++) {
+    const v3d_dense_train_layer& L = layers[l];
+    DT_TRY(v3d_conv2d_pack_weights(L.weight, nullptr, DT_C, DT_C, L.ksize, V3D_PREC_BF16X3, a.image(2 * l), stream));
+    hipLaunchKernelGGL(dt_wt_flip_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream, L.weight, L.ksize * L.ksize, wt);
+    DT_TRY(v3d_conv2d_pack_weights(wt, nullptr, DT_C, DT_C, L.ksize, V3D_PREC_BF16X3, a.image(2 * l + 1), stream));
+  }
+  return v3d_conv2d_pack_weights(head_weight, nullptr, O, DT_C, 1, V3D_PREC_BF16X3, a.base + a.off_himg, stream);
+}
+
+// y = the raw convolution of x (no bias, no activation) -- a forward layer, or the data gradient on image 2 l + 1.
+// partial (forward only): the batch-statistics partials of y, a.stat_rows rows.
+static int dt_step_conv(const DtArena& a, DtT x, const void* image, int ksize, DtT y, float* partial, v3d_stream_t stream) {
+  if (!a.split) return v3d_dense_train_conv(x.hi, image, a.B, a.H, a.W, ksize, y.hi, partial, stream);
+  DT_TRY(dt_conv2d_plain(x.hi, x.lo, image, nullptr, 0, a.B, a.H, a.W, DT_C, DT_C, ksize, y.hi, y.lo, nullptr, stream));
+  if (partial)
+    hipLaunchKernelGGL(dt_bn_stats_kernel, dim3(a.stat_rows), dim3(256), 0, (hipStream_t)stream, (const dt_bf16*)y.hi, (const dt_bf16*)y.lo, a.M,
+                       partial);
   return V3D_OK;
 }
 
-#define DT_TRY(call) do { const int rc_ = (call); if (rc_ != V3D_OK) return rc_; } while (0)
+static int dt_step_head_fwd(const DtArena& a, DtT x, const float* weight, const float* bias, int O, float* maps, v3d_stream_t stream) {
+  if (!a.split) return v3d_dense_train_head_fwd(x.hi, a.B, a.H, a.W, weight, bias, O, maps, stream);
+  V3D_CHECK_LAUNCH();
+  return dt_conv2d_plain(x.hi, x.lo, a.base + a.off_himg, bias, 0, a.B, a.H, a.W, DT_C, O, 1, nullptr, nullptr, maps, stream);
+}
+
+static int dt_forward(DtT bev, int B, int H, int W, const v3d_dense_train_layer* layers, int n_layers, const float* head_weight,
+                      const float* head_bias, int O, void* arena, float* maps, bool split, v3d_stream_t stream) {
+  const DtArena a = dt_arena_layout(B, H, W, n_layers, O, split, arena);
+  for (int l = 0; l < n_layers; l++)
+    if (!layers[l].weight || !layers[l].gamma || !layers[l].beta || (layers[l].ksize != 1 && layers[l].ksize != 3)) return V3D_EINVAL;
+  DT_TRY(dt_step_pack(a, layers, n_layers, head_weight, O, stream));
+  float* partial = (float*)(a.base + a.off_partial);
+  DtT x = bev;
+  for (int l = 0; l < n_layers; l++) {
+    const v3d_dense_train_layer& L = layers[l];
+    const DtT raw = a.at(a.off_raw, l), act = a.at(a.off_act, l);
+    float* mean = (float*)(a.base + a.off_stat) + (size_t)l * 2 * DT_C;
+    DT_TRY(dt_step_conv(a, x, a.image(2 * l), L.ksize, raw, partial, stream));
+    DT_TRY(v3d_dense_train_bn_finalize(partial, a.stat_rows, a.M, L.eps, L.momentum, mean, mean + DT_C, L.running_mean, L.running_var,
+                                       L.num_batches_tracked, stream));
+    DT_TRY(dt_bn_relu_apply(raw, a.M, mean, mean + DT_C, L.gamma, L.beta, 1, act, stream));
+    x = act;
+  }
+  return dt_step_head_fwd(a, x, head_weight, head_bias, O, maps, stream);
+}
+
+static int dt_backward(DtT bev, const float* dmaps, int B, int H, int W, const v3d_dense_train_layer* layers, int n_layers,
+                       const float* head_weight, int O, void* arena, float* dhead_weight, float* dhead_bias, DtT dbev, bool split,
+                       v3d_stream_t stream) {
+  const DtArena a = dt_arena_layout(B, H, W, n_layers, O, split, arena);
+  void* ws = a.base + a.off_ws;
+  const size_t ws_bytes = a.total - a.off_ws;
+  const DtT g[2] = {a.at(a.off_g0), a.at(a.off_g1)};
+  const DtT feat = a.at(a.off_act, n_layers - 1);
+  DT_TRY(dt_head_bwd(feat.hi, feat.lo, dmaps, B, H, W, head_weight, O, g[0].hi, g[0].lo, dhead_weight, dhead_bias, ws, ws_bytes, stream));
+  int cur = 0;  // g[cur] = gradient w.r.t. the post-ReLU output of layer l
+  for (int l = n_layers - 1; l >= 0; l--) {
+    const v3d_dense_train_layer& L = layers[l];
+    if (!L.grad_weight || !L.grad_gamma || !L.grad_beta || (L.ksize != 1 && L.ksize != 3)) return V3D_EINVAL;
+    const DtT raw = a.at(a.off_raw, l), xin = l == 0 ? bev : a.at(a.off_act, l - 1);
+    const float* mean = (const float*)(a.base + a.off_stat) + (size_t)l * 2 * DT_C;
+    // gradient w.r.t. the raw convolution output, in place
+    DT_TRY(dt_bn_relu_bwd(raw.hi, raw.lo, g[cur].hi, g[cur].lo, a.M, mean, mean + DT_C, L.gamma, L.beta, 1, g[cur].hi, g[cur].lo, L.grad_gamma,
+                          L.grad_beta, ws, ws_bytes, stream));
+    DT_TRY(dt_wgrad(xin, g[cur], B, H, W, L.ksize, L.grad_weight, ws, ws_bytes, stream));
+    DT_TRY(dt_step_conv(a, g[cur], a.image(2 * l + 1), L.ksize, l == 0 ? dbev : g[cur ^ 1], nullptr, stream));
+    cur ^= 1;
+  }
+  return V3D_OK;
+}
 
 // bev: bf16 NHWC (B, H, W, 128) -> maps fp32 (B, O, H, W).  layers[l]: weight (128, 128, k, k), gamma, beta, running statistics.
 extern "C" int v3d_dense_train_forward(const void* bev, int B, int H, int W, const v3d_dense_train_layer* layers, int n_layers,
                                        const float* head_weight, const float* head_bias, int O, void* arena, float* maps,
                                        v3d_stream_t stream) {
   if (!bev || !layers || !arena || !maps || !head_weight || n_layers < 1 || n_layers > 16) return V3D_EINVAL;
-  const DtArena a = dt_arena_layout(B, H, W, n_layers, O);
-  unsigned char* base = (unsigned char*)arena;
-  const long long M = (long long)B * H * W;
-  const void* x = bev;
-  const size_t img_stride = (((size_t)9 * DT_B_BYTES) + 255) & ~(size_t)255;
-  DtPackJobs jobs;
-  for (int l = 0; l < n_layers; l++) {
-    const v3d_dense_train_layer& L = layers[l];
-    if (!L.weight || !L.gamma || !L.beta || (L.ksize != 1 && L.ksize != 3)) return V3D_EINVAL;
-    jobs.w[l] = L.weight;
-    jobs.taps[l] = L.ksize * L.ksize;
-  }
-  // image 2 l: forward, 2 l + 1: transposed / tap-flipped for the data gradient (read by v3d_dense_train_backward: the weights
-  // do not change between the two calls of a step)
-  hipLaunchKernelGGL(dt_pack_all_kernel, dim3(32, 2 * n_layers), dim3(256), 0, (hipStream_t)stream, jobs, base + a.off_img, img_stride);
-  for (int l = 0; l < n_layers; l++) {
-    const v3d_dense_train_layer& L = layers[l];
-    void* img = base + a.off_img + (size_t)(2 * l) * img_stride;
-    void* raw = base + a.off_raw + (size_t)l * a.act_bytes;
-    void* act = base + a.off_act + (size_t)l * a.act_bytes;
-    float* mean = (float*)(base + a.off_stat) + (size_t)l * 2 * DT_C;
-    float* partial = (float*)(base + a.off_partial);
-    DT_TRY(v3d_dense_train_conv(x, img, B, H, W, L.ksize, raw, partial, stream));
-    DT_TRY(v3d_dense_train_bn_finalize(partial, a.tiles, M, L.eps, L.momentum, mean, mean + DT_C, L.running_mean, L.running_var,
-                                       L.num_batches_tracked, stream));
-    DT_TRY(v3d_dense_train_bn_relu_apply(raw, M, mean, mean + DT_C, L.gamma, L.beta, 1, act, stream));
-    x = act;
-  }
-  return v3d_dense_train_head_fwd(x, B, H, W, head_weight, head_bias, O, maps, stream);
+  return dt_forward(dt_t(bev), B, H, W, layers, n_layers, head_weight, head_bias, O, arena, maps, false, stream);
 }
 
 // dmaps fp32 (B, O, H, W) -> gradients of every layer (layers[l].grad_*), of the head, and of the input (dbev, bf16 NHWC).
@@ -1314,172 +1437,16 @@ extern "C" int v3d_dense_train_backward(const void* bev, const float* dmaps, int
                                         float* dhead_bias, void* dbev, v3d_stream_t stream) {
   if (!bev || !dmaps || !layers || !arena || !head_weight || !dhead_weight || !dhead_bias || !dbev || n_layers < 1 || n_layers > 16)
     return V3D_EINVAL;
-  const DtArena a = dt_arena_layout(B, H, W, n_layers, O);
-  unsigned char* base = (unsigned char*)arena;
-  const long long M = (long long)B * H * W;
-  const size_t img_stride = (((size_t)9 * DT_B_BYTES) + 255) & ~(size_t)255;
-  void* ws = base + a.off_ws;
-  const size_t ws_bytes = a.total - a.off_ws;
-  void* g[2] = {base + a.off_g0, base + a.off_g1};
-  const void* feat = base + a.off_act + (size_t)(n_layers - 1) * a.act_bytes;
-  DT_TRY(v3d_dense_train_head_bwd(feat, dmaps, B, H, W, head_weight, O, g[0], dhead_weight, dhead_bias, ws, ws_bytes, stream));
-  int cur = 0;  // g[cur] = gradient w.r.t. the post-ReLU output of layer l
-  for (int l = n_layers - 1; l >= 0; l--) {
-    const v3d_dense_train_layer& L = layers[l];
-    if (!L.grad_weight || !L.grad_gamma || !L.grad_beta) return V3D_EINVAL;
-    const void* raw = base + a.off_raw + (size_t)l * a.act_bytes;
-    const void* xin = l == 0 ? bev : (const void*)(base + a.off_act + (size_t)(l - 1) * a.act_bytes);
-    const float* mean = (const float*)(base + a.off_stat) + (size_t)l * 2 * DT_C;
-    // gradient w.r.t. the raw convolution output, in place
-    DT_TRY(v3d_dense_train_bn_relu_bwd(raw, g[cur], M, mean, mean + DT_C, L.gamma, L.beta, 1, g[cur], L.grad_gamma, L.grad_beta, ws,
-                                       ws_bytes, stream));
-    DT_TRY(v3d_dense_train_wgrad(xin, g[cur], B, H, W, L.ksize, L.grad_weight, ws, ws_bytes, stream));
-    void* img = base + a.off_img + (size_t)(2 * l + 1) * img_stride;  // packed by the forward call
-    void* out = l == 0 ? dbev : g[cur ^ 1];
-    DT_TRY(v3d_dense_train_conv(g[cur], img, B, H, W, L.ksize, out, nullptr, stream));
-    cur ^= 1;
-  }
-  return V3D_OK;
+  return dt_backward(dt_t(bev), dmaps, B, H, W, layers, n_layers, head_weight, O, arena, dhead_weight, dhead_bias, dt_t(dbev), false, stream);
 }
 
-// ------------------------------------------------------------------------------------------------ the same step, fp32-class ("bf16x3")
-// The reference's train.py:58-66 runs the dense half in fp32 (no autocast).  This variant keeps EVERY tensor of the step as a
-// split pair (hi + lo bf16 planes: 16 significant bits) and evaluates every product with three MFMA terms (hi*hi + hi*lo + lo*hi,
-// fp32 accumulation: 2^-17 per product, scale-free -- gradients need no calibration):
-//   convolutions, forward and data gradient   csrc/dense_conv.hip's bf16x3 kernels (the inference RPN's), raw output, no epilogue;
-//                                             the data gradient is the same convolution on the channel-swapped, tap-flipped weights
-//   weight gradient                           dt_wgrad_kernel three times -- (x_hi, dy_hi), (x_hi, dy_lo), (x_lo, dy_hi) -- into three
-//                                             sets of slab partials, summed by one fixed-order reduction
-//   batch statistics, BN + ReLU, their        the kernels above on hi + lo (fp32 arithmetic; statistics from the stored values,
-//   backward, the head's gradients            fixed-order two-level reductions as before)
-//   head forward                              dense_conv.hip's 1x1 stream kernel (bias, fp32 NCHW maps)
-// About 2.4x the traffic and 3x the matrix work of the bf16-storage step; no tensor of it ever exists in reduced precision.
-__global__ __launch_bounds__(256) void dt_wt_flip_kernel(const float* __restrict__ w, int taps, float* __restrict__ wt) {
-  const int total = DT_C * DT_C * taps;  // wt[ci][co][t] = w[co][ci][taps - 1 - t]
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-    const int t = i % taps, co = (i / taps) % DT_C, ci = i / (taps * DT_C);
-    wt[i] = w[((size_t)co * DT_C + ci) * taps + (taps - 1 - t)];
-  }
-}
-
-// dt_wgrad_reduce_kernel for any number of slab partials: thread (co, g) sums slabs g, g + 8, ... in that order, the eight group
-// sums are combined in the same fixed tree.
-__global__ __launch_bounds__(1024) void dt_wgrad_reduce_any_kernel(const float* __restrict__ partial, int slabs, int taps, float* __restrict__ dw) {
-  __shared__ float grp[8][3][DT_C];
-  const int ci = blockIdx.x, a0 = blockIdx.y * 3, na = taps - a0 < 3 ? taps - a0 : 3;
-  const int co = threadIdx.x & (DT_C - 1), g = threadIdx.x >> 7;
-  const size_t total = (size_t)taps * DT_C * DT_C;
-  for (int a = 0; a < na; a++) {
-    float v = 0.f;
-    for (int s = g; s < slabs; s += 8) v += partial[(size_t)s * total + ((size_t)(a0 + a) * DT_C + ci) * DT_C + co];
-    grp[g][a][co] = v;
-  }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < DT_C * na; idx += 1024) {
-    const int c = idx / na, a = idx - c * na;
-    const float v = ((grp[0][a][c] + grp[1][a][c]) + (grp[2][a][c] + grp[3][a][c])) + ((grp[4][a][c] + grp[5][a][c]) + (grp[6][a][c] + grp[7][a][c]));
-    dw[((size_t)c * DT_C + ci) * taps + a0 + a] = v;
-  }
-}
-
-static int dt_wgrad_split(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, int B, int H, int W, int ksize, float* dw,
-                          void* workspace, size_t workspace_bytes, hipStream_t st) {
-  if (workspace_bytes < 3 * v3d_dense_train_wgrad_workspace(ksize)) return V3D_EWORKSPACE;
-  const long long tiles = (long long)B * ((H + DT3_TH - 1) / DT3_TH) * ((W + DT3_TW - 1) / DT3_TW);
-  const int slabs = (int)(tiles < DT_WG_SLABS ? tiles : DT_WG_SLABS), taps = ksize * ksize;
-  float* partial = (float*)workspace;
-  const size_t term = (size_t)slabs * taps * DT_C * DT_C;
-  static V3dPerDeviceFlag attr9, attr1;
-  V3D_CHECK_HIP(v3d_set_max_lds(attr9, (const void*)dt_wgrad_kernel<9>, DT_W2_SMEM));
-  V3D_CHECK_HIP(v3d_set_max_lds(attr1, (const void*)dt_wgrad_kernel<1>, DT_W2_SMEM));
-  const void* xs[3] = {x_hi, x_hi, x_lo};
-  const void* ys[3] = {dy_hi, dy_lo, dy_hi};
-  for (int t = 0; t < 3; t++) {
-    if (ksize == 3)
-      hipLaunchKernelGGL(dt_wgrad_kernel<9>, dim3(4 * slabs), dim3(768), DT_W2_SMEM, st, (const dt_bf16*)xs[t], (const dt_bf16*)ys[t], B, H, W,
-                         slabs, partial + t * term);
-    else
-      hipLaunchKernelGGL(dt_wgrad_kernel<1>, dim3(4 * slabs), dim3(768), DT_W2_SMEM, st, (const dt_bf16*)xs[t], (const dt_bf16*)ys[t], B, H, W,
-                         slabs, partial + t * term);
-  }
-  hipLaunchKernelGGL(dt_wgrad_reduce_any_kernel, dim3(DT_C, (taps + 2) / 3), dim3(1024), 0, st, partial, 3 * slabs, taps, dw);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
-}
-
-struct DtArenaS {
-  size_t plane;  // one bf16 plane of an activation
-  size_t off_raw, off_act, off_stat, off_partial, off_img, off_himg, off_wt, off_g0, off_g1, off_ws, img, total;
-};
-static DtArenaS dt_arena_layout_split(int B, int H, int W, int n_layers, int O) {
-  DtArenaS a;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  a.plane = up((size_t)B * H * W * DT_C * 2);
-  a.img = up(v3d_conv2d_weight_image_bytes(DT_C, DT_C, 3));
-  size_t o = 0;
-  a.off_raw = o; o += (size_t)n_layers * 2 * a.plane;
-  a.off_act = o; o += (size_t)n_layers * 2 * a.plane;
-  a.off_stat = o; o += up((size_t)n_layers * 2 * DT_C * 4);
-  a.off_partial = o; o += up((size_t)DT_RED_BLOCKS * 2 * DT_C * 4);
-  a.off_img = o; o += (size_t)n_layers * 2 * a.img;
-  a.off_himg = o; o += up(v3d_conv2d_weight_image_bytes(DT_C, O, 1));
-  a.off_wt = o; o += up((size_t)9 * DT_C * DT_C * 4);
-  a.off_g0 = o; o += 2 * a.plane;
-  a.off_g1 = o; o += 2 * a.plane;
-  size_t ws = 3 * v3d_dense_train_wgrad_workspace(3);
-  if (v3d_dense_train_head_workspace(O) > ws) ws = v3d_dense_train_head_workspace(O);
-  if (v3d_dense_train_bn_bwd_workspace() > ws) ws = v3d_dense_train_bn_bwd_workspace();
-  a.off_ws = o; o += up(ws);
-  a.total = o;
-  return a;
-}
-
-extern "C" size_t v3d_dense_train_arena_bytes_split(int B, int H, int W, int n_layers, int O) {
-  if (B < 1 || H < 1 || W < 1 || n_layers < 1 || O < 1) return 0;
-  return dt_arena_layout_split(B, H, W, n_layers, O).total;
-}
-
-// bev: split NHWC planes (B, H, W, 128) -> maps fp32 (B, O, H, W)
+// the same step on split NHWC planes (B, H, W, 128): bev_hi + bev_lo -> maps fp32 (B, O, H, W)
 extern "C" int v3d_dense_train_forward_split(const void* bev_hi, const void* bev_lo, int B, int H, int W, const v3d_dense_train_layer* layers,
                                              int n_layers, const float* head_weight, const float* head_bias, int O, void* arena, float* maps,
                                              v3d_stream_t stream) {
   if (!bev_hi || !bev_lo || !layers || !arena || !maps || !head_weight || n_layers < 1 || n_layers > 16 || O < 1 || O > 16) return V3D_EINVAL;
   if ((long long)B * H * W > 0x7FFFFFF0ll / DT_C) return V3D_EINVAL;
-  const DtArenaS a = dt_arena_layout_split(B, H, W, n_layers, O);
-  unsigned char* base = (unsigned char*)arena;
-  const long long M = (long long)B * H * W;
-  hipStream_t st = (hipStream_t)stream;
-  float* wt = (float*)(base + a.off_wt);
-  for (int l = 0; l < n_layers; l++) {  // image 2 l: forward, 2 l + 1: the data gradient's (read by the backward call of this step)
-    const v3d_dense_train_layer& L = layers[l];
-    if (!L.weight || !L.gamma || !L.beta || (L.ksize != 1 && L.ksize != 3)) return V3D_EINVAL;
-    DT_TRY(v3d_conv2d_pack_weights(L.weight, nullptr, DT_C, DT_C, L.ksize, V3D_PREC_BF16X3, base + a.off_img + (size_t)(2 * l) * a.img, stream));
-    hipLaunchKernelGGL(dt_wt_flip_kernel, dim3(64), dim3(256), 0, st, L.weight, L.ksize * L.ksize, wt);
-    DT_TRY(v3d_conv2d_pack_weights(wt, nullptr, DT_C, DT_C, L.ksize, V3D_PREC_BF16X3, base + a.off_img + (size_t)(2 * l + 1) * a.img, stream));
-  }
-  DT_TRY(v3d_conv2d_pack_weights(head_weight, nullptr, O, DT_C, 1, V3D_PREC_BF16X3, base + a.off_himg, stream));
-  const long long want = (M + 15) / 16;
-  const int blocks = (int)(want < DT_RED_BLOCKS ? want : DT_RED_BLOCKS);
-  float* partial = (float*)(base + a.off_partial);
-  const void *x_hi = bev_hi, *x_lo = bev_lo;
-  for (int l = 0; l < n_layers; l++) {
-    const v3d_dense_train_layer& L = layers[l];
-    unsigned char* raw = base + a.off_raw + (size_t)l * 2 * a.plane;
-    unsigned char* act = base + a.off_act + (size_t)l * 2 * a.plane;
-    float* mean = (float*)(base + a.off_stat) + (size_t)l * 2 * DT_C;
-    DT_TRY(dt_conv2d_plain(x_hi, x_lo, base + a.off_img + (size_t)(2 * l) * a.img, nullptr, 0, B, H, W, DT_C, DT_C, L.ksize, raw,
-                                  raw + a.plane, nullptr, stream));
-    hipLaunchKernelGGL(dt_bn_stats_kernel, dim3(blocks), dim3(256), 0, st, (const dt_bf16*)raw, (const dt_bf16*)(raw + a.plane), M, partial);
-    DT_TRY(v3d_dense_train_bn_finalize(partial, blocks, M, L.eps, L.momentum, mean, mean + DT_C, L.running_mean, L.running_var,
-                                       L.num_batches_tracked, stream));
-    const long long ab = (M + 15) / 16;
-    hipLaunchKernelGGL(dt_bn_relu_apply_kernel, dim3((unsigned)(ab < 4096 ? ab : 4096)), dim3(256), 0, st, (const dt_bf16*)raw,
-                       (const dt_bf16*)(raw + a.plane), M, mean, mean + DT_C, L.gamma, L.beta, 1, (dt_bf16*)act, (dt_bf16*)(act + a.plane));
-    x_hi = act;
-    x_lo = act + a.plane;
-  }
-  V3D_CHECK_LAUNCH();
-  return dt_conv2d_plain(x_hi, x_lo, base + a.off_himg, head_bias, 0, B, H, W, DT_C, O, 1, nullptr, nullptr, maps, stream);
+  return dt_forward(dt_t(bev_hi, bev_lo), B, H, W, layers, n_layers, head_weight, head_bias, O, arena, maps, true, stream);
 }
 
 // dmaps fp32 (B, O, H, W) -> gradients of every layer, of the head, and of the input (dbev: split NHWC planes)
@@ -1489,32 +1456,6 @@ extern "C" int v3d_dense_train_backward_split(const void* bev_hi, const void* be
   if (!bev_hi || !bev_lo || !dmaps || !layers || !arena || !head_weight || !dhead_weight || !dhead_bias || !dbev_hi || !dbev_lo || n_layers < 1 ||
       n_layers > 16 || O < 1 || O > 16)
     return V3D_EINVAL;
-  const DtArenaS a = dt_arena_layout_split(B, H, W, n_layers, O);
-  unsigned char* base = (unsigned char*)arena;
-  const long long M = (long long)B * H * W;
-  hipStream_t st = (hipStream_t)stream;
-  void* ws = base + a.off_ws;
-  const size_t ws_bytes = a.total - a.off_ws;
-  unsigned char* g[2] = {base + a.off_g0, base + a.off_g1};
-  const unsigned char* feat = base + a.off_act + (size_t)(n_layers - 1) * 2 * a.plane;
-  DT_TRY(dt_head_bwd(feat, feat + a.plane, dmaps, B, H, W, head_weight, O, g[0], g[0] + a.plane, dhead_weight, dhead_bias, ws, ws_bytes, stream));
-  int cur = 0;  // g[cur] = gradient w.r.t. the post-ReLU output of layer l
-  for (int l = n_layers - 1; l >= 0; l--) {
-    const v3d_dense_train_layer& L = layers[l];
-    if (!L.grad_weight || !L.grad_gamma || !L.grad_beta) return V3D_EINVAL;
-    const unsigned char* raw = base + a.off_raw + (size_t)l * 2 * a.plane;
-    const void* xin_hi = l == 0 ? bev_hi : (const void*)(base + a.off_act + (size_t)(l - 1) * 2 * a.plane);
-    const void* xin_lo = l == 0 ? bev_lo : (const void*)(base + a.off_act + (size_t)(l - 1) * 2 * a.plane + a.plane);
-    const float* mean = (const float*)(base + a.off_stat) + (size_t)l * 2 * DT_C;
-    // gradient w.r.t. the raw convolution output, in place
-    DT_TRY(dt_bn_relu_bwd(raw, raw + a.plane, g[cur], g[cur] + a.plane, M, mean, mean + DT_C, L.gamma, L.beta, 1, g[cur], g[cur] + a.plane,
-                          L.grad_gamma, L.grad_beta, ws, ws_bytes, stream));
-    DT_TRY(dt_wgrad_split(xin_hi, xin_lo, g[cur], g[cur] + a.plane, B, H, W, L.ksize, L.grad_weight, ws, ws_bytes, st));
-    void* out_hi = l == 0 ? dbev_hi : (void*)g[cur ^ 1];
-    void* out_lo = l == 0 ? dbev_lo : (void*)(g[cur ^ 1] + a.plane);
-    DT_TRY(dt_conv2d_plain(g[cur], g[cur] + a.plane, base + a.off_img + (size_t)(2 * l + 1) * a.img, nullptr, 0, B, H, W, DT_C, DT_C,
-                                  L.ksize, out_hi, out_lo, nullptr, stream));
-    cur ^= 1;
-  }
-  return V3D_OK;
+  return dt_backward(dt_t(bev_hi, bev_lo), dmaps, B, H, W, layers, n_layers, head_weight, O, arena, dhead_weight, dhead_bias,
+                     dt_t(dbev_hi, dbev_lo), true, stream);
 }

@@ -102,16 +102,9 @@ class DenseTrainPlan(object):
         self.B, self.H, self.W, self.device = int(B), int(H), int(W), device
         self.O = head.conv_cls.out_channels + head.conv_reg.out_channels
         self.split = precision == "bf16x3"
-        lib = L.lib()
-        if self.split:
-            n = int(lib.v3d_dense_train_arena_bytes_split(self.B, self.H, self.W, len(self.convs), self.O))
-            self.arena = torch.empty(n, dtype=torch.uint8, device=device)
-        else:
-            n = int(lib.v3d_dense_train_arena_bytes(self.B, self.H, self.W, len(self.convs), self.O))
-            self.arena = torch.empty(n, dtype=torch.uint8, device=device)
-            with torch.cuda.device(device):
-                L.check(lib.v3d_dense_train_arena_init(L.ptr(self.arena), self.B, self.H, self.W, len(self.convs), self.O, L.stream_ptr()),
-                        "dense_train_arena_init")
+        arena_bytes = getattr(L.lib(), "v3d_dense_train_arena_bytes_split" if self.split else "v3d_dense_train_arena_bytes")
+        n = int(arena_bytes(self.B, self.H, self.W, len(self.convs), self.O))
+        self.arena = torch.empty(n, dtype=torch.uint8, device=device)  # nothing in it is read before it is written
         self.generation = 0
 
     def parameters(self):
@@ -149,6 +142,10 @@ class DenseTrainPlan(object):
         b = torch.cat((self.head.conv_cls.bias.detach(), self.head.conv_reg.bias.detach()), 0)
         return w.float().contiguous(), b.float().contiguous()
 
+    def _planes(self, t):
+        """The native calls' pointer arguments of a tensor: (hi, lo) of a split pair, else the one bf16 plane."""
+        return (L.ptr(t[0]), L.ptr(t[1])) if self.split else (L.ptr(t),)
+
     def forward(self, bev):
         """bev bf16 (B, 128, H, W) channels_last [split plan: fp32 (B, 128, H, W)] -> fused head maps fp32 (B, O, H, W)."""
         maps = torch.empty((self.B, self.O, self.H, self.W), dtype=torch.float32, device=self.device)
@@ -158,13 +155,9 @@ class DenseTrainPlan(object):
             if self.split:
                 from .runtime import to_split_nhwc
                 bev = to_split_nhwc(bev.float().contiguous())  # (hi, lo) bf16 NHWC planes, kept for the backward (weight gradient)
-                L.check(L.lib().v3d_dense_train_forward_split(L.ptr(bev[0]), L.ptr(bev[1]), self.B, self.H, self.W, io, len(self.convs),
-                                                              L.ptr(self._hw), L.ptr(self._hb), self.O, L.ptr(self.arena), L.ptr(maps),
-                                                              L.stream_ptr()), "dense_train_forward_split")
-            else:
-                L.check(L.lib().v3d_dense_train_forward(L.ptr(bev), self.B, self.H, self.W, io, len(self.convs), L.ptr(self._hw),
-                                                        L.ptr(self._hb), self.O, L.ptr(self.arena), L.ptr(maps), L.stream_ptr()),
-                        "dense_train_forward")
+            name = "dense_train_forward_split" if self.split else "dense_train_forward"
+            L.check(getattr(L.lib(), "v3d_" + name)(*self._planes(bev), self.B, self.H, self.W, io, len(self.convs), L.ptr(self._hw),
+                                                    L.ptr(self._hb), self.O, L.ptr(self.arena), L.ptr(maps), L.stream_ptr()), name)
         stats = [t for b in self.bns if b.track_running_stats and b.running_mean is not None
                  for t in (b.running_mean, b.running_var, b.num_batches_tracked)]
         if stats:  # updated through raw pointers: bump the version counters (host side only)
@@ -187,19 +180,18 @@ class DenseTrainPlan(object):
         io = self._io(grads)
         with torch.cuda.device(self.device):
             if self.split:
-                planes = torch.empty((2, self.B, self.H, self.W, 128), dtype=torch.bfloat16, device=self.device)
-                L.check(L.lib().v3d_dense_train_backward_split(L.ptr(self._bev[0]), L.ptr(self._bev[1]), L.ptr(dmaps), self.B, self.H, self.W,
-                                                               io, len(self.convs), L.ptr(self._hw), self.O, L.ptr(self.arena), L.ptr(dhw),
-                                                               L.ptr(dhb), L.ptr(planes[0]), L.ptr(planes[1]), L.stream_ptr()),
-                        "dense_train_backward_split")
-                dbev = torch.empty((self.B, 128, self.H, self.W), dtype=torch.float32, device=self.device)  # what the sparse plan takes
-                L.check(L.lib().v3d_split_nhwc_to_nchw(L.ptr(planes[0]), L.ptr(planes[1]), self.B, 128, self.H, self.W, L.ptr(dbev),
-                                                       L.stream_ptr()), "split_nhwc_to_nchw")
+                out = torch.empty((2, self.B, self.H, self.W, 128), dtype=torch.bfloat16, device=self.device)
             else:
-                dbev = torch.empty((self.B, 128, self.H, self.W), dtype=torch.bfloat16, device=self.device, memory_format=torch.channels_last)
-                L.check(L.lib().v3d_dense_train_backward(L.ptr(self._bev), L.ptr(dmaps), self.B, self.H, self.W, io, len(self.convs),
-                                                         L.ptr(self._hw), self.O, L.ptr(self.arena), L.ptr(dhw), L.ptr(dhb), L.ptr(dbev),
-                                                         L.stream_ptr()), "dense_train_backward")
+                out = torch.empty((self.B, 128, self.H, self.W), dtype=torch.bfloat16, device=self.device, memory_format=torch.channels_last)
+            name = "dense_train_backward_split" if self.split else "dense_train_backward"
+            L.check(getattr(L.lib(), "v3d_" + name)(*self._planes(self._bev), L.ptr(dmaps), self.B, self.H, self.W, io, len(self.convs),
+                                                    L.ptr(self._hw), self.O, L.ptr(self.arena), L.ptr(dhw), L.ptr(dhb), *self._planes(out),
+                                                    L.stream_ptr()), name)
+            dbev = out
+            if self.split:
+                dbev = torch.empty((self.B, 128, self.H, self.W), dtype=torch.float32, device=self.device)  # what the sparse plan takes
+                L.check(L.lib().v3d_split_nhwc_to_nchw(L.ptr(out[0]), L.ptr(out[1]), self.B, 128, self.H, self.W, L.ptr(dbev),
+                                                       L.stream_ptr()), "split_nhwc_to_nchw")
         nc = self.head.conv_cls.out_channels
         grads += [dhw[:nc].reshape(self.head.conv_cls.weight.shape), dhb[:nc], dhw[nc:].reshape(self.head.conv_reg.weight.shape), dhb[nc:]]
         return dbev, grads
