@@ -651,6 +651,35 @@ int v3d_keypoint_seg_loss_fwd_bwd(const float* keypoints, const float* logits, i
                                   float gamma, uint8_t* labels, float* losses, float* d_logits, v3d_stream_t stream);
 int v3d_keypoint_seg_loss_scale(float* d_logits, int rows, const float* g, v3d_stream_t stream);
 
+/* ---- Voxel RoI pooling for PV-RCNN's stage 2 (the pooling of Voxel R-CNN, arXiv 2012.15712; opt-in, cfg.VOXELPOOL; no upstream
+ * counterpart).  The definition is this repository's (detector/voxel_roi_pool.py, tests/voxel_roi_pool_ref.py).
+ * The voxel query of ONE level: points (rows, 3) f32 are the RoI grid points, frame of a row = row / rows_per_frame; the level is its
+ * active coordinates coords (cap, 4) i32 = (b, z, y, x), 16-byte aligned, of which the first min(*n, cap) rows are live (n: DEVICE
+ * int32 -- never read by the host: the call only enqueues and can be captured), its shape_host (D, H, W), scale_host (x, y, z) = base
+ * voxel size * stride as the caller rounded it in fp32 and offset_host (x, y, z) = the grid origin.  Per point, all in fp32 with one
+ * IEEE operation per step: home cell v = floor((p - offset) / scale); candidates v + (dz, dy, dx), |d| <= range_host (rz, ry, rx), in
+ * ascending (dz, dy, dx) order; hit = inside the shape, an active site of the point's frame (b < 64), and
+ * (dx^2 + dy^2) + dz^2 < radius * radius for d = ((u * scale + offset) + 0.5 * scale) - p.  idx (rows, nsample) i32 = the rows of the
+ * first nsample hits in scan order, the rest repeating the first; no hit: all -1 and empty[row] = 1 (u8).  The result does not depend
+ * on the order of the coordinate rows' insertion into the hash.  workspace: v3d_voxel_query_workspace(cap) bytes (the coordinate hash,
+ * rebuilt by every call).  rows <= 2^22, nsample <= 64, range <= 7 per axis, cap < 2^24 - 1: beyond, V3D_EUNSUPPORTED. */
+size_t v3d_voxel_query_workspace(int cap);
+int v3d_voxel_query(const float* points, int rows, int rows_per_frame, const int32_t* coords, const int32_t* n, int cap,
+                    const int32_t* shape_host, const float* scale_host, const float* offset_host, const int32_t* range_host,
+                    float radius, int nsample, int32_t* idx, uint8_t* empty, void* workspace, size_t workspace_bytes,
+                    v3d_stream_t stream);
+/* The level's shared two-layer MLP and the max over the slots in one launch.  The first layer is linear in its input row
+ * [centre(u) - p | feat(u)] and its feature part depends on the voxel alone: the caller computes P (cap, K1) = feat @ W1[3:] once per
+ * active voxel (v3d_linear_rows; row stride ldp, ldp % 4 == 0, 16-byte aligned), and this kernel forms
+ *   h[s, k] = relu(P[u_s, k] + ((r.x * wx[0, k] + r.y * wx[1, k]) + r.z * wx[2, k]) + b1[k]),   u_s = idx[row, s], r = centre(u_s) - p
+ *   out[row * ldo + j] = max over s of relu(sum_k h[s, k] * W[k * Nout + j] + bias[j])           (fmaf chain, k ascending)
+ * for j < Nout; a row whose idx[row, 0] < 0 (an empty point) is written as exact zeros.  wx (3, K1), b1 (K1), W (K1, Nout), bias (Nout)
+ * with eval BatchNorm folded in by the caller; out is a column block of the caller's (rows, ldo) matrix, other columns untouched.
+ * (K1, Nout) in {16, 32, 64}^2 except (16, 64) and (64, 16), rows <= 2^22, nsample <= 64: beyond, V3D_EUNSUPPORTED. */
+int v3d_voxel_pool_pair(const float* P, int ldp, const int32_t* coords, int cap, const float* points, const int32_t* idx, int rows,
+                        int nsample, const float* scale_host, const float* offset_host, int K1, const float* wx, const float* b1,
+                        const float* W, const float* bias, int Nout, float* out, int ldo, v3d_stream_t stream);
+
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.
  * Every layer must be conv + BatchNorm1d (training mode: batch statistics) [+ ReLU] with a power-of-two Cout in [4, 256].

@@ -69,6 +69,14 @@ def _defaults():
         # (hidden widths MLPS) whose sigmoid scales every keypoint's row before RoI-grid pooling; supervised by a focal loss on
         # "inside a ground-truth box", keypoints inside a box grown by GT_EXTRA_WIDTH (w, l, h) only are ignored
         PKW=dict(ENABLED=False, MLPS=[256], GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], FOCAL_ALPHA=0.25, FOCAL_GAMMA=2.0, LOSS_WEIGHT=1.0),
+        # voxel RoI pooling for stage 2 of PV-RCNN (detector/voxel_roi_pool.py), opt-in: the GRID^3 regular grid points of every RoI
+        # query the backbone's own voxels of LEVELS (1: the voxelized input, k + 1: the output of stage k -- strides 2, 4, 8 and
+        # channels 32, 64, 64 for [2, 3, 4]) inside an index window of half-widths RANGE (rz, ry, rx) and a RADIUS in metres, at most
+        # NSAMPLE per point, pooled by a PointNet per level (MLPS after the 3 + C input) and reduced per RoI (MLPS_REDUCTION; None:
+        # [GRID^3 * 96, 256, 256], a given list must start with that width); LEVEL_CHANNELS: None = the backbone's channels of LEVELS,
+        # else the channel count per level (levels that do not come from this backbone); replaces keypoints, set abstraction, BEV lookup and RoI-grid pooling
+        VOXELPOOL=dict(ENABLED=False, GRID=6, LEVELS=[2, 3, 4], RANGE=[[2, 2, 2], [2, 2, 2], [1, 2, 2]], RADIUS=[0.4, 0.8, 1.6],
+                       NSAMPLE=16, MLPS=[[32, 32], [32, 32], [32, 32]], MLPS_REDUCTION=None, LEVEL_CHANNELS=None),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",

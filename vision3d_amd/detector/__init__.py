@@ -11,6 +11,7 @@ _EXPORTS = {
     "RefinementLoss": "refinement",
     "KeypointWeighting": "keypoint_weighting",
     "KeypointSegLoss": "keypoint_weighting",
+    "VoxelRoiPool": "voxel_roi_pool",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -10,10 +10,14 @@ Data flow of the pieces that exist upstream (its `forward` raises: stage 2 was n
     [raw points, level 0..3] --set abstraction around the keypoints--> per-keypoint features, + bilinear BEV lookup
     BEV map --ProposalLayer--> (P_cls, P_reg)
 
+With cfg.VOXELPOOL.ENABLED (opt-in) stage 2 is fed without keypoints: the RoI grid points pool the sparse CNN's own levels
+(detector/voxel_roi_pool.py), the keypoint sampler, the set abstraction, the BEV lookup and RoI-grid pooling are not built.
+
 Sub-module names (`pnets`, `roi_grid_pool`, `vfe`, `cnn`, `bev`, `proposal_layer`, `refinement_layer`) are the
 reference's, so checkpoints load.  FPS / ball query / grouping run on the MI355X kernels behind
 vision3d_amd.pointnet2.
 """
+import contextlib
 import copy
 
 import torch
@@ -21,7 +25,7 @@ from torch import nn
 
 from ..pointnet2 import pointnet2_utils as pn2
 from ..pointnet2.pointnet2_modules import PointnetSAModuleMSG
-from . import keypoint_weighting, layers, proposal, refinement, roi_grid_pool, sparse_cnn
+from . import keypoint_weighting, layers, proposal, refinement, roi_grid_pool, sparse_cnn, voxel_roi_pool
 
 
 from ..runtime import PlanCache as _PlanCache  # (a dict a deep copy of the model starts empty: events, pinned words, device clones)
@@ -39,6 +43,10 @@ class PV_RCNN(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
+        self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
+        if self.voxel_pool:
+            self._init_voxel_pool(cfg)
+            return
         self.pnets = self.build_pointnets(cfg)
         self.roi_grid_pool = roi_grid_pool.RoiGridPool(cfg)
         self.vfe = layers.VoxelFeatureExtractor()
@@ -49,6 +57,17 @@ class PV_RCNN(nn.Module):
         if keypoint_weighting.pkw_config(cfg)["ENABLED"]:  # (the attribute, and with it its state_dict keys, exist only then)
             c_total = sum(sum(p.out_channels()) for p in self.pnets) + cfg.PROPOSAL.C_IN  # (+ the BEV map the proposal head reads)
             self.keypoint_weighting = keypoint_weighting.KeypointWeighting(cfg, c_total)
+
+    def _init_voxel_pool(self, cfg):
+        """cfg.VOXELPOOL.ENABLED: stage 2 pools the backbone's own voxels around the RoI grid points (detector/voxel_roi_pool.py) -- no
+        keypoint sampler, point nets, BEV gatherer or RoI-grid pooling are built; the other sub-modules keep their names."""
+        if keypoint_weighting.pkw_config(cfg)["ENABLED"]:
+            raise ValueError("cfg.PKW.ENABLED with cfg.VOXELPOOL.ENABLED: voxel RoI pooling has no keypoints to weight")
+        self.vfe = layers.VoxelFeatureExtractor()
+        self.cnn = sparse_cnn.CNN_FACTORY[cfg.CNN](cfg)
+        self.voxel_roi_pool = voxel_roi_pool.VoxelRoiPool(cfg, self.cnn.voxel_offset, self.cnn.base_voxel_size)
+        self.proposal_layer = proposal.ProposalLayer(cfg)
+        self.refinement_layer = refinement.RefinementLayer(cfg)
 
     def build_pointnets(self, cfg):
         """One multi-scale set-abstraction module per feature source (raw points, then the CNN levels)."""
@@ -180,7 +199,7 @@ class PV_RCNN(nn.Module):
         # voxel CNN and the proposal head, and joins before the first consumer (the set abstraction of stage 2).  A caller that
         # already knows the next frame can start its sampling earlier still (`prefetch_keypoints`).
         main = torch.cuda.current_stream(item["points"].device)
-        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc":  # ("spc": sampled behind stage 1, _proposals_then_keypoints)
+        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc" and not self.voxel_pool:  # ("spc": sampled behind stage 1, _proposals_then_keypoints)
             self.prefetch_keypoints(item)
         native = self._native_item(item)
         if native:                    # eval, no autograd, voxels of the device Preprocessor: the sparse CNN as one native plan
@@ -190,7 +209,12 @@ class PV_RCNN(nn.Module):
                 voxel_features = item["voxel_mean"]
             else:                         # reference-style (M, K, C) slots + occupancy
                 voxel_features = self.vfe(item["features"], item["occupancy"])
-            cnn_features, bev_map = self.cnn(voxel_features, item["coordinates"], item["batch_size"])
+            if self.voxel_pool:
+                volumes, bev_map = self.cnn.forward_sparse(voxel_features, item["coordinates"], item["batch_size"])
+                cnn_features = [voxel_roi_pool.VoxelLevel(volumes[lv - 1].features, volumes[lv - 1].indices, None, volumes[lv - 1].spatial_shape,
+                                                          self.cfg.STRIDES[lv - 1]) for lv in self.voxel_roi_pool.levels]
+            else:
+                cnn_features, bev_map = self.cnn(voxel_features, item["coordinates"], item["batch_size"])
         if native and self.native_tail:  # the fused [cls | reg] maps are what the native top-k of stage1_proposals reads
             item["_head_maps"] = self.proposal_layer.native_head(bev_map)
             item["P_cls"], item["P_reg"] = self.proposal_layer.maps_from_fused(item["_head_maps"])
@@ -309,6 +333,11 @@ class PV_RCNN(nn.Module):
                 plan.check_overflow()  # raises with the layers that hit their capacity
             break
         outs = st["outs"]
+        if self.voxel_pool:
+            # the levels as the plan holds them: every row of its buffers, the live count in device memory (the host words read above
+            # judge the frame; nothing of stage 2 is sized by them)
+            whole = [(vm, co, None, self.cnn.grid_shape)] + list(outs)
+            return [voxel_roi_pool.VoxelLevel(*whole[lv - 1], self.cfg.STRIDES[lv - 1]) for lv in self.voxel_roi_pool.levels], st["bev_map"]
         volumes = [spconv.SparseConvTensor(vm, co, self.cnn.grid_shape, b)]
         volumes += [spconv.SparseConvTensor(f[:n], c[:n], shape, b) for (f, c, _, shape), n in zip(outs, host)]
         points = [self.cnn.to_global(stride, vol) for stride, vol in zip(self.cfg.STRIDES, volumes)]
@@ -361,6 +390,9 @@ class PV_RCNN(nn.Module):
         return items
 
     def _refuse_prefetch_under_spc(self):
+        if self.voxel_pool:
+            raise RuntimeError("prefetch_keypoints: cfg.VOXELPOOL.ENABLED pools the backbone's voxels around the RoI grid points; the "
+                               "model has no keypoints to sample")
         if self.keypoint_sampler()[0] == "spc":
             raise RuntimeError("prefetch_keypoints: KEYPOINTS.SAMPLER 'spc' samples around the frame's stage-1 proposals, so the "
                                "keypoints cannot be started before stage 1 (use 'sector' or 'fps' to prefetch)")
@@ -403,6 +435,17 @@ class PV_RCNN(nn.Module):
         class_idx = torch.arange(n_cls, device=scores.device).repeat_interleave(head.TOPK)
         return boxes.reshape(b, -1, head.DOF), scores.reshape(b, -1), class_idx
 
+    def _voxel_stage2(self, item, train=False):
+        """Stage 2 under cfg.VOXELPOOL: the stage-1 proposals (constants under training), the voxel RoI pooling of the backbone levels
+        stage 1 left in the item, the refinement head.  Leaves what `forward` leaves except keypoints / keypoint_features."""
+        with torch.no_grad() if train else contextlib.nullcontext():
+            boxes, scores, class_idx = self.stage1_proposals(item)
+        boxes = boxes.detach() if train else boxes
+        pooled = self.voxel_roi_pool(boxes, item["_cnn_features"])
+        deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
+        item.update(proposals=boxes, proposal_scores=scores, proposal_class=class_idx, pooled_features=pooled, R_reg=deltas, R_cls=conf)
+        return item, boxes, deltas, conf
+
     def forward(self, item, samples=None, decode=True):
         """Stage 1 + stage 2.  Adds to `item`: keypoints, P_cls, P_reg, keypoint_features (B, 512, K) [cfg.PKW: weighted with the
         sigmoid of K_cls (B, K), which is added too], proposals (B, n, 7),
@@ -411,6 +454,11 @@ class PV_RCNN(nn.Module):
         (B, n, NUM_GRIDPOINTS, 3) in [0, 1) fixes the RoI grid points (the reference draws them with an unseeded torch.rand,
         roi_grid_pool.py:59)."""
         item = self.proposal(item)
+        if self.voxel_pool:  # (`samples` is not used: the RoI grid is regular)
+            item, boxes, deltas, _ = self._voxel_stage2(item)
+            if decode:
+                item["boxes_refined"] = self.refinement_layer.apply_refinements(deltas, boxes)
+            return item
         early = self._proposals_then_keypoints(item)
         features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
         boxes, scores, class_idx = early or self.stage1_proposals(item)
@@ -441,6 +489,8 @@ class PV_RCNN(nn.Module):
         M_rcls, M_rreg for RefinementLoss; with cfg.PKW enabled also K_cls (B, K) and K_label (B, K) for KeypointSegLoss, which the
         caller adds to ProposalLoss + RefinementLoss."""
         item = self.proposal(item)
+        if self.voxel_pool:
+            return self.refinement_targets()(self._voxel_stage2(item, train=True)[0])
         with torch.no_grad():
             early = self._proposals_then_keypoints(item)
         features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
@@ -468,7 +518,7 @@ class PV_RCNN(nn.Module):
         nothing is waited for."""
         if not (self._native_item(item) and self.native_tail):
             raise RuntimeError("inference_begin: frames of the device Preprocessor in eval mode without autograd")
-        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc":
+        if "keypoints" not in item and self.keypoint_sampler()[0] != "spc" and not self.voxel_pool:
             self.prefetch_keypoints(item)
         st = self._native_cnn_launch(item, slot)
         item["_head_maps"] = self.proposal_layer.native_head(st["bev_map"])
@@ -488,13 +538,16 @@ class PV_RCNN(nn.Module):
         if ready is not None:
             main.wait_event(ready)
             item["keypoints"].record_stream(main)
-        early = self._proposals_then_keypoints(item)
-        features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
-        boxes, scores, class_idx = early or self.stage1_proposals(item)
-        pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
-        deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
-        item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,
-                    pooled_features=pooled, R_reg=deltas, R_cls=conf)
+        if self.voxel_pool:
+            item, boxes, deltas, conf = self._voxel_stage2(item)
+        else:
+            early = self._proposals_then_keypoints(item)
+            features = self.point_feature_extract(item, item["_cnn_features"], item["_bev_map"])
+            boxes, scores, class_idx = early or self.stage1_proposals(item)
+            pooled = self.roi_grid_pool(boxes, item["keypoints"], features, samples)
+            deltas, conf = self.refinement_layer(item["points"], pooled, boxes)
+            item.update(keypoint_features=features, proposals=boxes, proposal_scores=scores, proposal_class=class_idx,
+                        pooled_features=pooled, R_reg=deltas, R_cls=conf)
         item["boxes_refined"], raw = self.proposal_layer.native_refine_nms(deltas, boxes, conf, finalize=False)
         slot = st["cnn"]["slot"]
         pinned = self.__dict__.setdefault("_host_count", _PlanCache())

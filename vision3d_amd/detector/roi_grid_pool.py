@@ -21,6 +21,30 @@ def yaw_rotate(local, yaw):
     return torch.stack((cos * lx - sin * ly, sin * lx + cos * ly, lz), dim=-1)
 
 
+def gridpoints(boxes, samples, torch_trig=False):
+    """boxes (b, n, 7), samples (b, n, m, 3) in the unit cube -> (b, n, m, 3): centre + Rz(yaw) (size * (samples - 0.5)).  The one
+    statement of the product both RoI poolings place their points with (RoiGridPool: random draws; VoxelRoiPool: a regular grid)."""
+    b, n = boxes.shape[:2]
+    if (boxes.is_cuda and boxes.dtype == torch.float32 and samples.dtype == torch.float32 and boxes.shape[-1] == 7
+            and not (torch.is_grad_enabled() and (boxes.requires_grad or samples.requires_grad))):
+        # the statements below in one launch (csrc/pointops.hip v3d_roi_grid_points): same values.  The yaw's cos / sin are the
+        # device library's cosf / sinf inside that launch -- on this stack bit-identical to torch.cos / torch.sin
+        # (tests/test_gpu_pointops.py::test_roi_grid_points_trig_equals_torch); torch_trig: hand torch's values in instead
+        from .. import _lib as L
+        bx, sm = boxes.contiguous(), samples.contiguous()
+        cos = sin = None
+        if torch_trig:
+            yaw = bx[..., 6]
+            cos, sin = yaw.cos().contiguous(), yaw.sin().contiguous()
+        out = torch.empty_like(sm)
+        with L.device_guard(bx.device):
+            L.check(L.lib().v3d_roi_grid_points(L.ptr(bx), L.ptr(sm), L.ptr(cos), L.ptr(sin), b * n, sm.shape[2], L.ptr(out),
+                                                L.stream_ptr()), "roi_grid_points")
+        return out
+    centre, size, yaw = boxes[..., None, 0:3], boxes[..., None, 3:6], boxes[..., 6]
+    return centre + yaw_rotate(size * (samples - 0.5), yaw)
+
+
 class RoiGridPool(nn.Module):
 
     def __init__(self, cfg):
@@ -46,24 +70,7 @@ class RoiGridPool(nn.Module):
         b, n = boxes.shape[:2]
         if samples is None:
             samples = torch.rand((b, n, self.cfg.GRIDPOOL.NUM_GRIDPOINTS, 3), device=boxes.device, generator=self.generator)
-        if (boxes.is_cuda and boxes.dtype == torch.float32 and samples.dtype == torch.float32 and boxes.shape[-1] == 7
-                and not (torch.is_grad_enabled() and (boxes.requires_grad or samples.requires_grad))):
-            # the statements below in one launch (csrc/pointops.hip v3d_roi_grid_points): same values.  The yaw's cos / sin are the
-            # device library's cosf / sinf inside that launch -- on this stack bit-identical to torch.cos / torch.sin
-            # (tests/test_gpu_pointops.py::test_roi_grid_points_trig_equals_torch); TORCH_TRIG: hand torch's values in instead
-            from .. import _lib as L
-            bx, sm = boxes.contiguous(), samples.contiguous()
-            cos = sin = None
-            if self.TORCH_TRIG:
-                yaw = bx[..., 6]
-                cos, sin = yaw.cos().contiguous(), yaw.sin().contiguous()
-            out = torch.empty_like(sm)
-            with L.device_guard(bx.device):
-                L.check(L.lib().v3d_roi_grid_points(L.ptr(bx), L.ptr(sm), L.ptr(cos), L.ptr(sin), b * n, sm.shape[2], L.ptr(out),
-                                                    L.stream_ptr()), "roi_grid_points")
-            return out
-        centre, size, yaw = boxes[..., None, 0:3], boxes[..., None, 3:6], boxes[..., 6]
-        return centre + yaw_rotate(size * (samples - 0.5), yaw)
+        return gridpoints(boxes, samples, self.TORCH_TRIG)
 
     def sample_gridpoints_torch(self, boxes, samples):
         """The reference's statements op by op (the cross-check of the fused launch in the tests)."""

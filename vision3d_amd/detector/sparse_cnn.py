@@ -164,15 +164,27 @@ class SparseCNNBase(nn.Module):
         """(B, C, D, H, W) dense volume with z folded into the channels: (B, C * D, H, W)."""
         return volume.dense().flatten(1, 2)
 
-    def forward(self, features, coordinates, batch_size):
+    def _run_stages(self, features, coordinates, batch_size, levels):
+        """The stages in turn; `levels` receives (stride, input of the stage) before each stage runs.  -> the last stage's output."""
         level = spconv.SparseConvTensor(features, coordinates.int(), self.grid_shape, batch_size)
         if self.training and torch.is_grad_enabled():
             spconv.prebuild_rulebooks(self.blocks, level)  # all host reads of the step happen here, before any conv
-        points = []
         for stride, stage in zip(self.cfg.STRIDES, self.blocks):
-            points.append(self.to_global(stride, level))
+            levels(stride, level)
             level = stage(level)
+        return level
+
+    def forward(self, features, coordinates, batch_size):
+        points = []
+        level = self._run_stages(features, coordinates, batch_size, lambda stride, lv: points.append(self.to_global(stride, lv)))
         return points, self.to_bev(level)
+
+    def forward_sparse(self, features, coordinates, batch_size):
+        """-> ([SparseConvTensor] the input of every stage: level k + 1 of cfg.VOXELPOOL.LEVELS is entry k, BEV map): the levels as the
+        backbone holds them, for the voxel RoI pooling (detector/voxel_roi_pool.py) -- `forward` without the padded point sets."""
+        levels = []
+        level = self._run_stages(features, coordinates, batch_size, lambda stride, lv: levels.append(lv))
+        return levels, self.to_bev(level)
 
 
 class SpMiddleFHD(SparseCNNBase):
