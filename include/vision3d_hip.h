@@ -164,6 +164,31 @@ int v3d_augment_frame(const float* points, int N, int C, const float* boxes, con
                       double factor, double cos_theta, double sin_theta, double theta, float* out_points, float* out_boxes,
                       int64_t* out_class_idx, void* work, size_t work_bytes, v3d_stream_t stream);
 
+/* ---- f2c: per-object ground-truth noise of B frames (two launches, no host read, no atomic decides a result, deterministic).
+ * Replaces nothing upstream -- vision3d/dataset/augmentation.py has no such class --: it is the object noise of VoxelNet section 3.1 /
+ * SECOND, defined by this repository (float64 restatement tests/object_noise_ref.py).  The frames are
+ * concatenated: points (n_points, C >= 3) f32, boxes (n_boxes, 7) f32 = (x, y, z, w, l, h, yaw), frame b owning the rows
+ * [point_offsets_host[b], point_offsets_host[b + 1]) / [box_offsets_host[b], box_offsets_host[b + 1]) -- (B + 1) i32 each, on the
+ * HOST.  The caller's draws: trans (n_boxes, T, 3) f32, rot (n_boxes, T) f32.
+ *   candidate (i, t)  centre (x_i + trans[i,t,0], y_i + trans[i,t,1]), yaw_i + rot[i,t] (one fp32 add each), size unchanged
+ *   collision         the operator of v3d_box_iou_rotated (same device function, candidate first) on (x, y, w, l, yaw_deg),
+ *                     yaw_deg = yaw * 57.29577951308232f (one fp32 multiply), > collision_iou: true geometry
+ *   selection         per frame, sequentially in box order: chosen[i] = the smallest t whose candidate collides with no box j != i of
+ *                     the frame, j < i at its already moved pose, j > i at its original pose; none: chosen[i] = -1, the box stays
+ *   out_boxes         (n_boxes, 7): the chosen candidate's x, y, yaw and z_i + trans[i,t,2]; chosen = -1: copied bit for bit
+ *   out_points        (n_points, C): a point belongs to the lowest-index box of its frame whose inside test passes -- the test of
+ *                     v3d_points_in_boxes(use_z = 1) on the ORIGINAL boxes, same bits --; with (c, s) = (cosf, sinf)(rot[i,t]) taken
+ *                     once per box and (cx, cy) the original centre, in uncontracted fp32: dx = x - cx, dy = y - cy,
+ *                     x' = ((dx * c - dy * s) + cx) + trans_x, y' = ((dx * s + dy * c) + cy) + trans_y, z' = z + trans_z; columns
+ *                     >= 3 and all other points copied, row order and count unchanged (out_points must not alias points)
+ *   chosen            (n_boxes) i32
+ * Scene points that lie where a box lands are not removed; a box may leave the grid.  Limits: at most 128 boxes per frame,
+ * 1 <= T <= 256, B <= 64 -- beyond them V3D_EUNSUPPORTED (the sizes are host data: the call can refuse).  workspace: 16-byte aligned. */
+size_t v3d_object_noise_workspace(int n_boxes, int T);
+int v3d_object_noise(const float* points, const int32_t* point_offsets_host, const float* boxes, const int32_t* box_offsets_host,
+                     int B, int C, const float* trans, const float* rot, int T, float collision_iou, float* out_points,
+                     float* out_boxes, int32_t* chosen, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+
 /* ---- f2b: the GT-sampling database cut out of a batch of annotated frames (three launches per batch, no host read).
  * Replaces DatabaseBuilder._process_item / _demean (vision3d/dataset/augmentation.py:201-243) with its PointsInCuboids call
  * (vision3d/core/geometry.py:27-48; "~10 ms for each scene" in numpy).  points (n_points, C >= 3) f32 = the frames behind each

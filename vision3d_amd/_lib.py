@@ -41,6 +41,8 @@ _SIGNATURES = {
     "v3d_augment_work_bytes": (_sz, [_i, _i, _i]),
     "v3d_augment_frame": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double,
                                _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_object_noise_workspace": (_sz, [_i, _i]),
+    "v3d_object_noise": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_database_work_bytes": (_sz, [_i, _i, _i]),
     "v3d_database_extract": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _sz, _vp]),
     "v3d_voxelize_workspace": (_sz, [_i]),

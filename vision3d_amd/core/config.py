@@ -92,8 +92,14 @@ def _defaults():
         PROPOSAL=dict(C_IN=128, TOPK=100),
         REFINEMENT=dict(MLPS=[256, 128]),
         TRAIN=dict(LR=1e-3, LAMBDA=1.0, EPOCHS=80, BATCH_SIZE=6, REFINEMENT_NUM_NEGATIVES=128),
+        # OBJECT_NOISE: per-object ground-truth noise (dataset/augmentation.py ObjectNoiseAugmentation; VoxelNet 3.1 / SECOND, not in the
+        # reference), opt-in: every box, with the points inside it, tries up to NUM_TRY poses -- translation ~ N(0, TRANSLATION_STD)
+        # (x, y, z), yaw + U(ROTATION) -- and takes the first whose BEV IoU with every other box is <= COLLISION_IOU, or stays; runs
+        # before GT sampling and the global flip / scale / rotation
         AUG=dict(GLOBAL_SCALE=[0.95, 1.05], GLOBAL_ROTATION=[-math.pi / 4, math.pi / 4], FLIP_HORIZONTAL=True,
-                 DATABASE_SAMPLE=True, NUM_SAMPLE_OBJECTS=[15, 10, 10], MIN_NUM_SAMPLE_PTS=8),
+                 DATABASE_SAMPLE=True, NUM_SAMPLE_OBJECTS=[15, 10, 10], MIN_NUM_SAMPLE_PTS=8,
+                 OBJECT_NOISE=dict(ENABLED=False, NUM_TRY=100, TRANSLATION_STD=[1.0, 1.0, 0.5], ROTATION=[-0.7853981634, 0.7853981634],
+                                   COLLISION_IOU=1e-2)),
     ))
 
 

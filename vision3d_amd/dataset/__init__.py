@@ -8,6 +8,7 @@ import importlib
 _EXPORTS = {
     "ChainedAugmentation": "augmentation", "SampleAugmentation": "augmentation", "FlipAugmentation": "augmentation",
     "ScaleAugmentation": "augmentation", "RotateAugmentation": "augmentation", "SampleDatabase": "augmentation",
+    "ObjectNoiseAugmentation": "augmentation",
     "read_points": "kitti", "read_labels": "kitti", "read_calib": "kitti", "boxes_in_lidar_frame": "kitti",
     "crop_to_camera_view": "kitti", "load_frame": "kitti", "Calib": "kitti", "Labels": "kitti",
     "DatabaseBuilder": "database", "build_annotations": "database", "extract_objects": "database", "box_prep": "database",

@@ -22,6 +22,10 @@ Two forms of the same computation.  The classes `SampleAugmentation` / `FlipAugm
 result, so all of them are made first -- same calls, same order -- and the frame is two launches (collision filter + boxes; point
 filter + ordered compaction + paste + transform) and one host read (the ragged sizes).  `ChainedAugmentation(fused=False)` keeps
 the class-by-class chain; the two are compared bit for bit in tests/test_gpu_augmentation.py.
+
+Per-object noise (`ObjectNoiseAugmentation`, cfg.AUG.OBJECT_NOISE, off by default) is not in the reference: every ground-truth box
+moves, with the points inside it, by its own random translation and yaw, retried until it collides with no other box (VoxelNet 3.1 /
+SECOND; the definition is DESIGN.md section 7).  Enabled, `ChainedAugmentation` runs it first, on the scene's own boxes and points.
 """
 import os
 import pickle
@@ -30,7 +34,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..core.geometry import PointsNotInRectangles
+from ..core.geometry import PointsNotInRectangles, points_in_boxes_mask
 from ..ops import box_iou_rotated
 
 BEV = [0, 1, 3, 4, 6]
@@ -200,24 +204,163 @@ class SampleAugmentation(Augmentation):
         return points, boxes, class_idx
 
 
+RAD2DEG = 57.29577951308232  # yaw -> the degrees box_iou_rotated reads: object noise tests TRUE geometry (no call site upstream to match)
+
+
+class ObjectNoiseAugmentation(Augmentation):
+    """Per-object ground-truth noise (VoxelNet 3.1 / SECOND; nothing upstream -- the definition is DESIGN.md section 7, restated in
+    float64 by tests/object_noise_ref.py).  Box i tries the poses (xy_i + trans[i, t, :2], yaw_i + rot[i, t]), t = 0 .. NUM_TRY - 1, and
+    takes the first that collides (BEV IoU > COLLISION_IOU) with no other box -- boxes before it at their moved pose, boxes after it at
+    their original one -- or stays; the points strictly inside the original box (lowest box index first) rotate about its centre and
+    translate with it, z included.  Scene points where a box lands are not removed; a box may leave GRID_BOUNDS.
+
+        noise = ObjectNoiseAugmentation(cfg, rng)
+        points, boxes = noise(points, boxes)             # numpy in -> numpy out, cuda in -> cuda out
+        noise.last_chosen                                # (n,) int32 on the device: the try each box took, -1 = stayed
+
+    Native: `v3d_object_noise` (csrc/object_noise.hip), two launches for any number of frames (`batch`), no host read.  Beyond its limits
+    (128 boxes per frame, 256 tries, 64 frames) `torch_statement` -- the same definition op by op -- takes over."""
+
+    MAX_BOXES, MAX_TRY, MAX_FRAMES = 128, 256, 64
+
+    def __init__(self, cfg, rng=None):
+        super().__init__(cfg, rng)
+        node = cfg.AUG.get("OBJECT_NOISE") or {}
+        self.num_try = int(node.get("NUM_TRY", 100))
+        if self.num_try < 1:
+            raise ValueError(f"cfg.AUG.OBJECT_NOISE.NUM_TRY must be at least 1, got {self.num_try}")
+        self.translation_std = [float(v) for v in node.get("TRANSLATION_STD", [1.0, 1.0, 0.5])]
+        self.rotation = [float(v) for v in node.get("ROTATION", [-0.7853981634, 0.7853981634])]
+        self.collision_iou = float(np.float32(node.get("COLLISION_IOU", 1e-2)))
+        self.last_chosen = None
+
+    def draw(self, n):
+        """(trans (n, T, 3), rot (n, T)) float32 from `self.rng`: normal(0, TRANSLATION_STD), then uniform(ROTATION)."""
+        T = self.num_try
+        trans = self.rng.normal(0, self.translation_std, (n, T, 3))
+        rot = self.rng.uniform(self.rotation[0], self.rotation[1], (n, T))
+        return trans.astype(np.float32), rot.astype(np.float32)
+
+    def native_ok(self, sizes, T):
+        return len(sizes) <= self.MAX_FRAMES and 1 <= T <= self.MAX_TRY and all(n <= self.MAX_BOXES for n in sizes)
+
+    def torch_statement(self, points, boxes, trans, rot):
+        """The definition op by op on device tensors (a Python loop over the boxes, no host read): -> points, boxes, chosen (n,) int32.
+        `box_iou_rotated` is the predicate (candidates = rows), `points_in_boxes_mask` (v3d_points_in_boxes, use_z) the membership."""
+        n, T = rot.shape
+        dev = boxes.device
+        cur = boxes.clone()  # box j at its current pose: moved for j < i, original for j > i
+        chosen = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        tries = torch.arange(T, device=dev)
+        for i in range(n):
+            cand = cur[i].repeat(T, 1)
+            cand[:, 0] = boxes[i, 0] + trans[i, :, 0]
+            cand[:, 1] = boxes[i, 1] + trans[i, :, 1]
+            cand[:, 2] = boxes[i, 2] + trans[i, :, 2]
+            cand[:, 6] = boxes[i, 6] + rot[i]
+            others = torch.cat((cur[:i], cur[i + 1:]))
+            hit = box_iou_rotated(self._bev(cand), self._bev(others)) > self.collision_iou  # (T, n - 1)
+            first = torch.where(hit.any(1), T, tries).min()  # T: every try collides
+            found = first < T
+            chosen[i] = torch.where(found, first, -1).to(torch.int32)
+            cur[i] = torch.where(found, cand[first.clamp(max=T - 1)], cur[i])
+        if points.shape[0] == 0 or n == 0:
+            return points.clone(), cur, chosen
+        inside = points_in_boxes_mask(points, boxes, True)  # (N, n) on the ORIGINAL boxes
+        owner = torch.where(inside, torch.arange(n, device=dev), n).min(1).values  # lowest box index; n: in no box
+        own = owner.clamp(max=n - 1)
+        t = chosen.long().clamp(min=0)
+        moved = (owner < n) & (chosen[own] >= 0)
+        pick = torch.arange(n, device=dev)
+        angle, shift = rot[pick, t], trans[pick, t]  # of the chosen try, per box
+        c, s = torch.cos(angle)[own], torch.sin(angle)[own]
+        cx, cy = boxes[own, 0], boxes[own, 1]
+        dx, dy = points[:, 0] - cx, points[:, 1] - cy
+        x = ((dx * c - dy * s) + cx) + shift[own, 0]
+        y = ((dx * s + dy * c) + cy) + shift[own, 1]
+        z = points[:, 2] + shift[own, 2]
+        xyz = torch.where(moved[:, None], torch.stack((x, y, z), 1), points[:, :3])
+        return torch.cat((xyz, points[:, 3:]), 1), cur, chosen
+
+    @staticmethod
+    def _bev(boxes):
+        return torch.stack((boxes[:, 0], boxes[:, 1], boxes[:, 3], boxes[:, 4], boxes[:, 6] * RAD2DEG), 1)
+
+    def batch(self, list_of_points, list_of_boxes, draws=None):
+        """B frames in ONE native call (two launches) -> (list of points, list of boxes); `last_chosen`: the frames' boxes behind each
+        other.  draws: a list of (trans, rot) per frame, default `self.draw(n)` frame by frame."""
+        as_numpy = [isinstance(p, np.ndarray) for p in list_of_points]
+        points = [_to_device(p, torch.float32).contiguous() for p in list_of_points]
+        boxes = [_to_device(b, torch.float32).reshape(-1, 7).contiguous() for b in list_of_boxes]
+        if draws is None:
+            draws = [self.draw(b.shape[0]) for b in boxes]
+        B = len(points)
+        if B == 0:
+            return [], []
+        dev = points[0].device
+        L.require_gpu("object_noise", *points, *boxes)
+        trans = [_to_device(np.asarray(d[0], np.float32) if not torch.is_tensor(d[0]) else d[0], torch.float32) for d in draws]
+        rot = [_to_device(np.asarray(d[1], np.float32) if not torch.is_tensor(d[1]) else d[1], torch.float32) for d in draws]
+        sizes, T, C = [b.shape[0] for b in boxes], self.num_try, points[0].shape[1]
+        for b, tr, ro in zip(boxes, trans, rot):
+            if tuple(tr.shape) != (b.shape[0], T, 3) or tuple(ro.shape) != (b.shape[0], T):
+                raise RuntimeError(f"object_noise: draws must be (n, {T}, 3) and (n, {T}) per frame, got {tuple(tr.shape)} and {tuple(ro.shape)}")
+        if any(p.shape[1] != C for p in points):
+            raise RuntimeError("object_noise: the frames of a batch must have the same number of point columns")
+        if not self.native_ok(sizes, T):
+            out = [self.torch_statement(p, b, tr, ro) for p, b, tr, ro in zip(points, boxes, trans, rot)]
+            out_p, out_b = [o[0] for o in out], [o[1] for o in out]
+            self.last_chosen = torch.cat([o[2] for o in out])
+        else:
+            cat = (lambda ts: ts[0] if B == 1 else torch.cat(ts))
+            all_p, all_b = cat(points), cat(boxes)
+            all_t, all_r = cat(trans).contiguous(), cat(rot).contiguous()
+            p_off = np.concatenate([[0], np.cumsum([p.shape[0] for p in points])])
+            b_off = np.concatenate([[0], np.cumsum(sizes)])
+            res_p, res_b = torch.empty_like(all_p), torch.empty_like(all_b)
+            chosen = torch.empty(int(b_off[-1]), dtype=torch.int32, device=dev)
+            with L.device_guard(dev):
+                work_bytes = int(L.lib().v3d_object_noise_workspace(int(b_off[-1]), T))
+                work = L.workspace(work_bytes, dev)
+                L.check(L.lib().v3d_object_noise(L.ptr(all_p), L.host_i32(p_off), L.ptr(all_b), L.host_i32(b_off), B, C, L.ptr(all_t),
+                                                 L.ptr(all_r), T, self.collision_iou, L.ptr(res_p), L.ptr(res_b), L.ptr(chosen),
+                                                 L.ptr(work), work_bytes, L.stream_ptr()), "object_noise")
+            out_p = [res_p[p_off[b]:p_off[b + 1]] for b in range(B)]
+            out_b = [res_b[b_off[b]:b_off[b + 1]] for b in range(B)]
+            self.last_chosen = chosen
+        out_p = [p.cpu().numpy() if a else p for p, a in zip(out_p, as_numpy)]
+        out_b = [b.cpu().numpy() if a else b for b, a in zip(out_b, as_numpy)]
+        return out_p, out_b
+
+    def __call__(self, points, boxes, draws=None):
+        out_p, out_b = self.batch([points], [boxes], None if draws is None else [draws])
+        return out_p[0], out_b[0]
+
+
 SAMPLE_RECORD = np.dtype([("box_row", np.int32), ("pt_start", np.int32), ("pt_len", np.int32), ("cls", np.int32),
                           ("px", np.float64), ("py", np.float64)])  # AugSample of csrc/augment.hip
 
 
 class ChainedAugmentation(Augmentation):
     """sample -> flip -> scale -> rotate (augmentation.py:31-48).  numpy in -> numpy out (float32, the dtype the reference's
-    dataset casts to); cuda tensors in -> cuda tensors out.  fused (default): the frame through `v3d_augment_frame`."""
+    dataset casts to); cuda tensors in -> cuda tensors out.  fused (default): the frame through `v3d_augment_frame`.
+    cfg.AUG.OBJECT_NOISE.ENABLED (not in the reference, off by default): per-object noise runs FIRST, on the scene's own boxes and
+    points, its draws taken from the shared `rng` before the chain's; disabled, not one extra draw is made."""
 
     def __init__(self, cfg, database=None, rng=None, fused=True):
         super().__init__(cfg, rng)
         self.fused = fused
         self.sample = SampleAugmentation(cfg, database, self.rng) if cfg.AUG.DATABASE_SAMPLE else None
         self.augmentations = [FlipAugmentation(cfg, self.rng), ScaleAugmentation(cfg, self.rng), RotateAugmentation(cfg, self.rng)]
+        noise = cfg.AUG.get("OBJECT_NOISE")  # (a config written before the key existed: disabled)
+        self.object_noise = ObjectNoiseAugmentation(cfg, self.rng) if noise and noise.get("ENABLED") else None
 
     def __call__(self, points, boxes, class_idx):
         as_numpy = isinstance(points, np.ndarray)
         points, boxes = _to_device(points, torch.float32), _to_device(boxes, torch.float32)
         class_idx = _to_device(np.asarray(class_idx, np.int64) if as_numpy else class_idx, torch.int64)
+        if self.object_noise is not None:
+            points, boxes = self.object_noise(points, boxes)
         if self.fused:
             points, boxes, class_idx = self.fused_frame(points, boxes, class_idx)
         else:
