@@ -705,6 +705,43 @@ int v3d_voxel_pool_pair(const float* P, int ldp, const int32_t* coords, int cap,
                         int nsample, const float* scale_host, const float* offset_host, int K1, const float* wx, const float* b1,
                         const float* W, const float* bias, int Nout, float* out, int ldo, v3d_stream_t stream);
 
+/* ---- Anchor-free centre heatmap head (CenterPoint, arXiv 2006.11275; stage 1 of PV-RCNN++; opt-in, cfg.CENTERHEAD; no upstream
+ * counterpart).  The definition is this repository's (detector/center_head.py, tests/center_head_ref.py, csrc/center_head.hip).
+ * Fused head maps (B, n_cls + 8, H, W) f32: channels [0, n_cls) heat logits, n_cls + j for j = 0..7 = dx, dy, z, log w, log l, log h,
+ * sin yaw, cos yaw, raw.  geom_host = (px, py, x_lo, y_lo) as doubles: metres per cell and the grid origin.  Common limits: B <= 64,
+ * n_cls <= 8, H * W <= 2^24, at most 128 objects per frame, topk <= 1024 -- beyond them V3D_EUNSUPPORTED before any launch (the sizes
+ * are host data).  fp32, the caller's stream, no host read, bit-repeatable; no atomic decides a value.
+ * Targets (ONE launch; every cell of heat is written, no clear needed): boxes (n, 7) f32 = (x, y, z, w, l, h, yaw) and classes (n) i32
+ * of all frames flat, frame b owning rows [box_offsets_host[b], box_offsets_host[b + 1]).  fx = (x - x_lo) / px, fy likewise (fp32),
+ * (ix, iy) = floor; an object is live when it lies inside the map, 0 <= class < n_cls and w, l, h are finite and > 0.  Radius r =
+ * max(min_radius, int(min of the three CornerNet roots at min_overlap of (w / px, l / py))) in double, sigma = (2 r + 1) / 6.
+ *   heat (B, n_cls, H, W) f32   max over the frame's live objects of the class whose (2 r + 1)^2 window covers the cell of
+ *                               exp(-(du^2 + dv^2) / (2 sigma^2)); exactly 1 at a centre, exactly 0 outside every window
+ *   ind / mask / cls (B, 128)   i32 iy * W + ix (-1: not live) / u8 live / i32 the given class (0 in the padding rows)
+ *   reg (B, 128, 8) f32         (fx - ix, fy - iy, z, log w, log l, log h, sin yaw, cos yaw); zeros where not live */
+int v3d_center_targets(const float* boxes, const int32_t* classes, const int32_t* box_offsets_host, int B, int n_cls, int H, int W,
+                       const double* geom_host, double min_overlap, int min_radius, float* heat, int32_t* ind, uint8_t* mask,
+                       int32_t* cls, float* reg, v3d_stream_t stream);
+/* CenterLoss and its gradient with respect to the fused maps (three launches).  N = max(#mask, 1) over the batch, p = sigmoid(logit):
+ * hm = sum over the heat cells of [heat == 1: -(1 - p)^alpha log p; else: -(1 - heat)^beta p^alpha log(1 - p)] / N (log p =
+ * -softplus(-x), log(1 - p) = -softplus(x), no clamp); reg = sum over the masked objects and j of code_weights_host[j] * |map[n_cls + j]
+ * at the object's cell - reg[j]| / N.  losses[3] = {hm, reg, N}; dmaps (the maps' shape) = d hm in the heat channels, d reg in the box
+ * channels: objects of one cell add up in object order, every other box cell is an exact zero, sign(0) = 0.  _scale multiplies the two
+ * channel groups with the upstream gradients (device scalars).  Sums in double in a fixed order.  workspace: 8-byte aligned. */
+size_t v3d_center_loss_workspace(void);
+int v3d_center_loss_fwd_bwd(const float* maps, const float* heat, const int32_t* ind, const uint8_t* mask, const float* reg, int B,
+                            int n_cls, int H, int W, float alpha, float beta, const float* code_weights_host, float* losses,
+                            float* dmaps, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+int v3d_center_loss_scale(float* dmaps, int B, int n_cls, int H, int W, const float* g_hm, const float* g_reg, v3d_stream_t stream);
+/* Peak decode (two launches, capturable).  A cell is a peak of its (frame, class) channel when its logit is >= that of each of its up
+ * to eight in-map neighbours (a NaN logit is never a peak); per (frame, class) the topk peaks of highest logit, ties to the lower
+ * cell, become boxes (B, n_cls * topk, 7) = ((ix + dx) px + x_lo, (iy + dy) py + y_lo, z, exp(log w, log l, log h), atan2(sin, cos)),
+ * fp32 and uncontracted, and scores (B, n_cls * topk) = sigmoid(logit), group-major, score descending inside a group -- the layout of
+ * v3d_proposals_topk.  A group with fewer peaks ends in slots of score 0 and an all-zero box.  workspace: 8-byte aligned. */
+size_t v3d_center_decode_workspace(int B, int n_cls, int H, int W);
+int v3d_center_decode(const float* maps, int B, int n_cls, int H, int W, const double* geom_host, int topk, float* boxes,
+                      float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.
  * Every layer must be conv + BatchNorm1d (training mode: batch statistics) [+ ReLU] with a power-of-two Cout in [4, 256].

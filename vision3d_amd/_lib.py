@@ -129,6 +129,12 @@ _SIGNATURES = {
     "v3d_voxel_query_workspace": (_sz, [_i]),
     "v3d_voxel_query": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "v3d_voxel_pool_pair": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "v3d_center_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "v3d_center_loss_workspace": (_sz, []),
+    "v3d_center_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_center_loss_scale": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "v3d_center_decode_workspace": (_sz, [_i, _i, _i, _i]),
+    "v3d_center_decode": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "v3d_conv2d_weight_image_bytes": (_sz, [_i, _i, _i]),
     "v3d_densify_nhwc_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "v3d_split_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -8,6 +8,7 @@ _EXPORTS = {
     "Preprocessor": "preprocess", "TrainPreprocessor": "preprocess",
     "ProposalTargetAssigner": "proposal_targets",
     "RefinementTargetAssigner": "refinement_targets",
+    "CenterTargetAssigner": "center_targets",
 }
 __all__ = sorted(_EXPORTS)
 

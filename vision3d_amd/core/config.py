@@ -77,6 +77,13 @@ def _defaults():
         # else the channel count per level (levels that do not come from this backbone); replaces keypoints, set abstraction, BEV lookup and RoI-grid pooling
         VOXELPOOL=dict(ENABLED=False, GRID=6, LEVELS=[2, 3, 4], RANGE=[[2, 2, 2], [2, 2, 2], [1, 2, 2]], RADIUS=[0.4, 0.8, 1.6],
                        NSAMPLE=16, MLPS=[[32, 32], [32, 32], [32, 32]], MLPS_REDUCTION=None, LEVEL_CHANNELS=None),
+        # anchor-free centre heatmap head for SECOND (detector/center_head.py, core/center_targets.py), opt-in: a class heat map + eight raw
+        # regression channels (dx, dy, z, log w, log l, log h, sin yaw, cos yaw) per BEV cell in place of the anchor head; targets are
+        # Gaussian splats of CornerNet radius (MIN_OVERLAP, at least MIN_RADIUS cells), the loss the penalty-reduced focal loss
+        # (FOCAL_ALPHA, FOCAL_BETA) + L1 weighted by CODE_WEIGHTS, inference the PROPOSAL.TOPK heat peaks per (frame, class) through
+        # rotated NMS at NMS_IOU and the score_thresh of ANCHORS
+        CENTERHEAD=dict(ENABLED=False, MIN_OVERLAP=0.1, MIN_RADIUS=2, FOCAL_ALPHA=2.0, FOCAL_BETA=4.0, CODE_WEIGHTS=[1.0] * 8,
+                        NMS_IOU=0.01),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",

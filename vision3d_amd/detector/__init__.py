@@ -12,6 +12,8 @@ _EXPORTS = {
     "KeypointWeighting": "keypoint_weighting",
     "KeypointSegLoss": "keypoint_weighting",
     "VoxelRoiPool": "voxel_roi_pool",
+    "CenterHead": "center_head",
+    "CenterLoss": "center_head",
 }
 __all__ = sorted(_EXPORTS)
 

@@ -18,6 +18,8 @@ def bucket_points(n, quantum=2048):
 class GraphedSecond(object):
 
     def __init__(self, model, anchors, frame_sizes, slot=0):
+        from .center_head import refuse_centerhead
+        refuse_centerhead(model.cfg, "the captured-graph runner")
         self.model, self.anchors = model, anchors
         self.frame_sizes = [int(n) for n in frame_sizes]
         self.offsets = [0]

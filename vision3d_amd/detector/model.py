@@ -42,6 +42,8 @@ class PV_RCNN(nn.Module):
 
     def __init__(self, cfg):
         super().__init__()
+        from .center_head import refuse_centerhead
+        refuse_centerhead(cfg, "PV_RCNN")
         self.cfg = cfg
         self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
         if self.voxel_pool:

@@ -167,7 +167,9 @@ class Second(nn.Module):
         for k, st, pd in ((3, 2, 1), (3, 2, 1), (3, 2, 0), (3, 2, 0)):
             z = (z + 2 * pd - k) // st + 1
         self.rpn = RPN(C_in=64 * z)
-        self.head = ProposalLayer(cfg)
+        from .center_head import CenterHead, centerhead_enabled
+        self.center_head = centerhead_enabled(cfg)  # cfg.CENTERHEAD (opt-in): heat map + box regression in place of the anchor head
+        self.head = CenterHead(cfg) if self.center_head else ProposalLayer(cfg)
         self.cfg = cfg
         # "the parameters may have changed" counter for the captured-graph runners (detector/graph.py): bumped by load_state_dict, by
         # every train() / eval() switch (an optimizer step happens in training mode) and by notify_weights_changed() (in-place edits
@@ -335,9 +337,9 @@ class Second(nn.Module):
 
             def run():
                 maps, state["plan"] = self._head_maps_from_item(item)
-                return self.head.inference_native(maps, item["anchors"], overflow_flag=state["plan"].overflow_any())
+                return self.head.inference_native(maps, None if self.center_head else item["anchors"], overflow_flag=state["plan"].overflow_any())
             return self._with_recalibration(run, lambda: state["plan"])
-        return self.head.inference(self.feature_extract(item), item["anchors"])
+        return self.head.inference(self.feature_extract(item), None if self.center_head else item["anchors"])
 
     # ---- fused path: raw device points in, proposals out (voxelizer + sparse backbone in one native call)
     def backbone_plan(self, max_batch, max_points, slot=0):
@@ -419,14 +421,18 @@ class Second(nn.Module):
         per frame).  Returns `run(clouds) -> (boxes, batch_idx, class_idx, scores)`; each call copies the clouds
         into a static buffer, replays the graph (a single launch for ~150 kernels) and does the final
         variable-length selection.  Re-capture (call again) when the geometry changes."""
+        from .center_head import refuse_centerhead
         from .graph import GraphedSecond
+        refuse_centerhead(self.cfg, "Second.graphed_inference")
         return GraphedSecond(self, anchors, frame_sizes)
 
     def pipelined_inference(self, anchors, frame_sizes, depth=2, autotune=False):
         """Throughput mode: `depth` captured graphs on `depth` streams, frame i+1 is submitted before frame i's result
         is collected (see detector/graph.py:PipelinedSecond).  `run.submit(clouds)`, `run.collect()`.
         autotune: `depth` is the maximum; streams and depth are picked by measurement on the first frame."""
+        from .center_head import refuse_centerhead
         from .graph import PipelinedSecond
+        refuse_centerhead(self.cfg, "Second.pipelined_inference")
         return PipelinedSecond(self, anchors, frame_sizes, depth, autotune)
 
     def inference_points(self, clouds, anchors, dense="mfma", proposals="native"):
@@ -445,5 +451,8 @@ class Second(nn.Module):
                 maps = self.dense_plan().forward(hi, lo, occ=occ, in_entry=plan.bev_entry(), range_flag=plan.overflow_any())
                 return self.head.inference_native(maps, anchors, overflow_flag=plan.overflow_any())
             return self._with_recalibration(run, lambda: plan)
+        if self.center_head:
+            raise ValueError("inference_points: cfg.CENTERHEAD.ENABLED has one proposal stage (proposals='native'; CenterHead.decode_torch "
+                             "is its op-by-op statement)")
         cls_map, reg_map = self.head_maps_from_points(clouds)
         return self.head.inference_from_maps(cls_map, reg_map, anchors)
