@@ -705,6 +705,31 @@ int v3d_voxel_pool_pair(const float* P, int ldp, const int32_t* coords, int cap,
                         int nsample, const float* scale_host, const float* offset_host, int K1, const float* wx, const float* b1,
                         const float* W, const float* bias, int Nout, float* out, int ldo, v3d_stream_t stream);
 
+/* ---- VectorPool aggregation (PV-RCNN++, arXiv 2102.00463; opt-in, cfg.VECTORPOOL; no upstream counterpart).  The definition is this
+ * repository's (detector/vector_pool.py, tests/vector_pool_ref.py, csrc/vector_pool.hip).  xyz (B, N, 3) f32 support points, new_xyz
+ * (B, M, 3) f32 queries, nv = vx * vy * vz sub-voxels; sub-voxel v = (i * vy + j) * vz + k has the centre c = q + off_v (one fp32 add per
+ * coordinate), off_v = (((2 i + 1) / vx - 1) R, ((2 j + 1) / vy - 1) R, ((2 k + 1) / vz - 1) R) computed in double and rounded once.
+ * fp32, the caller's stream, no host read, bit-repeatable; no atomic decides a result.  Limits: vx, vy, vz <= 3, B <= 64, N <= 2^20,
+ * B * N <= 2^24, B * M * nv <= 2^22, Cr <= 32, CL in {16, 32} -- beyond them V3D_EUNSUPPORTED before any launch.
+ * Query: per centre the three nearest rows of the query's own frame with d^2 = (dx dx + dy dy) + dz dz < R^2 (strict, fp32, not
+ * contracted, dx = p.x - c.x), in ascending (d^2, row index) order; a row whose coordinates are bit-equal to those of a chosen one is
+ * passed over.  idx (B * M * nv, 3) i32 frame-local rows (-1: missing), w (B * M * nv, 3) f32: u_k = 1 / (sqrtf(d^2_k) + 1e-8f),
+ * w_k = u_k / ((u_1 + u_2) + u_3) over the rows found, 0 for the missing ones.  The support rows are binned into an (x, y) cell grid
+ * in the workspace (v3d_vector_pool_query_workspace(B, N) bytes, 16-byte aligned, rebuilt by every call). */
+size_t v3d_vector_pool_query_workspace(int B, int N);
+int v3d_vector_pool_query(const float* xyz, const float* new_xyz, int B, int N, int M, int vx, int vy, int vz, float radius,
+                          int32_t* idx, float* w, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+/* Reduced features: out[n * Cr + j] = sum over m (ascending) of feat[n * ldf + m * Cr + j], m < C / Cr (C % Cr == 0). */
+int v3d_vector_pool_reduce(const float* feat, int ldf, int rows, int C, int Cr, float* out, v3d_stream_t stream);
+/* Gather, interpolation, offset columns, the sub-voxel's own linear layer, shift and ReLU in one launch.  fr (B * N, ldf) reduced
+ * features, idx / w from the query.  Row of (query, v): [sum_k w_k fr[idx_k] (fmaf chain, k ascending) | c - p_1 | c - p_2 | c - p_3],
+ * the columns of a missing neighbour zero;  out[row * ldo + v * CL + j] = relu(sum_i row[i] * W_local[(v * (Cr + 9) + i) * CL + j] +
+ * shift[v * CL + j]) (fmaf chain, i ascending; eval BatchNorm folded in by the caller: its scale into W_local, the rest into shift).
+ * out is a column block of the caller's (B * M, ldo) matrix, other columns untouched. */
+int v3d_vector_pool_embed(const float* fr, int ldf, const float* xyz, const float* new_xyz, const int32_t* idx, const float* w, int B,
+                          int N, int M, int vx, int vy, int vz, float radius, int Cr, int CL, const float* W_local, const float* shift,
+                          float* out, int ldo, v3d_stream_t stream);
+
 /* ---- Anchor-free centre heatmap head (CenterPoint, arXiv 2006.11275; stage 1 of PV-RCNN++; opt-in, cfg.CENTERHEAD; no upstream
  * counterpart).  The definition is this repository's (detector/center_head.py, tests/center_head_ref.py, csrc/center_head.hip).
  * Fused head maps (B, n_cls + 8, H, W) f32: channels [0, n_cls) heat logits, n_cls + j for j = 0..7 = dx, dy, z, log w, log l, log h,

@@ -129,6 +129,10 @@ _SIGNATURES = {
     "v3d_voxel_query_workspace": (_sz, [_i]),
     "v3d_voxel_query": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     "v3d_voxel_pool_pair": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "v3d_vector_pool_query_workspace": (_sz, [_i, _i]),
+    "v3d_vector_pool_query": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_vector_pool_reduce": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "v3d_vector_pool_embed": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "v3d_center_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_center_loss_workspace": (_sz, []),
     "v3d_center_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),

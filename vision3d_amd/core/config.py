@@ -77,6 +77,19 @@ def _defaults():
         # else the channel count per level (levels that do not come from this backbone); replaces keypoints, set abstraction, BEV lookup and RoI-grid pooling
         VOXELPOOL=dict(ENABLED=False, GRID=6, LEVELS=[2, 3, 4], RANGE=[[2, 2, 2], [2, 2, 2], [1, 2, 2]], RADIUS=[0.4, 0.8, 1.6],
                        NSAMPLE=16, MLPS=[[32, 32], [32, 32], [32, 32]], MLPS_REDUCTION=None, LEVEL_CHANNELS=None),
+        # VectorPool aggregation of PV-RCNN++ (detector/vector_pool.py), opt-in: replaces the set-abstraction modules of the keypoint
+        # feature extraction (PSA: one entry per feature source -- raw points, then the four CNN levels) and of RoI-grid pooling
+        # (GRIDPOOL).  REDUCED: channels after the grouped sum (must divide the source's channel count), LOCAL: width of every
+        # sub-voxel's own linear layer, GROUPS: VOXELS [vx, vy, vz] sub-voxels, the radius (PSA: RADIUS_SCALE times the source's larger
+        # cfg.PSA.RADII entry, or an explicit RADIUS; GRIDPOOL: RADIUS in metres) and the group's MLP widths POST; MSG_POST: widths behind
+        # the concatenated groups -- the defaults end in the widths of the set-abstraction modules (32, 32, 64, 128, 128 and 192), so the
+        # keypoint features stay 512 wide and NUM_GRIDPOINTS * MSG_POST[-1] = GRIDPOOL.MLPS_REDUCTION[0]; refused together with VOXELPOOL
+        VECTORPOOL=dict(ENABLED=False,
+                        PSA=dict(REDUCED=[1, 4, 16, 32, 32], LOCAL=32, MSG_POST=[[32], [32], [64], [128], [128]],
+                                 GROUPS=[dict(VOXELS=[2, 2, 2], RADIUS_SCALE=0.5, POST=[32, 32]),
+                                         dict(VOXELS=[3, 3, 3], RADIUS_SCALE=1.0, POST=[32, 32])]),
+                        GRIDPOOL=dict(REDUCED=32, LOCAL=32, MSG_POST=[192],
+                                      GROUPS=[dict(VOXELS=[3, 3, 3], RADIUS=0.8, POST=[64, 64]), dict(VOXELS=[3, 3, 3], RADIUS=1.6, POST=[64, 64])])),
         # anchor-free centre heatmap head for SECOND (detector/center_head.py, core/center_targets.py), opt-in: a class heat map + eight raw
         # regression channels (dx, dy, z, log w, log l, log h, sin yaw, cos yaw) per BEV cell in place of the anchor head; targets are
         # Gaussian splats of CornerNet radius (MIN_OVERLAP, at least MIN_RADIUS cells), the loss the penalty-reduced focal loss

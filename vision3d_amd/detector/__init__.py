@@ -12,6 +12,7 @@ _EXPORTS = {
     "KeypointWeighting": "keypoint_weighting",
     "KeypointSegLoss": "keypoint_weighting",
     "VoxelRoiPool": "voxel_roi_pool",
+    "VectorPoolAggregationMSG": "vector_pool",
     "CenterHead": "center_head",
     "CenterLoss": "center_head",
 }

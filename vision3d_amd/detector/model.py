@@ -10,6 +10,9 @@ Data flow of the pieces that exist upstream (its `forward` raises: stage 2 was n
     [raw points, level 0..3] --set abstraction around the keypoints--> per-keypoint features, + bilinear BEV lookup
     BEV map --ProposalLayer--> (P_cls, P_reg)
 
+With cfg.VECTORPOOL.ENABLED (opt-in) `pnets` and `roi_grid_pool.pnet` are VectorPool aggregation modules (detector/vector_pool.py)
+instead of set abstraction; the data flow is the same.
+
 With cfg.VOXELPOOL.ENABLED (opt-in) stage 2 is fed without keypoints: the RoI grid points pool the sparse CNN's own levels
 (detector/voxel_roi_pool.py), the keypoint sampler, the set abstraction, the BEV lookup and RoI-grid pooling are not built.
 
@@ -25,7 +28,7 @@ from torch import nn
 
 from ..pointnet2 import pointnet2_utils as pn2
 from ..pointnet2.pointnet2_modules import PointnetSAModuleMSG
-from . import keypoint_weighting, layers, proposal, refinement, roi_grid_pool, sparse_cnn, voxel_roi_pool
+from . import keypoint_weighting, layers, proposal, refinement, roi_grid_pool, sparse_cnn, vector_pool, voxel_roi_pool
 
 
 from ..runtime import PlanCache as _PlanCache  # (a dict a deep copy of the model starts empty: events, pinned words, device clones)
@@ -46,6 +49,8 @@ class PV_RCNN(nn.Module):
         refuse_centerhead(cfg, "PV_RCNN")
         self.cfg = cfg
         self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
+        if self.voxel_pool and vector_pool.vectorpool_config(cfg)["ENABLED"]:
+            raise ValueError("cfg.VECTORPOOL.ENABLED with cfg.VOXELPOOL.ENABLED: voxel RoI pooling builds no point nets to replace")
         if self.voxel_pool:
             self._init_voxel_pool(cfg)
             return
@@ -72,7 +77,11 @@ class PV_RCNN(nn.Module):
         self.refinement_layer = refinement.RefinementLayer(cfg)
 
     def build_pointnets(self, cfg):
-        """One multi-scale set-abstraction module per feature source (raw points, then the CNN levels)."""
+        """One multi-scale set-abstraction module per feature source (raw points, then the CNN levels); with cfg.VECTORPOOL.ENABLED
+        one VectorPool aggregation module each instead (detector/vector_pool.py: same call surface, never part of the fused
+        extraction -- its `_fusable` answers False, the op-by-op branch carries it)."""
+        if vector_pool.vectorpool_config(cfg)["ENABLED"]:
+            return vector_pool.build_keypoint_modules(cfg)
         return nn.Sequential(*(_set_abstraction(radii, mlps, cfg.SAMPLES_PN)
                                for radii, mlps in zip(cfg.PSA.RADII, cfg.PSA.MLPS)))
 

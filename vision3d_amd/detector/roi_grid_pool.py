@@ -52,8 +52,12 @@ class RoiGridPool(nn.Module):
         self.cfg = cfg
         grid = cfg.GRIDPOOL
         # the SA module appends 3 to the first channel count in place: give it a private copy of the spec
-        self.pnet = PointnetSAModuleMSG(npoint=-1, radii=grid.RADII_PN, nsamples=cfg.SAMPLES_PN,
-                                        mlps=copy.deepcopy(grid.MLPS_PN), use_xyz=True)
+        from . import vector_pool
+        if vector_pool.vectorpool_config(cfg)["ENABLED"]:  # opt-in: VectorPool aggregation under the same name (its `_fusable` is False)
+            self.pnet = vector_pool.build_gridpool_module(cfg)
+        else:
+            self.pnet = PointnetSAModuleMSG(npoint=-1, radii=grid.RADII_PN, nsamples=cfg.SAMPLES_PN,
+                                            mlps=copy.deepcopy(grid.MLPS_PN), use_xyz=True)
         self.reduction = MLP(grid.MLPS_REDUCTION)
         self.generator = None
 
