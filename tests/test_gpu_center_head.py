@@ -119,6 +119,23 @@ def test_loss_and_gradient_match_the_restatement(shape):
     assert torch.equal(half, 0.5 * grad)
 
 
+def test_upstream_gradients_scale_the_two_channel_groups_exactly():
+    """Backward under upstream gradients (2, 3) is the stored gradient -- what a backward under (1, 1) returns -- times 2 on the heat
+    channels and 3 on the box channels, one exact fp32 multiply per element.  The first two frames of the 33 x 47 case: an odd number of
+    cells (1 551), so the boundary between the channel groups falls inside a wave in both frames."""
+    case = train_case(33, 47)
+    n_cls = case["n_cls"]
+    two = dict(case, maps=case["maps"][:2], tgt={k: case["tgt"][k][:2] for k in ("heat", "ind", "mask", "reg")})
+    assert int(two["tgt"]["mask"].sum()) > 0
+    _, _, stored = fused_loss(two)
+    _, _, grad = fused_loss(two, (2.0, 3.0))
+    want = stored.clone()
+    assert float(want[:, :n_cls].abs().max()) > 0 and float(want[:, n_cls:].abs().max()) > 0
+    want[:, :n_cls] *= 2.0
+    want[:, n_cls:] *= 3.0
+    assert torch.equal(grad, want)
+
+
 @pytest.mark.parametrize("shape", K.TRAIN_SHAPES)
 def test_center_loss_module_fused_and_torch_paths(shape, monkeypatch):
     """CenterLoss on an item as Second.forward leaves it (fused maps + the views made from them): the native pass; the same item without

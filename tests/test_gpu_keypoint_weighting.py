@@ -174,6 +174,23 @@ def test_seg_loss_and_gradient_against_float64(alpha, gamma):
     assert torch.equal(item["K_cls"].grad, item_b["K_cls"].grad) and torch.equal(item["K_label"], item_b["K_label"])
 
 
+def test_upstream_gradient_scales_the_stored_gradient_exactly():
+    """Backward under an upstream gradient of 2 (and of 3) is the stored gradient -- what a backward under 1 returns -- times it, one
+    exact fp32 multiply per element.  B = 2, K = 257: 514 rows, two workgroups and two elements over; one scalar for the whole buffer."""
+    from vision3d_amd.detector import KeypointSegLoss
+    kp, boxes, class_idx = R.make_label_case(K=257)
+    kp, boxes, class_idx = kp[1:], boxes[1:], class_idx[1:]
+    logits = np.random.default_rng(7).normal(0, 2.5, kp.shape[:2]).astype(np.float32)
+    loss = KeypointSegLoss(pkw_cfg())
+    grads = {}
+    for up in (1.0, 2.0, 3.0):
+        item = _item(kp, boxes, class_idx, logits)
+        (up * loss(item)["keypoint_seg_loss"]).backward()
+        grads[up] = item["K_cls"].grad
+    assert grads[1.0].shape == (2, 257) and float(grads[1.0].abs().max()) > 0
+    assert torch.equal(grads[2.0], 2.0 * grads[1.0]) and torch.equal(grads[3.0], 3.0 * grads[1.0])
+
+
 def test_seg_loss_without_ground_truth_and_with_an_empty_frame():
     from vision3d_amd.detector import KeypointSegLoss
     kp, boxes, class_idx = R.make_label_case()

@@ -76,6 +76,27 @@ def test_fused_loss_is_bit_repeatable_and_matches_fp32_torch_on_a_full_map():
     assert float((outs[0][1] - x.grad).abs().max()) <= 1e-5 * float(x.grad.abs().max())
 
 
+def test_upstream_gradients_scale_the_two_channel_groups_exactly():
+    """The backward of every fused loss is one kernel (csrc/proposal_loss.hip loss_scale_kernel): under upstream gradients (2, 3) it
+    returns the stored gradient -- what a backward under (1, 1) returns -- times 2 on the class channels and 3 on the box channels,
+    one exact fp32 multiply per element.  HW = 35, a group of 560 elements with 70 class elements in front: no multiple of a wave or
+    of a workgroup, and two groups."""
+    cfg = second_car_cfg()
+    maps, tg = _inputs(5, b=2, h=5, w=7)
+    grads = {}
+    for up in ((1.0, 1.0), (2.0, 3.0)):
+        x = maps.clone().requires_grad_(True)
+        l = _fused_loss(cfg, x, tg)
+        (up[0] * l["cls_loss"] + up[1] * l["reg_loss"]).backward()
+        grads[up] = x.grad
+    na = cfg.NUM_CLASSES * cfg.NUM_YAW
+    want = grads[1.0, 1.0].clone()
+    assert float(want[:, :na].abs().max()) > 0 and float(want[:, na:].abs().max()) > 0
+    want[:, :na] *= 2.0
+    want[:, na:] *= 3.0
+    assert torch.equal(grads[2.0, 3.0], want)
+
+
 def test_second_train_forward_hands_its_fused_maps_to_the_loss():
     """Second.forward on the native training path leaves `_head_maps` in the item; ProposalLoss then runs the native pass and the
     parameter gradients equal those of the torch loss on the same step (same dense / sparse kernels underneath)."""

@@ -77,6 +77,47 @@ def test_empty_masks_give_zero_loss_and_zero_gradients():
     assert bool(torch.isfinite(x.grad).all()) and float(x.grad.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("n", [1, 65])
+def test_upstream_gradients_scale_the_two_gradients_exactly(n):
+    """Backward under upstream gradients (2, 3) is the stored gradient -- what a backward under (1, 1) returns -- times 2 on the
+    confidence column and 3 on the box columns, one exact fp32 multiply per element.  One row; 65 rows as (1, 65): one more than a wave,
+    the confidence gradients in front of the 7 * rows box gradients in one buffer."""
+    head, tg = _inputs(13, b=1, n=n)
+    if n == 1:
+        tg["M_rcls"][:] = True
+        tg["M_rreg"][:] = True
+    grads = {}
+    for up in ((1.0, 1.0), (2.0, 3.0)):
+        x, l = _run(head, tg, True)
+        (up[0] * l["refine_cls_loss"] + up[1] * l["refine_reg_loss"]).backward()
+        grads[up] = x.grad
+    want = grads[1.0, 1.0].clone()
+    assert float(want[..., 7].abs().max()) > 0 and float(want[..., :7].abs().max()) > 0
+    want[..., 7] *= 2.0
+    want[..., :7] *= 3.0
+    assert torch.equal(grads[2.0, 3.0], want)
+
+
+def test_scale_entry_takes_gradient_buffers_that_are_not_adjacent():
+    """v3d_refine_loss_scale with two separately allocated buffers (the autograd node hands it one: a single launch): each is scaled
+    by its own upstream gradient, exactly, and nothing behind either is written."""
+    from vision3d_amd import _lib as L
+    rows = 65
+    g = torch.Generator(device="cuda").manual_seed(17)
+    reg_buf = torch.full((rows * 7 + 64,), 7.0, device="cuda")
+    cls_buf = torch.full((rows + 64,), 7.0, device="cuda")
+    d_reg, d_cls = reg_buf[:rows * 7], cls_buf[:rows]
+    d_reg.copy_(torch.randn(rows * 7, device="cuda", generator=g))
+    d_cls.copy_(torch.randn(rows, device="cuda", generator=g))
+    assert d_reg.data_ptr() != d_cls.data_ptr() + 4 * rows
+    want_reg, want_cls = 3.0 * d_reg, 2.0 * d_cls
+    g_cls, g_reg = torch.tensor(2.0, device="cuda"), torch.tensor(3.0, device="cuda")
+    with L.device_guard(d_reg.device):
+        L.check(L.lib().v3d_refine_loss_scale(L.ptr(d_reg), L.ptr(d_cls), rows, L.ptr(g_cls), L.ptr(g_reg), L.stream_ptr()), "refine_loss_scale")
+    assert torch.equal(d_reg, want_reg) and torch.equal(d_cls, want_cls)
+    assert bool((reg_buf[rows * 7:] == 7.0).all()) and bool((cls_buf[rows:] == 7.0).all())
+
+
 def test_backward_twice_raises():
     head, tg = _inputs(7, b=1, n=64)
     _, l = _run(head, tg, True)

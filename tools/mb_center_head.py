@@ -117,7 +117,7 @@ def main(argv=None):
         assert torch.allclose(l1, l2, rtol=1e-4) and float((g1 - g2).abs().max()) <= 1e-4 * float(g2.abs().max()), "native and torch loss disagree"
         compare([("loss native (3 + 1 launches)  ", lambda: run_loss(True)), ("loss torch + autograd         ", lambda: run_loss(False))],
                 args.windows, args.reps)
-        kernel_times(lambda: run_loss(True), ("ch_loss_",))
+        kernel_times(lambda: run_loss(True), ("ch_loss_", "loss_scale_kernel"))
 
         # ---- decode
         native_d, torch_d = lambda: head.decode(maps), lambda: head.decode_torch(maps)

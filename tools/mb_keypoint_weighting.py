@@ -122,7 +122,7 @@ def main(argv=None):
             f"{sum(len(b) for b in boxes)} ground truths in {batch} frame(s)")
         compare("loss + backward, fused         ", lambda: run(loss), "loss + backward, torch         ", lambda: run(loss.forward_torch),
                 args.windows, args.reps)
-        kernel_times(lambda: run(loss), ("keypoint_seg_loss",))
+        kernel_times(lambda: run(loss), ("keypoint_seg_loss", "loss_scale_kernel"))
     with open(args.out, "w") as f:
         f.write("\n".join(LINES) + "\n")
     return 0

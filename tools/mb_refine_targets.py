@@ -93,7 +93,7 @@ def main(argv=None):
         assert torch.allclose(la, lb, rtol=1e-6) and torch.allclose(ga, gb, rtol=1e-5, atol=1e-7), "the two losses disagree"
         compare("loss + backward, fused        ", lambda: run(loss), "loss + backward, torch        ", lambda: run(loss.forward_torch),
                 args.windows, args.reps)
-        kernel_times(lambda: run(loss), ("refine_loss",))
+        kernel_times(lambda: run(loss), ("refine_loss", "loss_scale_kernel"))
     return 0
 
 

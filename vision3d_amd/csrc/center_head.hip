@@ -15,7 +15,8 @@
 //   per object ind = iy * W + ix, mask, cls, reg = (fx - ix, fy - iy, z, logf w, logf l, logf h, sinf yaw, cosf yaw), padded to
 //              CH_MAX_OBJ rows per frame; not live: ind = -1, mask = 0, cls = the given class, reg = 0.
 //   loss       N = max(#mask, 1) over the batch, p = sigmoid(x); heat == 1: -(1 - p)^alpha log p, else -(1 - heat)^beta p^alpha
-//              log(1 - p), with log p = -softplus(-x), log(1 - p) = -softplus(x); hm = sum / N.  reg = sum over masked objects and
+//              log(1 - p), with log p = -softplus(-x), log(1 - p) = -softplus(x) and p, 1 - p of loss_device.h v3d_sigmoid_pq;
+//              hm = sum / N.  reg = sum over masked objects and
 //              j of code_weights[j] |pred_j - target_j| / N, pred read at the object's cell; sign(0) = 0.
 //   decode     peak: logit >= each in-map neighbour (of 8).  Per (b, c) the topk peaks by logit, ties to the lower cell; box =
 //              ((ix + dx) px + x_lo, (iy + dy) py + y_lo, z, expf(w, l, h), atan2f(sin, cos)), score = sigmoid; missing: zeros.
@@ -25,15 +26,15 @@
 // maximum over the frame's records of its class whose window covers it -- no atomic, no clear: every heat cell is written once.
 // The tile-0, class-0 workgroup of a frame writes the frame's per-object rows.
 // ch_loss_heat_kernel: grid-stride over all channels of the maps: heat channels get their gradient, box channels exact zeros;
-// per-lane double sums, fixed tree per workgroup, partials to the workspace.  ch_loss_box_kernel: a workgroup per frame, lane = object:
-// the lowest-index masked object of a cell sums the gradients of the cell's objects in object order and stores them (plain stores
-// behind the zeros, in stream order).  ch_loss_finalize_kernel: partials summed in index order in double.
+// per-lane double sums, the workgroup sum of loss_device.h, partials to the workspace.  ch_loss_box_kernel: a workgroup per frame,
+// lane = object: the lowest-index masked object of a cell sums the gradients of the cell's objects in object order and stores them
+// (plain stores behind the zeros, in stream order).  ch_loss_finalize_kernel: partials summed in index order in double.
 // ch_peaks_kernel: grid (slices of 4096 cells, group = frame * n_cls + class): 64-bit keys (order-preserving logit bits << 32 |
 // ~cell; 0 = not a peak) sorted in LDS (bitonic), the slice's best topk to the workspace.  ch_select_kernel: a workgroup per group
 // merges the slices' sorted lists one at a time (best | next list reversed: one bitonic merge of 2048 keys, 11 steps), then decodes.
 // The cell of a key is the index the kernel itself wrote into it: no index is derived from a map value; a NaN logit is never a peak.
-#include "v3d_common.h"
-#include "../../include/vision3d_hip.h"
+#include "loss_device.h"
+#include "v3d_internal.h"
 
 #define CH_MAX_OBJ 128
 #define CH_MAX_FRAMES 64
@@ -43,6 +44,7 @@
 #define CH_SLICE 4096
 #define CH_LOSS_BLOCKS 512
 #define CH_SEL_THREADS 1024
+#define CH_FIN_THREADS 64  // ch_loss_finalize_kernel: one wave
 
 struct ChFrames {  // host offsets, passed by value: first object of each frame
   int bx[CH_MAX_FRAMES + 1];
@@ -127,26 +129,20 @@ __global__ __launch_bounds__(V3D_BLOCK) void ch_targets_kernel(const float* __re
 
 // ---- loss
 
+template <int THREADS>  // of the workgroup
 __device__ __forceinline__ int ch_count_masked(const uint8_t* __restrict__ mask, int rows, int* red) {
-  // the number of masked objects of the batch, by every workgroup for itself (<= 8 192 bytes): integer sums, order-free
+  // the number of masked objects of the batch, by every workgroup for itself (<= 8 192 bytes)
   int c = 0;
-  for (int i = threadIdx.x; i < rows; i += blockDim.x) c += mask[i] != 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  int t = 0;
-  for (int w = 0; w < (int)blockDim.x / 64; w++) t += red[w];
-  __syncthreads();
-  return t;
+  for (int i = threadIdx.x; i < rows; i += THREADS) c += mask[i] != 0;
+  return v3d_block_sum<THREADS / V3D_WAVE>(c, red);
 }
 
 __global__ __launch_bounds__(V3D_BLOCK) void ch_loss_heat_kernel(const float* __restrict__ maps, const float* __restrict__ heat,
                                                                  const uint8_t* __restrict__ mask, int B, int n_cls, int HW, float alpha,
                                                                  float beta, float* __restrict__ dmaps, double* __restrict__ partial) {
-  __shared__ int red_i[V3D_BLOCK / 64];
-  __shared__ double red[V3D_BLOCK / 64];
-  const int cnt = ch_count_masked(mask, B * CH_MAX_OBJ, red_i);
+  __shared__ int red_i[V3D_BLOCK / V3D_WAVE];
+  __shared__ double red[V3D_BLOCK / V3D_WAVE];
+  const int cnt = ch_count_masked<V3D_BLOCK>(mask, B * CH_MAX_OBJ, red_i);
   const float inv_n = 1.f / (float)(cnt > 0 ? cnt : 1);
   const int O = n_cls + 8;
   const long long total = (long long)B * O * HW;
@@ -158,17 +154,15 @@ __global__ __launch_bounds__(V3D_BLOCK) void ch_loss_heat_kernel(const float* __
     if (o < n_cls) {
       const float x = maps[i];
       const float t = heat[((size_t)b * n_cls + o) * HW + pix];
-      const float e = expf(-fabsf(x));
-      const float inv = 1.f / (1.f + e);
-      const float p = x >= 0.f ? inv : e * inv, q = x >= 0.f ? e * inv : inv;  // q = 1 - p without cancellation
-      const float l1pe = log1pf(e);
+      float e, p, q;
+      v3d_sigmoid_pq(x, e, p, q);
       if (t == 1.f) {
-        const float lp = -(fmaxf(-x, 0.f) + l1pe);  // log p = -softplus(-x)
+        const float lp = -v3d_softplus(-x, e);  // log p
         const float qa = alpha == 2.f ? q * q : powf(q, alpha);
         sum += (double)(-qa * lp);
         gx = qa * (alpha * p * lp - q);
       } else {
-        const float lq = -(fmaxf(x, 0.f) + l1pe);  // log(1 - p) = -softplus(x)
+        const float lq = -v3d_softplus(x, e);  // log(1 - p)
         const float nt = 1.f - t;
         const float w = beta == 4.f ? (nt * nt) * (nt * nt) : powf(nt, beta);
         const float pa = alpha == 2.f ? p * p : powf(p, alpha);
@@ -179,15 +173,8 @@ __global__ __launch_bounds__(V3D_BLOCK) void ch_loss_heat_kernel(const float* __
     }
     dmaps[i] = gx;  // (box channels: exact zeros; ch_loss_box_kernel stores the object cells behind this launch)
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int w = 0; w < V3D_BLOCK / 64; w++) t += red[w];
-    partial[blockIdx.x] = t;
-  }
+  const double t = v3d_block_sum<V3D_BLOCK / V3D_WAVE>(sum, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
 struct ChWeights {
@@ -203,7 +190,7 @@ __global__ __launch_bounds__(CH_MAX_OBJ) void ch_loss_box_kernel(const float* __
   __shared__ float s_g[CH_MAX_OBJ][8];
   __shared__ double s_l[CH_MAX_OBJ];
   const int tid = threadIdx.x, b = blockIdx.x;
-  const int cnt = ch_count_masked(mask, B * CH_MAX_OBJ, red_i);
+  const int cnt = ch_count_masked<CH_MAX_OBJ>(mask, B * CH_MAX_OBJ, red_i);
   const float inv_n = 1.f / (float)(cnt > 0 ? cnt : 1);
   const size_t o = (size_t)b * CH_MAX_OBJ + tid;
   int cell = ind[o];
@@ -247,10 +234,11 @@ __global__ __launch_bounds__(CH_MAX_OBJ) void ch_loss_box_kernel(const float* __
   }
 }
 
-__global__ void ch_loss_finalize_kernel(const double* __restrict__ heat_partial, int heat_blocks, const double* __restrict__ box_partial,
-                                        int B, const uint8_t* __restrict__ mask, float* __restrict__ losses) {
-  __shared__ int red_i[1];
-  const int cnt = ch_count_masked(mask, B * CH_MAX_OBJ, red_i);
+__global__ __launch_bounds__(CH_FIN_THREADS) void ch_loss_finalize_kernel(const double* __restrict__ heat_partial, int heat_blocks,
+                                                                          const double* __restrict__ box_partial, int B,
+                                                                          const uint8_t* __restrict__ mask, float* __restrict__ losses) {
+  __shared__ int red_i[CH_FIN_THREADS / V3D_WAVE];
+  const int cnt = ch_count_masked<CH_FIN_THREADS>(mask, B * CH_MAX_OBJ, red_i);
   const double n = (double)(cnt > 0 ? cnt : 1);
   if (threadIdx.x < 2) {
     const double* p = threadIdx.x == 0 ? heat_partial : box_partial;
@@ -259,17 +247,6 @@ __global__ void ch_loss_finalize_kernel(const double* __restrict__ heat_partial,
     for (int i = 0; i < m; i++) t += p[i];
     losses[threadIdx.x] = (float)(t / n);
     if (threadIdx.x == 0) losses[2] = (float)n;
-  }
-}
-
-__global__ __launch_bounds__(V3D_BLOCK) void ch_loss_scale_kernel(float* __restrict__ dmaps, int B, int n_cls, int HW,
-                                                                  const float* __restrict__ g_hm, const float* __restrict__ g_reg) {
-  const int O = n_cls + 8;
-  const long long total = (long long)B * O * HW;
-  const float gh = *g_hm, gr = *g_reg;
-  for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * V3D_BLOCK) {
-    const int o = (int)((i / HW) % O);
-    dmaps[i] *= o < n_cls ? gh : gr;
   }
 }
 
@@ -433,8 +410,8 @@ extern "C" int v3d_center_loss_fwd_bwd(const float* maps, const float* heat, con
   hipLaunchKernelGGL(ch_loss_heat_kernel, dim3(blocks), dim3(V3D_BLOCK), 0, st, maps, heat, mask, B, n_cls, HW, alpha, beta, dmaps,
                      heat_partial);
   hipLaunchKernelGGL(ch_loss_box_kernel, dim3(B), dim3(CH_MAX_OBJ), 0, st, maps, ind, mask, reg, B, n_cls, HW, cw, dmaps, box_partial);
-  hipLaunchKernelGGL(ch_loss_finalize_kernel, dim3(1), dim3(64), 0, st, (const double*)heat_partial, blocks, (const double*)box_partial, B,
-                     mask, losses);
+  hipLaunchKernelGGL(ch_loss_finalize_kernel, dim3(1), dim3(CH_FIN_THREADS), 0, st, (const double*)heat_partial, blocks,
+                     (const double*)box_partial, B, mask, losses);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }
@@ -444,11 +421,9 @@ extern "C" int v3d_center_loss_scale(float* dmaps, int B, int n_cls, int H, int 
   if (B < 1 || n_cls < 1 || H < 1 || W < 1) return V3D_EINVAL;
   if (B > CH_MAX_FRAMES || n_cls > CH_MAX_CLS || (long long)H * W > CH_MAX_CELLS) return V3D_EUNSUPPORTED;
   if (!dmaps || !g_hm || !g_reg) return V3D_EINVAL;
-  const long long total = (long long)B * (n_cls + 8) * H * W;
-  hipLaunchKernelGGL(ch_loss_scale_kernel, dim3((int)std::min<long long>(2048, (total + V3D_BLOCK - 1) / V3D_BLOCK)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, dmaps, B, n_cls, H * W, g_hm, g_reg);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
+  // heat channels *= *g_hm, box channels *= *g_reg
+  const long long HW = (long long)H * W, period = (n_cls + 8) * HW;
+  return v3d_i_loss_scale(dmaps, B, period, n_cls * HW, g_hm, g_reg, 2048, (hipStream_t)stream);
 }
 
 extern "C" size_t v3d_center_decode_workspace(int B, int n_cls, int H, int W) {

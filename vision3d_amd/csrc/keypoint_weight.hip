@@ -8,15 +8,10 @@
 //   keypoint feature matrix scaled in place with 16-byte loads and stores.  Memory-bound: the row is read and written once.
 // v3d_keypoint_seg_loss_fwd_bwd: labels, focal loss and its gradient in ONE launch of one workgroup (B * K is a few tens of thousands
 //   of rows): the frame's ground truths prepared into LDS with pib_device.h -- the test of v3d_points_in_boxes, bit for bit --,
-//   thread = keypoint (strided); counts in int, the loss in double, both summed in a fixed order: bit-repeatable.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
-
-#include "../../include/vision3d_hip.h"
+//   thread = keypoint (strided); counts in int, the loss in double, both summed in the fixed order of loss_device.h: bit-repeatable.
+#include "loss_device.h"
 #include "pib_device.h"
-#include "v3d_common.h"
+#include "v3d_internal.h"
 
 #define KW_WAVES (V3D_BLOCK / V3D_WAVE)  // rows of one workgroup
 
@@ -61,7 +56,7 @@ extern "C" int v3d_keypoint_weight(const float* hidden, int ldh, int H, const fl
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // keypoint segmentation loss: label 1 inside a ground-truth box (class >= 0) of the keypoint's own frame, 255 (ignored) inside
-// such a box grown by `extra`, else 0; sigmoid focal loss (ops/focal_loss.py, the expression of proposal_loss.hip) over the
+// such a box grown by `extra`, else 0; sigmoid focal loss (ops/focal_loss.py: loss_device.h v3d_sigmoid_focal) over the
 // labels != 255, divided by max(#label 1, 1); the gradient is written with the forward.
 // ------------------------------------------------------------------------------------------------------------------------------
 #define KS_MAX_GT 64  // ground truths staged per pass over a frame's keypoints (a frame with more takes several passes)
@@ -71,19 +66,6 @@ struct KsParams {
   float extra[3];
   float alpha, gamma;
 };
-
-template <typename T>
-__device__ __forceinline__ T ks_block_sum(T v, T* red) {  // fixed order: butterfly inside the wave, then the waves in index order
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (red may still be read by the previous sum)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-#pragma unroll
-  for (int w = 0; w < KW_WAVES; w++) t += red[w];
-  return t;
-}
 
 // every thread keeps ITS rows (tid, tid + 256, ... of every frame) through both passes: it reads back only labels it wrote itself
 __global__ __launch_bounds__(V3D_BLOCK) void keypoint_seg_loss_kernel(const float* __restrict__ keypoints, const float* __restrict__ logits,
@@ -140,8 +122,8 @@ __global__ __launch_bounds__(V3D_BLOCK) void keypoint_seg_loss_kernel(const floa
       c_ign += lab == 255;
     }
   }
-  const int n_fg = ks_block_sum(c_fg, red_i);
-  const int n_ign = ks_block_sum(c_ign, red_i);
+  const int n_fg = v3d_block_sum<KW_WAVES>(c_fg, red_i);
+  const int n_ign = v3d_block_sum<KW_WAVES>(c_ign, red_i);
   if (!logits) {  // labels alone (uniform over the workgroup)
     if (tid == 0 && losses) {
       losses[0] = 0.f;
@@ -159,33 +141,18 @@ __global__ __launch_bounds__(V3D_BLOCK) void keypoint_seg_loss_kernel(const floa
       const int lab = labels[i];
       float gx = 0.f;
       if (lab != 255) {
-        const float x = logits[i], t = lab == 1 ? 1.f : 0.f;
-        const float e = expf(-fabsf(x));
-        const float prob = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-        const float bce = fmaxf(x, 0.f) - x * t + log1pf(e);
-        const float p_t = prob * t + (1.f - prob) * (1.f - t);
-        const float q = 1.f - p_t;
-        const float w = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
-        const float qg = gamma == 2.f ? q * q : powf(q, gamma);
-        const float qg1 = gamma == 2.f ? q : powf(q, gamma - 1.f);
-        s += (double)(w * bce * qg);
-        // d/dx: bce' = prob - t, p_t' = prob (1 - prob) (2 t - 1)
-        gx = w * ((prob - t) * qg - bce * gamma * qg1 * prob * (1.f - prob) * (2.f * t - 1.f)) * inv_n;
+        float dx;
+        s += (double)v3d_sigmoid_focal(logits[i], lab == 1 ? 1.f : 0.f, alpha, gamma, dx);
+        gx = dx * inv_n;
       }
       d_logits[i] = gx;
     }
-  const double total = ks_block_sum(s, red_d);
+  const double total = v3d_block_sum<KW_WAVES>(s, red_d);
   if (tid == 0) {
     losses[0] = (float)(total / (double)max(n_fg, 1));
     losses[1] = (float)n_fg;
     losses[2] = (float)n_ign;
   }
-}
-
-// d_logits *= *g (the upstream gradient of the loss, a device scalar)
-__global__ __launch_bounds__(V3D_BLOCK) void keypoint_seg_loss_scale_kernel(float* __restrict__ d_logits, int rows, const float* __restrict__ g) {
-  const float gv = *g;
-  for (int i = blockIdx.x * V3D_BLOCK + threadIdx.x; i < rows; i += gridDim.x * V3D_BLOCK) d_logits[i] *= gv;
 }
 
 #define KS_MAX_ROWS (1 << 24)  // (counts are reported as float)
@@ -213,8 +180,5 @@ extern "C" int v3d_keypoint_seg_loss_scale(float* d_logits, int rows, const floa
   if (rows < 0 || rows > KS_MAX_ROWS || !g) return V3D_EINVAL;
   if (rows == 0) return V3D_OK;
   if (!d_logits) return V3D_EINVAL;
-  hipLaunchKernelGGL(keypoint_seg_loss_scale_kernel, dim3(std::min(64, v3d_ceil_div(rows, V3D_BLOCK))), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, d_logits, rows, g);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
+  return v3d_i_loss_scale(d_logits, 1, rows, rows, g, g, 64, (hipStream_t)stream);  // d_logits *= *g
 }

@@ -5,27 +5,23 @@
 // upstream broadcasts it over the three columns it is added to, counted three times) summed over the anchors with M_reg, both
 // divided by max(#M_reg, 1).  Through torch this is ~40 elementwise / reduction launches forward and backward (0.25 ms of a
 // 7.4 ms step); here: count the positives, one pass that writes the gradient of both terms with respect to the FUSED head maps
-// (B, n_cls * n_yaw * (1 + 7), H, W) and per-workgroup partial sums, one merge in a fixed order.  fp32, bit-repeatable.
+// (B, n_cls * n_yaw * (1 + 7), H, W) and per-workgroup partial sums, one merge in a fixed order.  fp32, bit-repeatable.  The focal
+// and smooth-L1 expressions and the workgroup sum are those of loss_device.h.
 //   class channel of anchor (cls, yaw):            cls * n_yaw + yaw
 //   box channel d of anchor (cls, yaw):  n_anchor + (cls * 7 + d) * n_yaw + yaw          (ProposalLayer.reshape_cls / reshape_reg)
+#include "loss_device.h"
 #include "v3d_internal.h"
 
 #define PL_BLOCKS 512
 #define PL_DOF 7
+#define PL_WAVES (V3D_BLOCK / V3D_WAVE)
 
 __global__ __launch_bounds__(V3D_BLOCK) void pl_count_kernel(const unsigned char* __restrict__ m_reg, long long n, int* __restrict__ partial) {
-  __shared__ int red[V3D_BLOCK / 64];
+  __shared__ int red[PL_WAVES];
   int c = 0;
   for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * V3D_BLOCK) c += m_reg[i] != 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-    for (int w = 0; w < V3D_BLOCK / 64; w++) t += red[w];
-    partial[blockIdx.x] = t;
-  }
+  const int t = v3d_block_sum<PL_WAVES>(c, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
 __global__ void pl_count_merge_kernel(const int* __restrict__ partial, int blocks, float* __restrict__ normalizer) {
@@ -43,7 +39,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void pl_main_kernel(const float* __restr
                                                             const unsigned char* __restrict__ m_reg, int B, int n_cls, int n_yaw, int HW,
                                                             float alpha, float gamma, const float* __restrict__ normalizer,
                                                             float* __restrict__ dmaps, float* __restrict__ partial) {
-  __shared__ float red[2][V3D_BLOCK / 64];
+  __shared__ float red[PL_WAVES];
   const int n_anchor = n_cls * n_yaw, O = n_anchor * (1 + PL_DOF);
   const long long total = (long long)B * n_anchor * HW;
   const float inv_n = 1.f / *normalizer;
@@ -58,18 +54,9 @@ __global__ __launch_bounds__(V3D_BLOCK) void pl_main_kernel(const float* __restr
     const float x = maps[ic];
     float gx = 0.f;
     if (m_cls[i]) {
-      const float t = g_cls[i] > 0 ? 1.f : 0.f;
-      const float e = expf(-fabsf(x));
-      const float prob = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-      const float bce = fmaxf(x, 0.f) - x * t + log1pf(e);
-      const float p_t = prob * t + (1.f - prob) * (1.f - t);
-      const float q = 1.f - p_t;
-      const float w = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
-      const float qg = gamma == 2.f ? q * q : powf(q, gamma);
-      const float qg1 = gamma == 2.f ? q : powf(q, gamma - 1.f);
-      s_cls += w * bce * qg;
-      // d/dx: bce' = prob - t, p_t' = prob (1 - prob) (2 t - 1)
-      gx = w * ((prob - t) * qg - bce * gamma * qg1 * prob * (1.f - prob) * (2.f * t - 1.f)) * inv_n;
+      float dx;
+      s_cls += v3d_sigmoid_focal(x, g_cls[i] > 0 ? 1.f : 0.f, alpha, gamma, dx);
+      gx = dx * inv_n;
     }
     dmaps[ic] = gx;
     // ---- box term
@@ -80,30 +67,17 @@ __global__ __launch_bounds__(V3D_BLOCK) void pl_main_kernel(const float* __restr
       const size_t ir = mb + ((size_t)n_anchor + (size_t)(cls * PL_DOF + d) * n_yaw + yaw) * HW + pix;
       float gd = 0.f;
       if (pos) {
-        const float diff = maps[ir] - g[d];
-        const float ad = fabsf(diff);
         const float wd = d == PL_DOF - 1 ? 3.f / 3.14159265358979323846f : 1.f;
-        s_reg += wd * (ad < 1.f ? 0.5f * diff * diff : ad - 0.5f);
-        gd = wd * fminf(fmaxf(diff, -1.f), 1.f) * inv_n;
+        float clamped;
+        s_reg += wd * v3d_smooth_l1(maps[ir] - g[d], clamped);
+        gd = wd * clamped * inv_n;
       }
       dmaps[ir] = gd;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    s_cls += __shfl_xor(s_cls, off);
-    s_reg += __shfl_xor(s_reg, off);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = s_cls;
-    red[1][threadIdx.x >> 6] = s_reg;
-  }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    float t = 0.f;
-    for (int w = 0; w < V3D_BLOCK / 64; w++) t += red[threadIdx.x][w];
-    partial[blockIdx.x * 2 + threadIdx.x] = t;
-  }
+  const float t_cls = v3d_block_sum<PL_WAVES>(s_cls, red);
+  const float t_reg = v3d_block_sum<PL_WAVES>(s_reg, red);
+  if (threadIdx.x < 2) partial[blockIdx.x * 2 + threadIdx.x] = threadIdx.x == 0 ? t_cls : t_reg;
 }
 
 __global__ void pl_finalize_kernel(const float* __restrict__ partial, int blocks, const float* __restrict__ normalizer,
@@ -116,16 +90,26 @@ __global__ void pl_finalize_kernel(const float* __restrict__ partial, int blocks
   }
 }
 
-// dmaps[class channels] *= *g_cls, dmaps[box channels] *= *g_reg (the upstream gradients of the two loss terms, device scalars)
-__global__ __launch_bounds__(V3D_BLOCK) void pl_scale_kernel(float* __restrict__ dmaps, int B, int n_anchor, int HW,
-                                                             const float* __restrict__ g_cls, const float* __restrict__ g_reg) {
-  const int O = n_anchor * (1 + PL_DOF);
-  const long long total = (long long)B * O * HW;
-  const float gc = *g_cls, gr = *g_reg;
-  for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * V3D_BLOCK) {
-    const int o = (int)((i / HW) % O);
-    dmaps[i] *= o < n_anchor ? gc : gr;
+// The backward of every fused loss: its stored gradient times the upstream gradients of its (one or two) loss terms, device scalars.
+// buf = `groups` groups of `period` elements: the first `head` of a group *= *g_head, the rest *= *g_tail.  Grid: x strides over one
+// group, y over the groups -- no index is divided.
+__global__ __launch_bounds__(V3D_BLOCK) void loss_scale_kernel(float* __restrict__ buf, int groups, long long period, long long head,
+                                                               const float* __restrict__ g_head, const float* __restrict__ g_tail) {
+  const float gh = *g_head, gt = *g_tail;
+  for (int g = blockIdx.y; g < groups; g += gridDim.y) {
+    float* p = buf + g * period;
+    for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < period; i += (long long)gridDim.x * V3D_BLOCK)
+      p[i] *= i < head ? gh : gt;
   }
+}
+
+int v3d_i_loss_scale(float* buf, int groups, long long period, long long head, const float* g_head, const float* g_tail, int max_blocks,
+                     hipStream_t st) {
+  const int gy = std::min(groups, max_blocks);
+  const int gx = (int)std::min<long long>(std::max(max_blocks / gy, 1), (period + V3D_BLOCK - 1) / V3D_BLOCK);
+  hipLaunchKernelGGL(loss_scale_kernel, dim3(gx, gy), dim3(V3D_BLOCK), 0, st, buf, groups, period, head, g_head, g_tail);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
 }
 
 extern "C" size_t v3d_proposal_loss_workspace(void) { return (size_t)PL_BLOCKS * (2 * sizeof(float) + sizeof(int)) + 256; }
@@ -156,9 +140,6 @@ extern "C" int v3d_proposal_loss_fwd_bwd(const float* maps, const int8_t* g_cls,
 extern "C" int v3d_proposal_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
                                        v3d_stream_t stream) {
   if (!dmaps || !g_cls || !g_reg || B < 1 || n_cls < 1 || n_yaw < 1 || H < 1 || W < 1) return V3D_EINVAL;
-  const long long total = (long long)B * n_cls * n_yaw * (1 + PL_DOF) * H * W;
-  hipLaunchKernelGGL(pl_scale_kernel, dim3((int)std::min<long long>(2048, (total + V3D_BLOCK - 1) / V3D_BLOCK)), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, dmaps, B, n_cls * n_yaw, H * W, g_cls, g_reg);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
+  const long long head = (long long)n_cls * n_yaw * H * W, period = head * (1 + PL_DOF);
+  return v3d_i_loss_scale(dmaps, B, period, head, g_cls, g_reg, 2048, (hipStream_t)stream);
 }

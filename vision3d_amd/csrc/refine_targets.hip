@@ -11,15 +11,12 @@
 //   3. the (draw, index) ranks of the foreground / background sampling are counted from LDS (every lane reads the same entry in
 //      the same step: a broadcast), the quotas from one block-wide count.
 // v3d_refine_loss_fwd_bwd: ONE launch of one workgroup (B * n is a few thousand rows): counts, both loss terms and both gradients;
-// sums are accumulated in double in a fixed order, so the result is bit-repeatable.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <algorithm>
-
-#include "../../include/vision3d_hip.h"
+// sums are accumulated in double in the fixed order of loss_device.h, so the result is bit-repeatable.
+#include "loss_device.h"
 #include "rotated_iou.h"
-#include "v3d_common.h"
+#include "v3d_internal.h"
+
+#define RT_WAVES (V3D_BLOCK / V3D_WAVE)
 
 // LDS of refine_targets_kernel: 72 KB of clipper slabs (4 waves x 24 points x 64 lanes x 12 B, as the other IoU kernels) + 8 KB
 // draws + 2 KB flags + 5.5 KB ground truths = ~88 KB static: one workgroup per CU on gfx950 (160 KB), which is all a launch of B
@@ -48,11 +45,11 @@ __global__ __launch_bounds__(V3D_BLOCK) void refine_targets_kernel(const float* 
                                                                    unsigned char* __restrict__ m_reg) {
   __shared__ v3d::Box3Prep s_gt[RT_MAX_GT];
   __shared__ int s_gt_class[RT_MAX_GT];
-  __shared__ v3d::P2 clip_pts[V3D_BLOCK / V3D_WAVE][24 * 64];  // the clipper's work arrays: LDS, not scratch (rotated_iou.h)
-  __shared__ float clip_dist[V3D_BLOCK / V3D_WAVE][24 * 64];
+  __shared__ v3d::P2 clip_pts[RT_WAVES][24 * 64];  // the clipper's work arrays: LDS, not scratch (rotated_iou.h)
+  __shared__ float clip_dist[RT_WAVES][24 * 64];
   __shared__ float s_draw[RT_MAX_ROI];
   __shared__ unsigned char s_flag[RT_MAX_ROI];  // bit 0: foreground, bit 1: gets a box target
-  __shared__ int s_red[V3D_BLOCK / V3D_WAVE];
+  __shared__ int s_red[RT_WAVES];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = min(p.n, RT_MAX_ROI);
   // the frame's slice of the flat ground-truth list, clamped to the list and to the staging limit
@@ -107,13 +104,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void refine_targets_kernel(const float* 
     n_fg_mine += fg;
   }
   // ---- sampling: #foreground of the frame, then every RoI's rank inside its own group by (draw, index)
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) n_fg_mine += __shfl_xor(n_fg_mine, off);
-  if ((tid & 63) == 0) s_red[tid >> 6] = n_fg_mine;
-  __syncthreads();  // (also: s_flag / s_draw are complete)
-  int count_fg = 0;
-#pragma unroll
-  for (int w = 0; w < V3D_BLOCK / V3D_WAVE; w++) count_fg += s_red[w];
+  const int count_fg = v3d_block_sum<RT_WAVES>(n_fg_mine, s_red);  // (its barriers also complete s_flag / s_draw)
   const bool all = p.rois_per_frame <= 0;
   const int take_fg = min(count_fg, max(p.fg_quota, 0));
   const int take_bg = min(n - count_fg, max(p.rois_per_frame - take_fg, 0));
@@ -158,46 +149,31 @@ extern "C" int v3d_refine_targets(const float* proposals, const int64_t* proposa
 // refinement loss: soft-target binary cross-entropy on the confidence logit over M_cls, smooth-L1 (beta 1) on the 7 residuals
 // over M_reg, each divided by its own count (at least 1); the gradients are written with the forward.
 // ------------------------------------------------------------------------------------------------------------------------------
-#define RL_WAVES (V3D_BLOCK / V3D_WAVE)
-
-template <typename T>
-__device__ __forceinline__ T rl_block_sum(T v, T* red) {  // fixed order: butterfly inside the wave, then the waves in index order
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();  // (red may still be read by the previous sum)
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-#pragma unroll
-  for (int w = 0; w < RL_WAVES; w++) t += red[w];
-  return t;
-}
-
 __global__ __launch_bounds__(V3D_BLOCK) void refine_loss_kernel(const float* __restrict__ r_reg, int ld_reg, const float* __restrict__ r_cls,
                                                                 int ld_cls, const float* __restrict__ g_conf,
                                                                 const float* __restrict__ g_reg, const unsigned char* __restrict__ m_cls,
                                                                 const unsigned char* __restrict__ m_reg, int rows,
                                                                 float* __restrict__ losses, float* __restrict__ d_reg,
                                                                 float* __restrict__ d_cls) {
-  __shared__ int red_i[RL_WAVES];
-  __shared__ double red_d[RL_WAVES];
+  __shared__ int red_i[RT_WAVES];
+  __shared__ double red_d[RT_WAVES];
   const int tid = threadIdx.x;
   int c_cls = 0, c_reg = 0;
   for (int i = tid; i < rows; i += V3D_BLOCK) {
     c_cls += m_cls[i] != 0;
     c_reg += m_reg[i] != 0;
   }
-  const int n_cls = rl_block_sum(c_cls, red_i);
-  const int n_reg = rl_block_sum(c_reg, red_i);
+  const int n_cls = v3d_block_sum<RT_WAVES>(c_cls, red_i);
+  const int n_reg = v3d_block_sum<RT_WAVES>(c_reg, red_i);
   const float inv_cls = 1.f / (float)max(n_cls, 1), inv_reg = 1.f / (float)max(n_reg, 1);
   double s_cls = 0.0, s_reg = 0.0;
   for (int i = tid; i < rows; i += V3D_BLOCK) {
     float gx = 0.f;
     if (m_cls[i]) {
       const float x = r_cls[(size_t)i * ld_cls], t = g_conf[i];
-      const float e = expf(-fabsf(x));
-      const float prob = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-      s_cls += (double)(fmaxf(x, 0.f) - x * t + log1pf(e));
+      float e;
+      const float prob = v3d_sigmoid(x, e);
+      s_cls += (double)v3d_bce_logits(x, t, e);
       gx = (prob - t) * inv_cls;
     }
     d_cls[i] = gx;
@@ -206,16 +182,15 @@ __global__ __launch_bounds__(V3D_BLOCK) void refine_loss_kernel(const float* __r
     for (int d = 0; d < 7; d++) {
       float gd = 0.f;
       if (pos) {
-        const float diff = r_reg[(size_t)i * ld_reg + d] - g_reg[(size_t)i * 7 + d];
-        const float ad = fabsf(diff);
-        s_reg += (double)(ad < 1.f ? 0.5f * diff * diff : ad - 0.5f);
-        gd = fminf(fmaxf(diff, -1.f), 1.f) * inv_reg;
+        float clamped;
+        s_reg += (double)v3d_smooth_l1(r_reg[(size_t)i * ld_reg + d] - g_reg[(size_t)i * 7 + d], clamped);
+        gd = clamped * inv_reg;
       }
       d_reg[(size_t)i * 7 + d] = gd;
     }
   }
-  const double t_cls = rl_block_sum(s_cls, red_d);
-  const double t_reg = rl_block_sum(s_reg, red_d);
+  const double t_cls = v3d_block_sum<RT_WAVES>(s_cls, red_d);
+  const double t_reg = v3d_block_sum<RT_WAVES>(s_reg, red_d);
   if (tid == 0) {
     losses[0] = (float)(t_cls / (double)max(n_cls, 1));
     losses[1] = (float)(t_reg / (double)max(n_reg, 1));
@@ -224,17 +199,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void refine_loss_kernel(const float* __r
   }
 }
 
-// d_cls *= *g_cls, d_reg *= *g_reg (the upstream gradients of the two loss terms, device scalars)
-__global__ __launch_bounds__(V3D_BLOCK) void refine_loss_scale_kernel(float* __restrict__ d_reg, float* __restrict__ d_cls, int rows,
-                                                                      const float* __restrict__ g_cls, const float* __restrict__ g_reg) {
-  const float gc = *g_cls, gr = *g_reg;
-  for (int i = blockIdx.x * V3D_BLOCK + threadIdx.x; i < rows * 8; i += gridDim.x * V3D_BLOCK) {
-    if (i < rows) d_cls[i] *= gc;
-    else d_reg[i - rows] *= gr;
-  }
-}
-
-#define RL_MAX_ROWS (1 << 24)  // (counts are reported as float; rows * 8 stays an int)
+#define RL_MAX_ROWS (1 << 24)  // (counts are reported as float)
 
 extern "C" int v3d_refine_loss_fwd_bwd(const float* R_reg, int ld_reg, const float* R_cls, int ld_cls, const float* G_conf,
                                        const float* G_reg, const uint8_t* M_cls, const uint8_t* M_reg, int rows, float* losses,
@@ -253,8 +218,11 @@ extern "C" int v3d_refine_loss_scale(float* dR_reg, float* dR_cls, int rows, con
   if (rows < 0 || rows > RL_MAX_ROWS || !g_cls || !g_reg) return V3D_EINVAL;
   if (rows == 0) return V3D_OK;
   if (!dR_reg || !dR_cls) return V3D_EINVAL;
-  hipLaunchKernelGGL(refine_loss_scale_kernel, dim3(std::min(64, v3d_ceil_div((long long)rows * 8, V3D_BLOCK))), dim3(V3D_BLOCK), 0,
-                     (hipStream_t)stream, dR_reg, dR_cls, rows, g_cls, g_reg);
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
+  // d_cls *= *g_cls, d_reg *= *g_reg: one launch where the two lie as [d_cls: rows | d_reg: rows * 7] (as the autograd node
+  // allocates them), else one each
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = rows;
+  if (dR_reg == dR_cls + n) return v3d_i_loss_scale(dR_cls, 1, 8 * n, n, g_cls, g_reg, 64, st);
+  const int rc = v3d_i_loss_scale(dR_cls, 1, n, n, g_cls, g_cls, 64, st);
+  return rc != V3D_OK ? rc : v3d_i_loss_scale(dR_reg, 1, 7 * n, 7 * n, g_reg, g_reg, 64, st);
 }

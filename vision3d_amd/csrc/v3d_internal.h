@@ -75,6 +75,11 @@ int v3d_i_nms_sorted(const void* prep_sorted, const int* order, int N, float iou
 
 int v3d_i_nms_mask_sorted(const void* prep_sorted, int N, float iou_threshold, unsigned long long* mask, hipStream_t st);
 
+// proposal_loss.hip: the backward of the fused losses (v3d_*_loss_scale).  buf = `groups` groups of `period` fp32 elements: the first
+// `head` of every group *= *g_head, the rest *= *g_tail (device scalars); about max_blocks workgroups at most.  groups, period > 0.
+int v3d_i_loss_scale(float* buf, int groups, long long period, long long head, const float* g_head, const float* g_tail, int max_blocks,
+                     hipStream_t st);
+
 // Arithmetic of the packed sparse kernels and of the dense head (split_prec.h, "the split-precision product"): bf16 pieces (2^-17 per
 // product, scale-free) or f16 pieces under per-tensor power-of-two scales (2^-22: fp32-class at the same three MFMAs).
 // (V3D_PREC_BF16X3 = 0 / V3D_PREC_F16S = 1: include/vision3d_hip.h)

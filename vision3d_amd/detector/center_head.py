@@ -16,6 +16,7 @@ from torch import nn
 
 from .. import _lib as L
 from ..ops import batched_nms_rotated_padded
+from .fused_loss import scale_gradient, take_gradient
 from .proposal import ProposalLayer, _raise_on_flag
 
 CENTERHEAD_DEFAULTS = dict(ENABLED=False, MIN_OVERLAP=0.1, MIN_RADIUS=2, FOCAL_ALPHA=2.0, FOCAL_BETA=4.0, CODE_WEIGHTS=[1.0] * 8,
@@ -205,18 +206,14 @@ class FusedCenterLossFunction(torch.autograd.Function):
             L.check(lib.v3d_center_loss_fwd_bwd(L.ptr(maps), L.ptr(heat), L.ptr(ind), L.ptr(mask), L.ptr(reg), b, n_cls, h, w, float(alpha),
                                                 float(beta), L.host_f32(code_weights), L.ptr(losses), L.ptr(dmaps), L.ptr(ws), ws.numel(),
                                                 L.stream_ptr()), "center_loss_fwd_bwd")
-        ctx.dmaps, ctx.geom = dmaps, (b, n_cls, h, w)
+        ctx.grad, ctx.geom = dmaps, (b, n_cls, h, w)
         return losses[0], losses[1]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_hm, g_reg):
-        dmaps, ctx.dmaps = ctx.dmaps, None
-        if dmaps is None:
-            raise RuntimeError("fused centre loss: backward called twice (the gradient buffer is consumed by the first call)")
-        gh, gr = g_hm.to(torch.float32).contiguous(), g_reg.to(torch.float32).contiguous()
-        with L.device_guard(dmaps.device):
-            L.check(L.lib().v3d_center_loss_scale(L.ptr(dmaps), *ctx.geom, L.ptr(gh), L.ptr(gr), L.stream_ptr()), "center_loss_scale")
+        dmaps = take_gradient(ctx, "centre")
+        scale_gradient("center_loss_scale", dmaps, (dmaps, *ctx.geom), (g_hm, g_reg))
         return (dmaps,) + (None,) * 8
 
 

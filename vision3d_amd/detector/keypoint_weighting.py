@@ -17,6 +17,7 @@ import torch
 from torch import nn
 
 from ..ops.focal_loss import sigmoid_focal_loss
+from .fused_loss import scale_gradient, take_gradient
 from .layers import MLP
 
 PKW_DEFAULTS = dict(ENABLED=False, MLPS=[256], GT_EXTRA_WIDTH=[0.2, 0.2, 0.2], FOCAL_ALPHA=0.25, FOCAL_GAMMA=2.0, LOSS_WEIGHT=1.0)
@@ -206,13 +207,8 @@ class FusedKeypointSegLossFunction(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_loss, _g_labels):
-        from .. import _lib as L
-        grad, ctx.grad = ctx.grad, None
-        if grad is None:
-            raise RuntimeError("fused keypoint segmentation loss: backward called twice (the gradient buffer is consumed by the first call)")
-        g = g_loss.to(torch.float32).contiguous()
-        with L.device_guard(grad.device):
-            L.check(L.lib().v3d_keypoint_seg_loss_scale(L.ptr(grad), ctx.rows, L.ptr(g), L.stream_ptr()), "keypoint_seg_loss_scale")
+        grad = take_gradient(ctx, "keypoint segmentation")
+        scale_gradient("keypoint_seg_loss_scale", grad, (grad, ctx.rows), (g_loss,))
         return grad, None, None, None, None, None, None
 
 

@@ -14,6 +14,7 @@ from torch import nn
 from .. import _lib as L
 from ..core.box_encode import decode
 from ..ops import batched_nms_rotated, batched_nms_rotated_padded, sigmoid_focal_loss
+from .fused_loss import scale_gradient, take_gradient
 
 
 _PINNED = {}
@@ -310,20 +311,14 @@ class FusedProposalLossFunction(torch.autograd.Function):
             L.check(lib.v3d_proposal_loss_fwd_bwd(L.ptr(maps), L.ptr(g_cls), L.ptr(m_cls), L.ptr(g_reg), L.ptr(m_reg), b, n_cls, n_yaw, h, w,
                                                   float(alpha), float(gamma), L.ptr(losses), L.ptr(dmaps), L.ptr(ws), ws.numel(),
                                                   L.stream_ptr()), "proposal_loss_fwd_bwd")
-        ctx.dmaps, ctx.geom = dmaps, (b, n_cls, n_yaw, h, w)
+        ctx.grad, ctx.geom = dmaps, (b, n_cls, n_yaw, h, w)
         return losses[0], losses[1]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_cls_loss, g_reg_loss):
-        from .. import _lib as L
-        dmaps, ctx.dmaps = ctx.dmaps, None
-        if dmaps is None:
-            raise RuntimeError("fused proposal loss: backward called twice (the gradient buffer is consumed by the first call)")
-        gc = g_cls_loss.to(torch.float32).contiguous()
-        gr = g_reg_loss.to(torch.float32).contiguous()
-        with L.device_guard(dmaps.device):
-            L.check(L.lib().v3d_proposal_loss_scale(L.ptr(dmaps), *ctx.geom, L.ptr(gc), L.ptr(gr), L.stream_ptr()), "proposal_loss_scale")
+        dmaps = take_gradient(ctx, "proposal")
+        scale_gradient("proposal_loss_scale", dmaps, (dmaps, *ctx.geom), (g_cls_loss, g_reg_loss))
         return (dmaps,) + (None,) * 8
 
 

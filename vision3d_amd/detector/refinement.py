@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..core.box_encode import decode, encode
+from .fused_loss import scale_gradient, take_gradient
 from .layers import MLP
 
 
@@ -72,29 +73,23 @@ class FusedRefinementLossFunction(torch.autograd.Function):
         cls, ld_cls = _rows(r_cls, 1)
         dev = r_reg.device
         losses = torch.empty(4, dtype=torch.float32, device=dev)
-        d_reg = torch.empty(r_reg.shape, dtype=torch.float32, device=dev)
-        d_cls = torch.empty(r_cls.shape, dtype=torch.float32, device=dev)
+        # both gradients in one buffer [d_cls: rows | d_reg: rows * 7]: backward scales them in one launch
+        grad = torch.empty(rows * 8, dtype=torch.float32, device=dev)
+        d_cls, d_reg = grad[:rows].view(r_cls.shape), grad[rows:].view(r_reg.shape)
         with L.device_guard(dev):
             L.check(L.lib().v3d_refine_loss_fwd_bwd(L.ptr(reg), ld_reg, L.ptr(cls), ld_cls, L.ptr(g_conf), L.ptr(g_reg), L.ptr(m_cls),
                                                     L.ptr(m_reg), rows, L.ptr(losses), L.ptr(d_reg), L.ptr(d_cls), L.stream_ptr()),
                     "refine_loss_fwd_bwd")
-        ctx.grads, ctx.rows = (d_reg, d_cls), rows
+        ctx.grad, ctx.rows, ctx.shapes = grad, rows, (r_cls.shape, r_reg.shape)
         ctx.counts = losses[2:4]  # (#M_rcls, #M_rreg) as the kernel counted them
         return losses[0], losses[1]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_cls_loss, g_reg_loss):
-        from .. import _lib as L
-        grads, ctx.grads = ctx.grads, None
-        if grads is None:
-            raise RuntimeError("fused refinement loss: backward called twice (the gradient buffers are consumed by the first call)")
-        d_reg, d_cls = grads
-        gc = g_cls_loss.to(torch.float32).contiguous()
-        gr = g_reg_loss.to(torch.float32).contiguous()
-        with L.device_guard(d_reg.device):
-            L.check(L.lib().v3d_refine_loss_scale(L.ptr(d_reg), L.ptr(d_cls), ctx.rows, L.ptr(gc), L.ptr(gr), L.stream_ptr()),
-                    "refine_loss_scale")
+        grad, rows = take_gradient(ctx, "refinement"), ctx.rows
+        d_cls, d_reg = grad[:rows].view(ctx.shapes[0]), grad[rows:].view(ctx.shapes[1])
+        scale_gradient("refine_loss_scale", grad, (d_reg, d_cls, rows), (g_cls_loss, g_reg_loss))
         return d_reg, d_cls, None, None, None, None
 
 
