@@ -117,17 +117,24 @@ def nms_margin(boxes, scores, thr):
     return float(lib().orc_nms_margin(_fp(boxes), _lp(order), boxes.shape[0], C.c_float(thr)))
 
 
-def batched_nms_rotated(boxes, scores, idxs, thr, use_ref=False):
-    """vision3d/ops/iou_nms.py:90-134 (coordinate-offset trick), numpy restatement."""
+def group_offset_boxes(boxes, idxs):
+    """vision3d/ops/iou_nms.py:127-133: every group's boxes moved by group * (coordinate range + 1) along x and y, in float32 --
+    boxes of different groups can then never overlap, and one plain NMS serves all groups."""
     boxes = _f32(boxes).reshape(-1, 5)
-    if boxes.size == 0:
-        return np.empty((0,), np.int64)
     mx = (np.maximum(boxes[:, 0], boxes[:, 1]) + np.maximum(boxes[:, 2], boxes[:, 3]) / np.float32(2)).max()
     mn = (np.minimum(boxes[:, 0], boxes[:, 1]) - np.minimum(boxes[:, 2], boxes[:, 3]) / np.float32(2)).min()
     offsets = np.asarray(idxs).astype(np.float32) * (mx - mn + np.float32(1))
     b = boxes.copy()
     b[:, :2] += offsets[:, None]
-    return nms_rotated(b, scores, thr, use_ref)
+    return b
+
+
+def batched_nms_rotated(boxes, scores, idxs, thr, use_ref=False):
+    """vision3d/ops/iou_nms.py:90-134 (coordinate-offset trick), numpy restatement."""
+    boxes = _f32(boxes).reshape(-1, 5)
+    if boxes.size == 0:
+        return np.empty((0,), np.int64)
+    return nms_rotated(group_offset_boxes(boxes, idxs), scores, thr, use_ref)
 
 
 # ---------------------------------------------------------------- voxelizer / VFE

@@ -100,8 +100,20 @@ def test_candidate_order_with_ties():
     # a single dominant anchor plus a 70 399-way tie below it
     maps[:, :cfg.NUM_YAW] = 2.0
     maps[0, 1, 5, 7] = 5.0
-    boxes2, _, _, scores2 = head.inference_native(dev(maps), anchors.cuda())
+    boxes2, bi2, ci2, scores2 = head.inference_native(dev(maps), anchors.cuda())
     np.testing.assert_array_equal(boxes2[0].cpu().numpy(), anchors[0, 1, 5, 7].numpy())
+    # ... and the whole output against the float64 statement: the dominant anchor, then the lowest-index anchors of the tie
+    import proposal_ref as R
+    thresh = [a["score_thresh"] for a in cfg.ANCHORS]
+    ref = R.stage(maps, anchors.numpy(), 1, 1, cfg.NUM_YAW, H, W, cfg.PROPOSAL.TOPK, thresh, 0.01)
+    R.assert_separated(maps[:, :cfg.NUM_YAW], thresh)
+    assert R.batched_margin(ref["bev"], ref["all_scores"], ref["groups"], 0.01) > 1e-5
+    assert 1 < len(ref["cand"]) < cfg.PROPOSAL.TOPK
+    assert boxes2.shape[0] == len(ref["cand"])
+    np.testing.assert_array_equal(boxes2.cpu().numpy(), ref["boxes"].astype(np.float32))  # zero deltas: box == anchor, bit for bit
+    np.testing.assert_array_equal(bi2.cpu().numpy(), ref["batch"])
+    np.testing.assert_array_equal(ci2.cpu().numpy(), ref["cls"])
+    np.testing.assert_allclose(scores2.cpu().numpy(), ref["scores"], rtol=1e-5, atol=1e-7)
 
 
 def test_graph_and_eager_native_paths_agree():

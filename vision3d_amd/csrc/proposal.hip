@@ -11,7 +11,13 @@
 //
 // Order semantics (the repository's spec where torch.topk leaves ties open): candidates of a group are ordered
 // by (sigmoid score descending, anchor index ascending), selected on the fp32 SIGMOID value exactly as the
-// reference selects (two logits that round to the same score are a tie).
+// reference selects (two logits that round to the same score are a tie: +20 and +30, +0.0 and -0.0).
+//
+// Non-finite logits: +inf scores 1.0 and -inf scores 0.0 like any other logit.  A NaN logit of either sign COUNTS AS -inf (score
+// 0.0, tied with the other zeros by anchor index, selected only when fewer than K other anchors exist): the frame is invalid
+// anyway, and torch's rule (NaN sorts first) would let a NaN-scored box suppress real ones before the score cut drops it.  The
+// replacement happens where level 1 loads a logit (prop_select), so no NaN key or score exists past that line -- which is what
+// the "every row is written" argument in prop_select rests on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -69,8 +75,17 @@ __device__ void prop_select(const float* __restrict__ x, const int* __restrict__
   for (int e = 0; e < EPT; e++) {
     const int i = tid + e * SEL_THREADS;
     xv[e] = i < n ? x[i] : 0.f;
+    if (LEVEL == 1 && xv[e] != xv[e]) xv[e] = -INFINITY;  // NaN counts as -inf (header): level 2 reads level-1 scores, never NaN
     kv[e] = prop_logit_key(xv[e]);
   }
+  // Every row i < Ke of cand[] is written below before the sort reads it.  Take the Ke in-range elements with the largest keys
+  // (the radix passes find the smallest of them, key `prefix`).  None is NaN, so each one's score compares >, == or < with s_t,
+  // and since the score does not decrease with the key (level 1: 1 / (1 + expf(-x)) with a monotone expf; level 2: the score is the key) none
+  // compares <.  So #{score > s_t} + #{score == s_t} >= Ke, while #{score > s_t} = n_gt < Ke (those lie strictly above the
+  // Ke-th key).  Phase A writes rows [0, n_gt); then either all ties fit (n_gt + ties == Ke rows, slots from the same counter)
+  // or the else branch writes rows n_gt + rank for every rank in [0, Ke - n_gt).  Each written row carries the position of an
+  // in-range element (i < n), so level 1 emits indices in [idx_base, idx_base + n) and level 2 forwards them through xi[pos];
+  // level 2's Ke-th largest row is a real one (the slices hold >= K real rows between them, sentinels score -1 < 0 <= s_t).
 
   float s_t = 0.f;
   if (Ke > 0) {
@@ -294,7 +309,9 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
         an[q] = ref_boxes[(size_t)t * 7 + q];
       }
     } else {
-      const int a = cand_anchor[t], yaw_i = a / g.HW, pix = a % g.HW;
+      // in [0, n_yaw * HW) by the argument in prop_select, which rests on a monotone expf; the clamp keeps the reads below in
+      // range without that assumption
+      const int a = min(max(cand_anchor[t], 0), g.n_yaw * g.HW - 1), yaw_i = a / g.HW, pix = a % g.HW;
 #pragma unroll
       for (int q = 0; q < 7; q++) {
         d[q] = maps[((size_t)b * g.ctot + n_anchor + (size_t)(c * 7 + q) * g.n_yaw + yaw_i) * g.HW + pix];

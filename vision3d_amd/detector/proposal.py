@@ -103,7 +103,8 @@ class ProposalLayer(nn.Module):
     def proposals_padded(self, cls_map, reg_map, anchors):
         """Everything up to (and including) NMS with NO host synchronisation: returns the B*n_cls*TOPK
         candidates (boxes, batch_idx, class_idx, scores) plus (keep padded, n_keep) on the device.  This is
-        the part that can live inside a captured HIP graph; `finalize` does the variable-length selection."""
+        the part that can live inside a captured HIP graph; `finalize` does the variable-length selection.
+        For a NaN logit this statement behaves differently from `native_proposals`: torch.topk sorts NaN first, the kernel last."""
         score_map = cls_map.sigmoid()
         B, n_cls = score_map.shape[:2]
         scores, anchor_idx = score_map.reshape(B, n_cls, -1).topk(self.TOPK, -1)
@@ -131,7 +132,9 @@ class ProposalLayer(nn.Module):
         the count and the plan's capacity verdict with ONE 8-byte copy.
         host_out (a PINNED int32 host tensor of two words, kept by the caller): the last kernel stores the pair straight into it
         (pinned memory is device-accessible) -- no copy is enqueued behind the frame at all; `finalize_native` synchronises the
-        stream and reads it."""
+        stream and reads it.
+        Non-finite logits: +inf scores 1.0 and -inf 0.0; a NaN class logit of either sign counts as -inf (score 0.0, tied with the
+        other zeros by anchor index, selected only when fewer than TOPK other anchors exist) -- never an out-of-range anchor."""
         cfg = self.cfg
         L.require_gpu("proposals", head_maps, anchors)
         maps, anc = L.as_f32("proposals", head_maps), L.as_f32("proposals", anchors)
