@@ -649,6 +649,33 @@ int v3d_refine_loss_fwd_bwd(const float* R_reg, int ld_reg, const float* R_cls, 
                             v3d_stream_t stream);
 int v3d_refine_loss_scale(float* dR_reg, float* dR_cls, int rows, const float* g_cls, const float* g_reg, v3d_stream_t stream);
 
+/* ---- Rotated 3-D IoU / DIoU loss of ALIGNED box pairs with its gradient (no upstream counterpart: the reference regresses box
+ * residuals under smooth-L1 only; this repository's definition, tests/iou_loss_ref.py).  Boxes (n, 7) f32 = (x, y, z, w, l, h, yaw),
+ * z = centre, yaw in RADIANS read geometrically (w along (cos yaw, sin yaw), as v3d_points_in_boxes) -- NOT the reading of
+ * v3d_box_iou_rotated_3d, which keeps the reference's.  Per pair: IoU = A_bev * overlap of the z extents / union of the volumes
+ * (0 where the union is not positive); term = 1 - IoU (kind V3D_IOU_LOSS_IOU) or 1 - IoU + rho2 / c2 (V3D_IOU_LOSS_DIOU: squared
+ * centre distance over the squared diagonal of the smallest world-aligned cuboid around both boxes).  A pair with a non-finite
+ * number or a size <= 0 (or whose fp32 arithmetic overflows) has IoU 0, term 1 and zero gradient.
+ * term (n), iou (n); d_pred / d_target (n, 7), each nullable: d term / d box, exact wherever term is differentiable, a finite
+ * one-sided value at kinks.  Any n >= 0; one launch, per-pair outputs only: no workspace, no reduction, no host synchronisation. */
+#define V3D_IOU_LOSS_IOU 0
+#define V3D_IOU_LOSS_DIOU 1
+int v3d_iou3d_loss_fwd_bwd(const float* pred, const float* target, int n, int kind, float* term, float* iou, float* d_pred,
+                           float* d_target, v3d_stream_t stream);
+
+/* The stage-2 IoU term of RefinementLoss (TRAIN.REFINEMENT_IOU_LOSS) and its gradient in ONE launch of one workgroup, like
+ * v3d_refine_loss_fwd_bwd.  rows = B * n RoIs.  R_reg: 7 residuals per row, row stride ld_reg floats (the head's (rows, 8) output
+ * read in place); proposals (rows, 7); gt_boxes (n_gt, 7); R_match (rows) i64 index into gt_boxes; M_reg (rows) u8.  Per row:
+ * pred = VoxelNet decode of the residuals against the proposal (xyz = d * (diag, diag, h_p) + xyz_p, wlh = exp(d) * wlh_p,
+ * yaw = d + yaw_p), term as above against gt_boxes[R_match].  Counted rows: M_reg set and 0 <= R_match < n_gt; the others add
+ * nothing and get zero gradient.  losses[2] = {sum of term over the counted rows / max(count, 1), count}; dR_reg (rows, 7)
+ * contiguous = d losses[0] / d R_reg through the decode (proposals and ground truths are constants); _scale multiplies it with
+ * the upstream gradient (device scalar).  Double sum in a fixed order: bit-repeatable.  No workspace, no host synchronisation. */
+int v3d_refine_iou_loss_fwd_bwd(const float* R_reg, int ld_reg, const float* proposals, const float* gt_boxes, int n_gt,
+                                const int64_t* R_match, const uint8_t* M_reg, int rows, int kind, float* losses, float* dR_reg,
+                                v3d_stream_t stream);
+int v3d_refine_iou_loss_scale(float* dR_reg, int rows, const float* g, v3d_stream_t stream);
+
 /* ---- Predicted Keypoint Weighting of PV-RCNN (arXiv 1912.13192 section 3.3; no upstream counterpart: model.py:72-74 hands every
  * keypoint to RoI-grid pooling with weight 1).  The definition is this repository's (detector/keypoint_weighting.py,
  * tests/keypoint_weighting_ref.py).  Replaces the last nn.Linear (H -> 1) of the head, the sigmoid and the broadcast multiply of

@@ -123,6 +123,9 @@ _SIGNATURES = {
     "v3d_refine_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_fwd_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_scale": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "v3d_iou3d_loss_fwd_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "v3d_refine_iou_loss_fwd_bwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "v3d_refine_iou_loss_scale": (_i, [_vp, _i, _vp, _vp]),
     "v3d_keypoint_weight": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "v3d_keypoint_seg_loss_fwd_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp]),
     "v3d_keypoint_seg_loss_scale": (_i, [_vp, _i, _vp, _vp]),

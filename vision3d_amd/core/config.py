@@ -111,7 +111,11 @@ def _defaults():
                       MLPS_REDUCTION=[16 * 192, 256, 256]),
         PROPOSAL=dict(C_IN=128, TOPK=100),
         REFINEMENT=dict(MLPS=[256, 128]),
-        TRAIN=dict(LR=1e-3, LAMBDA=1.0, EPOCHS=80, BATCH_SIZE=6, REFINEMENT_NUM_NEGATIVES=128),
+        # REFINEMENT_IOU_LOSS: rotated 3-D IoU loss on the DECODED stage-2 boxes (detector/refinement.py RefinementLoss, ops/iou_loss.py;
+        # not in the reference), opt-in: refine_iou_loss = mean over M_rreg of 1 - IoU(decode(R_reg, proposal), matched ground truth)
+        # (KIND "iou") or of 1 - IoU + centre distance^2 / enclosing diagonal^2 ("diou"), added to the stage-2 loss times WEIGHT
+        TRAIN=dict(LR=1e-3, LAMBDA=1.0, EPOCHS=80, BATCH_SIZE=6, REFINEMENT_NUM_NEGATIVES=128,
+                   REFINEMENT_IOU_LOSS=dict(ENABLED=False, KIND="iou", WEIGHT=1.0)),
         # OBJECT_NOISE: per-object ground-truth noise (dataset/augmentation.py ObjectNoiseAugmentation; VoxelNet 3.1 / SECOND, not in the
         # reference), opt-in: every box, with the points inside it, tries up to NUM_TRY poses -- translation ~ N(0, TRANSLATION_STD)
         # (x, y, z), yaw + U(ROTATION) -- and takes the first whose BEV IoU with every other box is <= COLLISION_IOU, or stays; runs

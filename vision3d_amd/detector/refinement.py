@@ -6,7 +6,8 @@ reference uses for every box residual (core/box_encode.py:13-23), with the propo
 
 Training (no upstream counterpart; the definition is this repository's, restated in tests/refine_targets_ref.py):
 `encode_refinements` inverts `apply_refinements`, `RefinementLoss` is the stage-2 loss over the targets of
-core/refinement_targets.py -- one native pass (csrc/refine_targets.hip) with the torch expressions kept beside it."""
+core/refinement_targets.py -- one native pass (csrc/refine_targets.hip) with the torch expressions kept beside it.  With
+TRAIN.REFINEMENT_IOU_LOSS enabled the loss gains a rotated 3-D IoU term on the decoded boxes (ops/iou_loss.py, csrc/iou_loss.hip)."""
 import math
 
 import torch
@@ -14,6 +15,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..core.box_encode import decode, encode
+from ..ops.iou_loss import KINDS as IOU_LOSS_KINDS, iou3d_loss_torch
 from .fused_loss import scale_gradient, take_gradient
 from .layers import MLP
 
@@ -93,18 +95,99 @@ class FusedRefinementLossFunction(torch.autograd.Function):
         return d_reg, d_cls, None, None, None, None
 
 
+class FusedRefinementIoULossFunction(torch.autograd.Function):
+    """The stage-2 IoU term and its gradient in one native pass (csrc/iou_loss.hip): (R_reg (..., 7), proposals (rows, 7), gt (G, 7),
+    R_match (rows) i64, M_rreg u8, kind) -> refine_iou_loss; per row the decode against the proposal, the pair term against the
+    matched ground truth and the chain rule back through the decode.  The kernel's count of the rows it took stays on the node as
+    `loss.grad_fn.counts`.  The gradient is computed with the forward; backward scales it with the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, r_reg, proposals, gt, match, m_reg, kind):
+        from .. import _lib as L
+        rows = match.numel()
+        reg, ld_reg = _rows(r_reg, 7)
+        dev = r_reg.device
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        grad = torch.empty(rows * 7, dtype=torch.float32, device=dev)
+        with L.device_guard(dev):
+            L.check(L.lib().v3d_refine_iou_loss_fwd_bwd(L.ptr(reg), ld_reg, L.ptr(proposals), L.ptr(gt), gt.shape[0], L.ptr(match),
+                                                        L.ptr(m_reg), rows, kind, L.ptr(losses), L.ptr(grad), L.stream_ptr()),
+                    "refine_iou_loss_fwd_bwd")
+        ctx.grad, ctx.rows, ctx.shape = grad, rows, r_reg.shape
+        ctx.counts = losses[1:2]  # (#rows counted) as the kernel counted them
+        return losses[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss):
+        grad = take_gradient(ctx, "refinement IoU")
+        scale_gradient("refine_iou_loss_scale", grad, (grad, ctx.rows), (g_loss,))
+        return grad.view(ctx.shape), None, None, None, None, None
+
+
 class RefinementLoss(nn.Module):
     """Stage-2 loss over (R_reg, R_cls) and the targets of RefinementTargetAssigner (G_conf, G_rreg, M_rcls, M_rreg):
     refine_cls_loss = sum over M_rcls of BCE-with-logits(R_cls, G_conf) / max(#M_rcls, 1) (PV-RCNN's IoU-guided confidence),
     refine_reg_loss = sum over M_rreg and the 7 components of smooth-L1 (beta 1) / max(#M_rreg, 1),
-    loss = refine_cls_loss + TRAIN.LAMBDA * refine_reg_loss."""
+    loss = refine_cls_loss + TRAIN.LAMBDA * refine_reg_loss.
+    With TRAIN.REFINEMENT_IOU_LOSS.ENABLED (the item then also needs proposals, R_match and the ground-truth boxes):
+    refine_iou_loss = sum over M_rreg of term(apply_refinements(R_reg, proposals), cat(boxes)[R_match]) / max(#M_rreg, 1), term =
+    1 - IoU (KIND "iou") or 1 - IoU + rho2 / c2 ("diou") of ops/iou_loss.py -- rotated 3-D IoU in the true geometry; proposals and
+    ground truths are constants, rows whose match is no ground truth are not counted --, and loss gains WEIGHT * refine_iou_loss."""
 
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
+        iou = cfg.TRAIN.get("REFINEMENT_IOU_LOSS") or {}  # (config files written before the term have no such key)
+        self.iou_enabled = bool(iou.get("ENABLED", False))
+        self.iou_kind, self.iou_weight = iou.get("KIND", "iou"), float(iou.get("WEIGHT", 1.0))
+        if self.iou_kind not in IOU_LOSS_KINDS:
+            raise ValueError(f"TRAIN.REFINEMENT_IOU_LOSS.KIND must be one of {sorted(IOU_LOSS_KINDS)}, got {self.iou_kind!r}")
 
-    def _result(self, cls_loss, reg_loss):
-        return dict(loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss, refine_cls_loss=cls_loss, refine_reg_loss=reg_loss)
+    def _result(self, cls_loss, reg_loss, iou_loss=None):
+        loss = cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss
+        if iou_loss is None:
+            return dict(loss=loss, refine_cls_loss=cls_loss, refine_reg_loss=reg_loss)
+        return dict(loss=loss + self.iou_weight * iou_loss, refine_cls_loss=cls_loss, refine_reg_loss=reg_loss, refine_iou_loss=iou_loss)
+
+    def _iou_inputs(self, item):
+        """-> (proposals (rows, 7), gt (G, 7), R_match (rows) i64), constants on the device of R_reg."""
+        missing = [k for k in ("proposals", "R_match", "boxes") if item.get(k) is None]
+        if missing:
+            raise RuntimeError(f"RefinementLoss: TRAIN.REFINEMENT_IOU_LOSS is enabled but the item has no {', '.join(missing)} "
+                               "(run the refinement target assigner on an item that holds the proposals and the ground-truth boxes)")
+        R_reg, boxes = item["R_reg"], item["boxes"]
+        boxes = [boxes] if torch.is_tensor(boxes) else list(boxes)
+        gt = torch.cat([torch.as_tensor(b).to(R_reg.device, torch.float32).reshape(-1, 7) for b in boxes]) if boxes \
+            else R_reg.new_zeros((0, 7), dtype=torch.float32)
+        proposals = item["proposals"].detach().to(R_reg.device, torch.float32).reshape(-1, 7)
+        match = item["R_match"].to(R_reg.device, torch.int64).reshape(-1)
+        if proposals.shape[0] != match.numel() or R_reg.numel() != 7 * match.numel():
+            raise RuntimeError("RefinementLoss: proposals, R_match and R_reg disagree on the number of RoIs")
+        return proposals.contiguous(), gt.contiguous(), match.contiguous()
+
+    def iou_term_torch(self, item):
+        """refine_iou_loss op by op in torch (any device / dtype of R_reg): decode, `iou3d_loss_torch`, masked mean.  A row whose
+        decoded box is not finite (an overflowing exp) counts with term 1 and passes no gradient, as in the native pass."""
+        R_reg, M_rreg = item["R_reg"], item["M_rreg"].ne(0).reshape(-1)
+        proposals, gt, match = self._iou_inputs(item)
+        proposals, gt, R = proposals.type_as(R_reg), gt.type_as(R_reg), R_reg.reshape(-1, 7)
+        counted = M_rreg & (match >= 0) & (match < gt.shape[0])
+        zero, one = R.new_zeros(()), R.new_ones(())
+        if gt.shape[0] == 0:
+            return torch.where(counted[:, None], R, zero).sum() * zero  # no ground truth at all: 0, still a function of R_reg
+        target = gt[match.clamp(0, gt.shape[0] - 1)]
+        with torch.no_grad():
+            use = counted & torch.isfinite(decode(R, proposals)).all(-1)
+        pred = decode(torch.where(use[:, None], R, zero), proposals)
+        term = torch.where(use, iou3d_loss_torch(pred, target, self.iou_kind), one)
+        return torch.where(counted, term, zero).sum() / counted.sum().clamp(min=1).type_as(R)
+
+    def _iou_fused(self, item):
+        R_reg, M_rreg = item["R_reg"], item["M_rreg"]
+        proposals, gt, match = self._iou_inputs(item)
+        as_u8 = lambda m: (m if m.dtype in (torch.bool, torch.uint8) else m.ne(0)).contiguous().view(torch.uint8)
+        return FusedRefinementIoULossFunction.apply(R_reg, proposals, gt, match, as_u8(M_rreg.reshape(-1)), IOU_LOSS_KINDS[self.iou_kind])
 
     def _fused(self, item):
         """The native pass applies to float32 predictions on the GPU with targets in the assigner's layout; else None."""
@@ -119,7 +202,7 @@ class RefinementLoss(nn.Module):
         as_u8 = lambda m: (m if m.dtype in (torch.bool, torch.uint8) else m.ne(0)).contiguous().view(torch.uint8)
         cls_loss, reg_loss = FusedRefinementLossFunction.apply(R_reg, R_cls.reshape(lead + (1,)), G_conf.contiguous(),
                                                               G_rreg.contiguous(), as_u8(M_rcls), as_u8(M_rreg))
-        return self._result(cls_loss, reg_loss)
+        return self._result(cls_loss, reg_loss, self._iou_fused(item) if self.iou_enabled else None)
 
     def forward_torch(self, item):
         """The same loss op by op in torch (any device / dtype): the fallback and the cross-check of the native pass."""
@@ -130,7 +213,7 @@ class RefinementLoss(nn.Module):
         cls_loss = torch.where(M_rcls, bce, zero).sum() / M_rcls.sum().clamp(min=1).type_as(R_reg)
         sl1 = F.smooth_l1_loss(R_reg, G_rreg.type_as(R_reg), reduction="none")
         reg_loss = torch.where(M_rreg.unsqueeze(-1), sl1, zero).sum() / M_rreg.sum().clamp(min=1).type_as(R_reg)
-        return self._result(cls_loss, reg_loss)
+        return self._result(cls_loss, reg_loss, self.iou_term_torch(item) if self.iou_enabled else None)
 
     def forward(self, item):
         fused = self._fused(item)
