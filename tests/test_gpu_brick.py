@@ -35,11 +35,9 @@ def _tables(L, nbr_dev, n_dev, cap):
     return tabs
 
 
-@pytest.mark.parametrize("order", ["morton", "shuffled"])
-def test_planner_tables_match_numpy(oracle, order):
+def _check_planner_tables(nbr):
+    """The planner's tables of the (n, 27) neighbour table `nbr` against their numpy statement -> ucnt."""
     from vision3d_amd import _lib as L
-    coords, shape = _stage2_sites(oracle, order)
-    nbr = oracle.subm_rulebook(coords, shape, 3)  # (n, 27)
     n = nbr.shape[0]
     nbr_dev = dev(np.ascontiguousarray(nbr.T), torch.int32)
     n_dev = torch.tensor([n], dtype=torch.int32, device="cuda")
@@ -66,10 +64,30 @@ def test_planner_tables_match_numpy(oracle, order):
     m = np.concatenate([nbr >= 0, np.zeros((pad, K), bool)]) if pad else nbr >= 0
     want_mask = (m.reshape(-1, 16, K).any(1) * (1 << np.arange(K, dtype=np.uint64))).sum(1).astype(np.uint32)
     np.testing.assert_array_equal(tmask, want_mask)
+    return ucnt
+
+
+@pytest.mark.parametrize("order", ["morton", "shuffled"])
+def test_planner_tables_match_numpy(oracle, order):
+    coords, shape = _stage2_sites(oracle, order)
+    ucnt = _check_planner_tables(oracle.subm_rulebook(coords, shape, 3))  # (n, 27)
     if order == "morton":
         assert ucnt.max() <= UMAX  # a spatial order keeps every neighbourhood inside the LDS slots
     else:
         assert (ucnt > UMAX).mean() > 0.5  # first-touch order of a shuffled sweep: the direct-gather body
+
+
+@pytest.mark.parametrize("n", [31, 33, 8191, 8193, 8225])
+def test_planner_tables_at_the_bitmap_scan_edges(n):
+    """The scan over the words of the planner's row bitmap (W = ceil(n / 32) words over 256 threads) on a synthetic table: W = 1 and 2
+    (255 and 254 threads own no word), 256 (one word each), 257 and 258 (two words per thread, the upper half of the threads none).
+    A third of the entries absent, a third rows nearby, a third any row: every pass sets bits in words of every wave."""
+    rng = np.random.default_rng(n)
+    near = np.clip(np.arange(n)[:, None] + rng.integers(-13, 14, (n, K)), 0, n - 1)
+    kind = rng.integers(0, 3, (n, K))
+    nbr = np.where(kind == 0, -1, np.where(kind == 1, near, rng.integers(0, n, (n, K)))).astype(np.int32)
+    ucnt = _check_planner_tables(nbr)
+    assert ucnt.max() > (UMAX if n > 8000 else 0)
 
 
 @pytest.mark.parametrize("order", ["morton", "shuffled"])

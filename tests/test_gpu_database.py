@@ -309,6 +309,33 @@ def test_batch_of_64_kitti_size_frames():
     check_against_restatement(frames, 8, 20000)
 
 
+def boxes_on_a_grid(n, points_of, seed):
+    """n boxes of 2 x 2 x 2 m, 4 m apart, any yaw; box g holds points_of(g) points (within 0.6 m of its centre: inside at every yaw)
+    -> one frame."""
+    rng = np.random.default_rng(seed)
+    g = np.arange(n)
+    boxes = np.stack([4.0 * (g % 16), 4.0 * (g // 16), np.zeros(n), *np.full((3, n), 2.0), rng.uniform(-3.0, 3.0, n)], 1)
+    owner = np.repeat(g, [points_of(i) for i in g])
+    pts = np.concatenate([boxes[owner, :3] + rng.uniform(-0.6, 0.6, (len(owner), 3)), rng.random((len(owner), 1))], 1)
+    pts = pts[rng.permutation(len(pts))].astype(np.float32)
+    return dict(points=pts, boxes=boxes, class_idx=np.zeros(n, np.int64))
+
+
+def test_256_boxes_every_third_kept():
+    """The scan over a frame's boxes (one thread per box, 256 = the limit): every third box holds 12 points and is kept, the others 3
+    and are dropped, so the kept boxes' first rows (rel_start) carry the sums across all three wave edges."""
+    frame = boxes_on_a_grid(256, lambda g: 12 if g % 3 == 0 else 3, 0)
+    check_against_restatement([frame], 8, 86 * 12)
+
+
+def test_batch_of_257_tiny_frames():
+    """257 frames of one box each, 8 points (5 of 7 frames) or 3 (dropped): the sums over the frames (db_locate, the rows before a
+    frame) take a second trip of 256 with a carry."""
+    frames = [boxes_on_a_grid(1, lambda g, f=f: 3 if f % 7 in (2, 5) else 8, f) for f in range(257)]
+    kept = sum(f % 7 not in (2, 5) for f in range(257))
+    check_against_restatement(frames, 4, kept * 8)
+
+
 # ---- 8
 def test_limits_and_cpu_tensors_are_refused(golden_db):
     from vision3d_amd.dataset import extract_objects

@@ -25,6 +25,22 @@ def test_fps_and_gather_exact(oracle):
         np.testing.assert_array_equal(furthest_point_sample(dev(p), k).cpu().numpy(), oracle.fps(p, k))
 
 
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1025, 1280, 1281, 4097])
+@pytest.mark.parametrize("xs", ["equal", "two_values"])
+def test_fps_one_bin_and_the_two_end_bins(oracle, n, xs):
+    """The counting sort of the slab kernel (1 024 x bins scanned by 256 threads) at its ends: all x equal -- every point in bin 0,
+    every other thread's base the whole cloud --, and x in {lo, hi} only -- bins 0 and 1 023, the last thread of the last wave.  N up
+    to 257 runs the plain kernel (the slab kernel starts at 1 025) and is kept as the same statement at a workgroup's edge; 1 025,
+    1 280 = 5 x 256 and 1 281 put the slabs' last positions on, before and behind a multiple of the 256 threads; 4 097 is the
+    32-slot instantiation."""
+    from vision3d_amd.pointnet2.pointnet2_utils import furthest_point_sample
+    rng = np.random.default_rng(n)
+    p = rng.standard_normal((2, n, 3)).astype(np.float32)
+    p[..., 0] = 3.25 if xs == "equal" else np.where(rng.random((2, n)) < 0.5, -7.5, 11.0)
+    k = min(n, 64)
+    np.testing.assert_array_equal(furthest_point_sample(dev(p), k).cpu().numpy(), oracle.fps(p, k))
+
+
 def test_ball_query_and_group_exact(oracle):
     from vision3d_amd.pointnet2.pointnet2_utils import ball_query, grouping_operation
     rng = np.random.default_rng(1)
@@ -464,6 +480,29 @@ def test_ball_query_grid_equals_scan_ragged_and_degenerate(n, m, ra, nsa, rb, ns
     qw = wide[:, torch.randint(0, n, (m,), generator=g)].contiguous() + 0.01
     (sa, sb), (ga, gb) = _both_algos(lambda PU: PU.ball_query_pair(ra, nsa, rb, nsb, wide, qw))
     assert torch.equal(sa, ga) and torch.equal(sb, gb)
+
+
+@pytest.mark.parametrize("n", [65, 4096])
+@pytest.mark.parametrize("first", ["half", "one"])
+def test_ball_query_grid_equals_scan_two_corner_clusters(n, first):
+    """The key scan of the grid build (1 024 threads, 16 waves) where a base can go wrong: two tight clusters at opposite corners of
+    the database's bounds, the low corner holding the first rows and the high corner the last, so that of each index chunk only the
+    first or the last cell is occupied and the last key's base is every other point; then one point in the first cell and all others
+    in the last.  Two frames, nsample 16, grid == scan."""
+    g = torch.Generator().manual_seed(n)
+    n_lo = n // 2 if first == "half" else 1
+    xyz = torch.rand(2, n, 3, generator=g) * 0.3
+    xyz[:, n_lo:, :2] += 60.0
+    xyz[:, 0, :2] = 0.0  # the corners themselves
+    xyz[:, -1, :2] = 60.3
+    pick = torch.cat([torch.tensor([0, n - 1]), torch.randint(0, n, (62,), generator=g)])
+    new_xyz = (xyz[:, pick] + 0.02).cuda().contiguous()
+    xyz = xyz.cuda()
+    (sa, sb), (ga, gb) = _both_algos(lambda PU: PU.ball_query_pair(0.1, 16, 0.5, 16, xyz, new_xyz))
+    assert torch.equal(sa, ga) and torch.equal(sb, gb)
+    assert (gb != 0).any()
+    s1, g1 = _both_algos(lambda PU: PU.ball_query(0.5, 16, xyz, new_xyz))
+    assert torch.equal(s1, g1) and torch.equal(g1, gb)
 
 
 def test_ball_query_grids_of_several_databases_in_one_launch():

@@ -97,6 +97,33 @@ def test_query_of_a_database_elsewhere_and_of_an_empty_one():
     assert ((idx % 3 == 2) | (idx == -1)).all() and (idx >= 0).any()
 
 
+def test_query_of_two_corner_clusters_and_an_empty_frame():
+    """The scan over the cells of a frame's grid (16 384 cells, 1 024 threads of 16 cells) where a base can go wrong: the support rows
+    in two clusters at opposite corners of their bounds, 127.5 reaches apart along x and y, so that the grid has 128 x 128 cells of
+    which the first and the last are occupied -- the last thread's base is every row before its own --; the second frame holds no
+    finite row.  idx exactly against the restatement on the decidable centres; the empty frame finds nothing."""
+    voxels, radius = (3, 3, 3), 0.4
+    reach = radius * (2.0 - 1.0 / 3.0) * (1.0 + 1e-5) + 1e-3  # the cell edge vector_pool.hip derives from (voxels, radius)
+    span = 127.5 * reach
+    rng = np.random.default_rng(5)
+    n = C.N_ROWS + C.N_DUP
+    lo = np.array([20.0, -3.0, -2.0])
+    rows = lo + rng.random((n, 3)) * np.array([0.5, 0.5, 1.2])
+    rows[n // 2:, :2] += span - 0.5
+    rows[0, :2], rows[-1, :2] = lo[:2], lo[:2] + span  # the corners of the bounds
+    rows[-C.N_DUP:-1] = rows[rng.integers(0, C.N_ROWS, C.N_DUP - 1)]
+    xyz = np.stack([rows, np.full((n, 3), np.nan)]).astype(np.float32)
+    q = rows[rng.integers(0, n, (C.B, C.M))] + rng.uniform(-0.3, 0.3, (C.B, C.M, 3))
+    q = q.astype(np.float32)
+    want, _, und = R.query(xyz[:1], q[:1], voxels, radius)
+    assert und.mean() <= 0.02
+    idx, w = _native(xyz, q, voxels, radius)
+    np.testing.assert_array_equal(idx[:1][~und], want[~und])
+    for half in (slice(0, n // 2), slice(n // 2, n)):  # both corners are found
+        assert ((idx[0] >= half.start) & (idx[0] < half.stop)).any()
+    assert (idx[1] == -1).all() and (w[1].view(np.uint32) == 0).all()
+
+
 @pytest.mark.parametrize("cr,cl,g", [(1, 16, 0), (4, 32, 1), (32, 16, 2), (32, 32, 3), (4, 16, 3), (1, 32, 2)])
 def test_embed_against_float64(cr, cl, g):
     """Reduction + embedding of one group on the native neighbours against the float64 restatement on the same neighbours, under

@@ -47,6 +47,13 @@ def test_ragged_batch_edges(oracle):
     compare(gpu_voxelize(clouds, synth.KITTI_BOUNDS), oracle_voxelize(oracle, clouds, synth.KITTI_BOUNDS))
 
 
+def test_two_frames_of_more_than_256_chunks(oracle):
+    """66 000 points in two frames: 258 chunks of 256 points, so the batch path's scan over the chunks' published counts takes a
+    second trip of 256 with a carry (the ragged batch above has 148 chunks)."""
+    clouds = [synth.make_cloud(10, 33000), synth.make_cloud(11, 33000)]
+    compare(gpu_voxelize(clouds, synth.KITTI_BOUNDS, 5, 40000), oracle_voxelize(oracle, clouds, synth.KITTI_BOUNDS, 5, 40000))
+
+
 def test_max_voxels_clip_and_small_max_pts(oracle):
     clouds = [synth.make_cloud(6), synth.make_cloud(7)[:3000], synth.make_cloud(8)]
     compare(gpu_voxelize(clouds, synth.KITTI_BOUNDS, 3, 2500), oracle_voxelize(oracle, clouds, synth.KITTI_BOUNDS, 3, 2500))

@@ -221,14 +221,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void aug_points_kernel(const float4* __r
     int total;
     const int rank = v3d_block_rank(out, total, lds);
     if (tid == 0) v3d_publish_count(w.chunk_counts + b, total);
-    int part = 0;
-    for (int q = tid; q < b; q += V3D_BLOCK) part += v3d_wait_count(w.chunk_counts + q);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    __syncthreads();
-    if ((tid & 63) == 0) lds[tid >> 6] = part;
-    __syncthreads();
-    const int prefix = lds[0] + lds[1] + lds[2] + lds[3];
+    const int prefix = v3d_wait_prefix(w.chunk_counts, b, lds);  // (v3d_block_rank left lds free)
     if (b == n_chunks - 1 && tid == 0) w.head[2] = prefix + total;
     if (out) {
       double x = p.x, y = p.y, z = p.z;
@@ -238,13 +231,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void aug_points_kernel(const float4* __r
     return;
   }
   // ---- the kept samples' points, behind ALL kept scene points
-  int part = 0;
-  for (int q = tid; q < n_chunks; q += V3D_BLOCK) part += v3d_wait_count(w.chunk_counts + q);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-  if ((tid & 63) == 0) lds[tid >> 6] = part;
-  __syncthreads();
-  const int base = lds[0] + lds[1] + lds[2] + lds[3];
+  const int base = v3d_wait_prefix(w.chunk_counts, n_chunks, lds);
   const int all = w.cum[k], sblocks = gridDim.x - n_chunks;
   for (int q = (b - n_chunks) * V3D_BLOCK + tid; q < all; q += sblocks * V3D_BLOCK) {
     int lo = 0, hi = k;  // the sample j with cum[j] <= q < cum[j + 1]

@@ -67,17 +67,9 @@ __global__ __launch_bounds__(256) void brick_plan_kernel(const int* __restrict__
   const int w_lo = min(tid * wpt, W), w_hi = min(w_lo + wpt, W);
   int local = 0;
   for (int w = w_lo; w < w_hi; w++) local += __popc(bm[w]);
-  int incl = local;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = incl - local;
-  for (int w = 0; w < wave; w++) base += wsum[w];
-  if (tid == 0) ucnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  int total;
+  int base = v3d_block_scan_incl<4>(local, total, wsum) - local;
+  if (tid == 0) ucnt[blockIdx.x] = total;
   int* ul = ulist + (size_t)blockIdx.x * BRK_UMAX;
   for (int w = w_lo; w < w_hi; w++) {
     pre[w] = base;

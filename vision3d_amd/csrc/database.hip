@@ -51,27 +51,11 @@ static __host__ __device__ inline DbWork db_work(void* base, int n_points, int n
 
 __device__ __forceinline__ int db_chunks(int n) { return n <= 0 ? 1 : (n + DB_CHUNK - 1) / DB_CHUNK; }
 
-// inclusive scan of one int per thread over the 256-thread block; `lds` >= 4 ints, free on return
+// inclusive scan of one int per thread over the 256-thread block, with the barrier behind it: `lds` >= 4 ints, free on return
 __device__ __forceinline__ int db_block_scan(int v, int& total, int* lds) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) lds[w] = incl;
+  const int incl = v3d_block_scan_incl<DB_WAVES>(v, total, lds);
   __syncthreads();
-  int woff = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < DB_WAVES; i++) {
-    const int c = lds[i];
-    if (i < w) woff += c;
-    tot += c;
-  }
-  __syncthreads();
-  total = tot;
-  return woff + incl;
+  return incl;
 }
 
 // sum over i < n of value(i), to every thread

@@ -1,26 +1,11 @@
 // loss_device.h -- the arithmetic the fused training losses share (proposal_loss.hip, refine_targets.hip, keypoint_weight.hip,
-// center_head.hip), stated once: the fixed-order workgroup sum, the logistic front end, BCE-with-logits, the sigmoid focal loss
+// center_head.hip), stated once: the fixed-order workgroup sum (v3d_block_sum: scan_device.h), the logistic front end, BCE-with-logits, the sigmoid focal loss
 // (ops/focal_loss.py) and smooth-L1, each with its gradient.  fp32, one IEEE operation per operator as written (-ffp-contract=off
 // is project-wide, so inlining changes no rounding): the float64 restatements under tests/ check these expressions.
 #pragma once
 #include <hip/hip_runtime.h>
 
-// Sum of v over a workgroup of WAVES waves, returned to every thread.  The order is fixed -- an xor butterfly inside the wave, then
-// the waves in index order through `red` (>= WAVES entries of LDS) --, which is what makes the losses bit-repeatable.  Every
-// thread of the workgroup calls it, at a workgroup-uniform point; it opens with the barrier that lets `red` be reused by the
-// next sum while slow waves still read the previous one.
-template <int WAVES, typename T>
-__device__ __forceinline__ T v3d_block_sum(T v, T* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  T t = 0;
-#pragma unroll
-  for (int w = 0; w < WAVES; w++) t += red[w];
-  return t;
-}
+#include "scan_device.h"  // v3d_block_sum: the fixed-order workgroup sum
 
 // The logistic front end: e = expf(-|x|) never overflows; sigmoid(x) from it by one division.
 __device__ __forceinline__ float v3d_sigmoid(float x, float& e) {

@@ -141,16 +141,8 @@ __global__ __launch_bounds__(FPS_SLAB_THREADS) void fps_slab_kernel(const float*
   int cnt[BPT], mine = 0;
 #pragma unroll
   for (int i = 0; i < BPT; i++) { cnt[i] = bin_cnt[tid * BPT + i]; mine += cnt[i]; }
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = incl - mine;
-  for (int w = 0; w < wave; w++) base += wsum[w];
+  int binned;  // (= N)
+  int base = v3d_block_scan_incl<NW>(mine, binned, wsum) - mine;
 #pragma unroll
   for (int i = 0; i < BPT; i++) {
     // slab boundaries: sorted positions 256 j (first) and 256 j + 255 (last) lie in the bins whose runs cover them
@@ -646,16 +638,8 @@ __global__ __launch_bounds__(BQG_BUILD_THREADS) void bq_grid_build_kernel(const 
   int sum = 0;
   for (int k = 0; k < kpt; k++)
     if (k_lo + k < BQG_MAX_KEYS) sum += cnt[k_lo + k];
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int run = incl - sum;
-  for (int i = 0; i < wave; i++) run += wsum[i];
+  int binned;  // the number of binned points
+  int run = v3d_block_scan_incl<BQG_BUILD_THREADS / V3D_WAVE>(sum, binned, wsum) - sum;
   for (int k = 0; k < kpt; k++) {
     const int c = k_lo + k;
     if (c < BQG_MAX_KEYS) {
@@ -664,11 +648,10 @@ __global__ __launch_bounds__(BQG_BUILD_THREADS) void bq_grid_build_kernel(const 
       run += own;
     }
   }
-  if (tid == BQG_BUILD_THREADS - 1) wsum[0] = run;  // the number of binned points
   __syncthreads();
   // the table as the queries read it: coalesced, not a thread's kpt consecutive words (the scan's layout: one 64-byte line per lane
   // and store instruction -- 30 us of a 45 us build at 26 000 keys); entry nkeys = the number of binned points
-  for (int c = tid; c <= nkeys; c += BQG_BUILD_THREADS) cell_start[c] = c < nkeys ? cnt[c] : wsum[0];
+  for (int c = tid; c <= nkeys; c += BQG_BUILD_THREADS) cell_start[c] = c < nkeys ? cnt[c] : binned;
   __syncthreads();
   // (d) scatter (the order inside a key's run is whatever the atomics give: the queries do not depend on it)
   for_points([&](int i, float x, float y, float z) { sorted[atomicAdd(&cnt[key_of(i, x, y)], 1)] = make_float4(x, y, z, __int_as_float(i)); });
@@ -680,12 +663,7 @@ __device__ __forceinline__ void bq_bitmap_emit(unsigned* __restrict__ bm, int wp
   unsigned* mine = bm + lane * wpl;
   int cnt = 0;
   for (int k = 0; k < wpl; k++) cnt += __popc(mine[k]);
-  int incl = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int up = __shfl_up(incl, d);
-    if (lane >= d) incl += up;
-  }
+  const int incl = v3d_wave_scan_incl(cnt);
   const int total = __shfl(incl, 63);
   int pos = incl - cnt, first = 0;
   const unsigned long long holders = __ballot(cnt > 0);
@@ -758,12 +736,8 @@ __global__ __launch_bounds__(BQG_WAVES * 64) void bq_grid_query_kernel(const flo
           len = cell_start[ch * ncell + row * g.nx + c1 + 1] - s_run;
         }
       }
-      int pre = len;  // inclusive prefix over the runs: positions in the query's candidate sequence
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const int up = __shfl_up(pre, d);
-        if (lane >= d) pre += up;
-      }
+      static_assert(3 * BQG_MAX_CHUNKS <= 32, "the runs of a query fit the scanned lanes");
+      const int pre = v3d_wave_scan_incl<32>(len);  // inclusive prefix over the runs (lanes < 3 * BQG_MAX_CHUNKS): positions in the query's candidate sequence
       int cnt_a = 0, cnt_b = 0;
       // (run r of the walk below is wave-uniform: v_readlane, not a trip through the LDS crossbar per value -- 72 of them per sparse query)
       auto lane_of = [](int v, int l) { return __builtin_amdgcn_readlane(v, l); };

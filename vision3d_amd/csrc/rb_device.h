@@ -268,12 +268,7 @@ __device__ __forceinline__ void rb_scan_emit_body(const int4* __restrict__ coord
   const long long t0 = base + (long long)tid * RB_PER_THREAD;
   const unsigned flags = live ? rb_first_flags(cand_slot, first_ticket, t0, nt) : 0u;
   const int mine = __popc(flags);
-  int incl = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int t = __shfl_up(incl, off);
-    if (lane >= off) incl += t;
-  }
+  const int incl = v3d_wave_scan_incl(mine);
   if (lane == 63) lds[w] = incl;
   __syncthreads();
   const int cnt = lds[0] + lds[1] + lds[2] + lds[3];
@@ -301,16 +296,7 @@ __device__ __forceinline__ void rb_scan_emit_body(const int4* __restrict__ coord
     c0 = coords[(int)(t / g.Kc)];
   }
   asm volatile("" ::: "memory");  // (the loads above stay in front of the spin below)
-  int part = 0;
-  {
-    const int n_live = (int)((nt + V3D_SCAN_CHUNK - 1) / V3D_SCAN_CHUNK);
-    for (int i = tid; i < min(b, n_live); i += V3D_BLOCK) part += v3d_wait_count(chunk_counts + i);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if (lane == 0) s_part[w] = part;
-  }
-  __syncthreads();
-  const int prefix = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+  const int prefix = v3d_wait_prefix(chunk_counts, min(b, (int)((nt + V3D_SCAN_CHUNK - 1) / V3D_SCAN_CHUNK)), s_part);  // (the live predecessors)
   if (last && tid == 0) {
     const int total = prefix + cnt;
     if (total > cap_out) {

@@ -135,22 +135,15 @@ __global__ __launch_bounds__(V3D_BLOCK) void vpq_bin_kernel(const float* __restr
 // One workgroup per frame: start[c + 1] (counts) -> inclusive sums in place (start[0] = 0), cursor[c] = start[c].
 __global__ __launch_bounds__(VPQ_SCAN_THREADS) void vpq_scan_kernel(VpqLayout L) {
   constexpr int PER = VPQ_CELLS / VPQ_SCAN_THREADS;
-  __shared__ int sums[VPQ_SCAN_THREADS];
+  __shared__ int wsum[VPQ_SCAN_THREADS / V3D_WAVE];
   const int b = blockIdx.x, tid = threadIdx.x;
   int* start = L.start + (size_t)b * (VPQ_CELLS + 1);
   int* cursor = L.cursor + (size_t)b * VPQ_CELLS;
   int v[PER], run = 0;
 #pragma unroll
   for (int k = 0; k < PER; k++) v[k] = start[1 + tid * PER + k], run += v[k];
-  sums[tid] = run;
-  __syncthreads();
-  for (int off = 1; off < VPQ_SCAN_THREADS; off <<= 1) {  // Hillis-Steele over the threads' totals
-    const int add = tid >= off ? sums[tid - off] : 0;
-    __syncthreads();
-    sums[tid] += add;
-    __syncthreads();
-  }
-  int base = sums[tid] - run;  // rows before this thread's cells
+  int rows;
+  int base = v3d_block_scan_incl<VPQ_SCAN_THREADS / V3D_WAVE>(run, rows, wsum) - run;  // rows before this thread's cells
 #pragma unroll
   for (int k = 0; k < PER; k++) {
     cursor[tid * PER + k] = base;

@@ -191,13 +191,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
   if constexpr (CHAINED) {
     __shared__ int s_part[V3D_BLOCK / V3D_WAVE];
     asm volatile("" ::: "memory");  // (the loads above are issued in front of the spin)
-    int part = 0;
-    for (int cb = threadIdx.x; cb < (int)blockIdx.x; cb += V3D_BLOCK) part += v3d_wait_count(chunk_offsets + cb);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = part;
-    __syncthreads();
-    const int prefix = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    const int prefix = v3d_wait_prefix(chunk_offsets, (int)blockIdx.x, s_part);
     rank += prefix;
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_voxels = min(prefix + tot, p.max_voxels);
   } else {
