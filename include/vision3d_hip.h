@@ -88,6 +88,19 @@ int v3d_proposals_flag(const float* head_maps, const float* anchors, int B, int 
  * Workspace: v3d_proposals_workspace. */
 int v3d_proposals_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                        float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+/* The same two calls for a head with a direction classifier (cfg.DIRECTION of vision3d_amd/detector/proposal.py; the sine-error loss
+ * + direction classifier of the SECOND paper, which upstream's ProposalLayer leaves out): head_maps (B, n_cls*n_yaw*9, H, W) =
+ * [cls | reg | dir], the direction logit of anchor (c, yaw) in channel n_cls*n_yaw*8 + c*n_yaw + yaw.  They replace the yaw of
+ * core/box_encode.py:21 (anchor yaw + residual, right only modulo pi under that loss) by
+ *   remainder(anchor yaw + residual - dir_offset, pi) + dir_offset + pi * [dir logit > 0]     (strict: +-0 and NaN give 0),
+ * in [dir_offset, dir_offset + 2 pi), fp32 with (float)M_PI.  Everything else -- selection, the other six components, NMS, score cut,
+ * launches, workspace -- is that of v3d_proposals_flag / v3d_proposals_topk. */
+int v3d_proposals_dir_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                           const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                           int64_t* out_class_idx, float* out_scores, int32_t* n_out /*[2]*/, const int32_t* aux_flag,
+                           void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset);
+int v3d_proposals_dir_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                           float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset);
 /* Stage-2 tail on candidates in that layout: refined = core/box_encode.py:13-21 decode of `deltas` against `proposals` (written to
  * `refined` (N, 7) when not NULL), score = sigmoid(conf), coordinate-offset batched rotated NMS per (frame, class) group
  * (ops/iou_nms.py:90-134), per-class score cut; outputs as v3d_proposals (padded to N rows, decreasing score, *n_out valid).
@@ -126,6 +139,13 @@ int v3d_assign_targets(const float* gt_boxes, const int64_t* gt_class, int n_gt,
                        int anchors_per_class, const float* iou_thresh_host, int allow_low_quality, int8_t* G_cls, uint8_t* M_cls,
                        float* G_reg, uint8_t* M_reg, int64_t* matches, void* workspace, size_t workspace_bytes,
                        v3d_stream_t stream);
+
+/* Direction targets of the anchor head (cfg.DIRECTION; no upstream counterpart -- the reference's ProposalTargetAssigner,
+ * core/proposal_targets.py:10-88, emits none): one elementwise launch over the outputs of v3d_assign_targets.  matches / M_reg (n) as
+ * that call wrote them, gt_boxes (n_gt, 7).  G_dir (n) i8: at M_reg the direction bit of the matched ground truth's ABSOLUTE yaw t,
+ * floor(remainder(t - offset, 2 pi) / pi) in {0, 1} (fp32, (float)M_PI); 0 elsewhere and where a match is not in [0, n_gt). */
+int v3d_direction_targets(const float* gt_boxes, int n_gt, const int64_t* matches, const uint8_t* M_reg, int64_t n, float offset,
+                          int8_t* G_dir, v3d_stream_t stream);
 
 /* ---- Stage-2 (RoI) targets of PV-RCNN in ONE launch, a workgroup per frame; upstream's core/refinement_targets.py raises
  * (SURVEY.md H11), so the definition is this repository's (tests/refine_targets_ref.py).  No (n x g) matrix, no workspace.
@@ -635,6 +655,20 @@ int v3d_proposal_loss_fwd_bwd(const float* maps, const int8_t* g_cls, const uint
                               void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 int v3d_proposal_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
                             v3d_stream_t stream);
+
+/* The same loss for a head with a direction classifier (cfg.DIRECTION; replaces ProposalLoss.forward of vision3d_amd/detector/proposal.py
+ * with DIRECTION enabled -- upstream's detector/proposal.py:100-141 has neither term): maps (B, n_cls * n_yaw * 9, H, W) = [cls | reg |
+ * dir], direction channel n_cls * n_yaw * 8 + cls * n_yaw + yaw; g_dir i8 (> 0 = bit 1) in the layout of g_cls.  cls_loss as above;
+ * reg_loss as above, with sin_yaw != 0 the yaw column's smooth-L1 argument is sin(P_yaw - G_yaw) (gradient smooth_l1'(sin D) cos D);
+ * dir_loss = sum over M_reg of max(x, 0) - x g + log1p(exp(-|x|)) / max(#M_reg, 1), gradient sigmoid(x) - g.  losses[4] = cls_loss,
+ * reg_loss, dir_loss, normalizer; dmaps = the three gradients in their channel groups.  _scale multiplies the three groups with
+ * their upstream gradients (device scalars; one: a device 1.0f) -- four launches of the two-way scale kernel.  fp32, bit-repeatable. */
+size_t v3d_proposal_dir_loss_workspace(void);
+int v3d_proposal_dir_loss_fwd_bwd(const float* maps, const int8_t* g_cls, const uint8_t* m_cls, const float* g_reg, const uint8_t* m_reg,
+                                  const int8_t* g_dir, int sin_yaw, int B, int n_cls, int n_yaw, int H, int W, float alpha, float gamma,
+                                  float* losses, float* dmaps, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+int v3d_proposal_dir_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
+                                const float* g_dir, const float* one, v3d_stream_t stream);
 
 /* ---- RefinementLoss (PV-RCNN stage 2; this repository's definition, tests/refine_targets_ref.py) and its gradient in ONE launch.
  * rows = B * n RoIs.  R_reg: 7 residuals per row, row stride ld_reg floats; R_cls: one confidence logit per row, stride ld_cls

@@ -30,6 +30,8 @@ _SIGNATURES = {
     "v3d_proposals": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_proposals_flag": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_proposals_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_proposals_dir_flag": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _f]),
+    "v3d_proposals_dir_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _f]),
     "v3d_refine_nms_workspace": (_sz, [_i, _i, _i]),
     "v3d_refine_nms": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_sparse_bn_workspace": (_sz, [_i, _i]),
@@ -37,6 +39,7 @@ _SIGNATURES = {
     "v3d_sparse_bn_relu_bwd": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_assign_targets_workspace": (_sz, [_i, _i, _i]),
     "v3d_assign_targets": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_direction_targets": (_i, [_vp, _i, _vp, _vp, C.c_int64, _f, _vp, _vp]),
     "v3d_points_in_boxes": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp]),
     "v3d_augment_work_bytes": (_sz, [_i, _i, _i]),
     "v3d_augment_frame": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -120,6 +123,9 @@ _SIGNATURES = {
     "v3d_proposal_loss_workspace": (_sz, []),
     "v3d_proposal_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "v3d_proposal_loss_scale": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "v3d_proposal_dir_loss_workspace": (_sz, []),
+    "v3d_proposal_dir_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_proposal_dir_loss_scale": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "v3d_refine_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_fwd_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_scale": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

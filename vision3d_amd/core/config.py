@@ -97,6 +97,13 @@ def _defaults():
         # rotated NMS at NMS_IOU and the score_thresh of ANCHORS
         CENTERHEAD=dict(ENABLED=False, MIN_OVERLAP=0.1, MIN_RADIUS=2, FOCAL_ALPHA=2.0, FOCAL_BETA=4.0, CODE_WEIGHTS=[1.0] * 8,
                         NMS_IOU=0.01),
+        # direction classifier + sine yaw loss of the SECOND paper for the anchor head (detector/proposal.py; not in the reference), opt-in:
+        # the encoded yaw residual is right only modulo pi, so one more logit per anchor says which half turn -- target = the bit
+        # floor(remainder(yaw - OFFSET, 2 pi) / pi) of the matched ground truth's absolute yaw (core/proposal_targets.py G_dir), loss =
+        # BCE-with-logits over the positives times LOSS_WEIGHT; decode = remainder(anchor yaw + residual - OFFSET, pi) + OFFSET + pi * [logit
+        # > 0].  SIN_YAW: the yaw column of the box loss takes sin(P_yaw - G_yaw) as its smooth-L1 argument (no cliff between residuals 0
+        # and pi).  The default OFFSET puts the bin edges on the diagonals, away from the axis-aligned headings and both anchor yaws
+        DIRECTION=dict(ENABLED=False, OFFSET=0.7853981634, SIN_YAW=True, LOSS_WEIGHT=0.2),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",

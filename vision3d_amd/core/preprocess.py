@@ -67,7 +67,7 @@ class Preprocessor(nn.Module):
 class TrainPreprocessor(Preprocessor):
 
     def collate_mapping(self, key, val):
-        if key in ("G_cls", "G_reg", "M_cls", "M_reg"):
+        if key in ("G_cls", "G_reg", "M_cls", "M_reg", "G_dir"):
             return torch.stack(val)
         return val
 

@@ -3,8 +3,11 @@
 `forward` runs the fused device kernels of csrc/targets.hip (IoU, column/row maxima, band labels, low-quality
 rule and box encoding in two launches, no n_gt x 70 400 matrix); `forward_torch` is the op-by-op statement of the
 reference (IoU matrix in csrc/iou_nms.hip + torch Matcher/encode) kept as the on-device cross-check.
-Emits G_cls/M_cls (n_cls, n_yaw, ny, nx), G_reg (..., 7), M_reg (..., 1).
+Emits G_cls/M_cls (n_cls, n_yaw, ny, nx), G_reg (..., 7), M_reg (..., 1) and, with cfg.DIRECTION.ENABLED, G_dir int8 in the shape
+of G_cls: the direction bit of the matched ground truth's absolute yaw at the positives, 0 elsewhere.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -14,6 +17,20 @@ from .anchor_generator import AnchorGenerator
 from .box_encode import encode
 
 BEV = [0, 1, 3, 4, 6]  # (x, y, w, l, yaw): yaw stays in radians although the op reads degrees (H1)
+DIRECTION_DEFAULTS = dict(ENABLED=False, OFFSET=0.7853981634, SIN_YAW=True, LOSS_WEIGHT=0.2)
+
+
+def direction_config(cfg):
+    """-> the keys of cfg.DIRECTION over their defaults (a config written before the key existed means "disabled")."""
+    out = dict(DIRECTION_DEFAULTS)
+    out.update(cfg.get("DIRECTION") or {})
+    return out
+
+
+def direction_bit(yaw, offset):
+    """floor(remainder(yaw - offset, 2 pi) / pi) in {0, 1}, in the dtype of `yaw` (fp32: pi = (float)M_PI, as csrc/targets.hip)."""
+    pi = yaw.new_tensor(math.pi)
+    return torch.remainder(yaw - yaw.new_tensor(offset), 2 * pi) >= pi
 
 
 class ProposalTargetAssigner(nn.Module):
@@ -23,6 +40,7 @@ class ProposalTargetAssigner(nn.Module):
         self.cfg = cfg
         self.anchors = AnchorGenerator(cfg).anchors.cuda()
         self.matchers = [Matcher(a["iou_thresh"], [0, -1, +1], cfg.ALLOW_LOW_QUALITY_MATCHES) for a in cfg.ANCHORS]
+        self.direction = direction_config(cfg)
 
     def compute_iou(self, boxes, anchors):
         return box_iou_rotated(boxes[:, BEV].contiguous(), anchors[:, BEV].contiguous())
@@ -55,6 +73,12 @@ class ProposalTargetAssigner(nn.Module):
         G_reg[pos] = encode(boxes[box_idx[pos]], self.anchors[pos])
         return G_reg, pos.unsqueeze(-1)
 
+    def get_dir_targets(self, boxes, box_idx, G_cls):
+        pos = G_cls == 1
+        G_dir = torch.zeros(G_cls.shape, dtype=torch.int8, device=G_cls.device)
+        G_dir[pos] = direction_bit(boxes[box_idx[pos]][:, 6].float(), self.direction["OFFSET"]).to(torch.int8)
+        return G_dir
+
     def forward(self, item):
         """Fused path: two launches of csrc/targets.hip."""
         dev = self.anchors.device
@@ -69,13 +93,19 @@ class ProposalTargetAssigner(nn.Module):
         M_cls = torch.empty(shape, dtype=torch.bool, device=dev)
         G_reg = torch.empty(self.anchors.shape, dtype=torch.float32, device=dev)
         M_reg = torch.empty(shape + (1,), dtype=torch.bool, device=dev)
+        matches = torch.empty(shape, dtype=torch.int64, device=dev) if self.direction["ENABLED"] else None
         lib = L.lib()
         ws = L.workspace(lib.v3d_assign_targets_workspace(n_gt, n_cls, A), dev)
         thresh = L.host_f32([t for a in self.cfg.ANCHORS[:n_cls] for t in a["iou_thresh"]])
         with torch.cuda.device(dev):
             L.check(lib.v3d_assign_targets(L.ptr(boxes), L.ptr(class_idx), n_gt, L.ptr(self.anchors), n_cls, A, thresh,
                                            int(bool(self.cfg.ALLOW_LOW_QUALITY_MATCHES)), L.ptr(G_cls), L.ptr(M_cls), L.ptr(G_reg),
-                                           L.ptr(M_reg), 0, L.ptr(ws), ws.numel(), L.stream_ptr()), "assign_targets")
+                                           L.ptr(M_reg), L.ptr(matches), L.ptr(ws), ws.numel(), L.stream_ptr()), "assign_targets")
+            if matches is not None:
+                G_dir = torch.empty(shape, dtype=torch.int8, device=dev)
+                L.check(lib.v3d_direction_targets(L.ptr(boxes), n_gt, L.ptr(matches), L.ptr(M_reg), matches.numel(),
+                                                  float(self.direction["OFFSET"]), L.ptr(G_dir), L.stream_ptr()), "direction_targets")
+                item["G_dir"] = G_dir
         item.update(G_cls=G_cls, G_reg=G_reg, M_cls=M_cls, M_reg=M_reg)
         return item
 
@@ -85,5 +115,7 @@ class ProposalTargetAssigner(nn.Module):
         box_idx, G_cls = self.match_all_classes(boxes, class_idx, box_ignore)
         G_cls, M_cls = self.get_cls_targets(G_cls)
         G_reg, M_reg = self.get_reg_targets(boxes, box_idx, G_cls)
+        if self.direction["ENABLED"]:
+            item["G_dir"] = self.get_dir_targets(boxes, box_idx, G_cls)
         item.update(G_cls=G_cls, G_reg=G_reg, M_cls=M_cls, M_reg=M_reg)
         return item

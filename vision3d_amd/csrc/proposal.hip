@@ -36,9 +36,21 @@
 #endif  // upper bound of level-1 slices per (frame, class) group (40 x topk 100 <= 4096 merge inputs)
 
 struct PropGeom {
-  int B, n_cls, n_yaw, HW, topk, ctot;  // ctot = n_cls*n_yaw*(1+7) channels of the fused head map
+  int B, n_cls, n_yaw, HW, topk, ctot;  // ctot = n_cls*n_yaw*(1+7) channels of the fused head map, (1+7+1) with a direction classifier
   float thresh[PROP_MAX_CLS];
+  int dir_base;      // first direction channel (n_cls*n_yaw*8: v3d_proposals_dir_*), -1 = the head has none
+  float dir_offset;  // cfg.DIRECTION.OFFSET
 };
+
+// Yaw of a head with a direction classifier (cfg.DIRECTION): raw = anchor yaw + residual is right modulo pi (the sine loss leaves the
+// half turns open); its representative in [offset, offset + pi) plus pi where the direction logit is positive.  The comparison is
+// strict: +0.0, -0.0 and NaN give bit 0.  fmodf is exact; the result lies in [offset, offset + 2 pi) up to the rounding of the sums.
+__device__ __forceinline__ float prop_dir_yaw(float raw, float offset, float dir_logit) {
+  const float pi = 3.14159274101257324f;  // (float)M_PI
+  float r = fmodf(raw - offset, pi);
+  if (r < 0.f) r += pi;
+  return r + offset + (dir_logit > 0.f ? pi : 0.f);
+}
 
 __device__ __forceinline__ float prop_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }  // torch: 1 / (1 + exp(-x))
 __device__ __forceinline__ unsigned prop_logit_key(float x) {                               // order-preserving
@@ -326,6 +338,12 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
     o[4] = expf(d[4]) * an[4];
     o[5] = expf(d[5]) * an[5];
     o[6] = d[6] + an[6];
+    if constexpr (!REFINE) {
+      if (g.dir_base >= 0) {  // a kernel argument: uniform over the workgroup
+        const int a = min(max(cand_anchor[t], 0), g.n_yaw * g.HW - 1), yaw_i = a / g.HW, pix = a % g.HW;
+        o[6] = prop_dir_yaw(o[6], g.dir_offset, maps[((size_t)b * g.ctot + g.dir_base + (size_t)c * g.n_yaw + yaw_i) * g.HW + pix]);
+      }
+    }
 #pragma unroll
     for (int q = 0; q < 7; q++) boxes[(size_t)t * 7 + q] = o[q];
     batch_idx[t] = b;
@@ -545,7 +563,7 @@ extern "C" int v3d_proposals(const float* head_maps, const float* anchors, int B
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores);
+                    float* topk_boxes, float* topk_scores, bool dir = false, float dir_offset = 0.f);
 
 extern "C" int v3d_proposals_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W,
                                   int topk, const float* score_thresh_host, float iou_threshold, float* out_boxes,
@@ -563,10 +581,30 @@ extern "C" int v3d_proposals_topk(const float* head_maps, const float* anchors, 
                   workspace_bytes, stream, boxes, scores);
 }
 
+// The two entry points for a head with a direction classifier (cfg.DIRECTION): head_maps (B, n_cls*n_yaw*9, H, W) = [cls | reg | dir],
+// the direction logit of anchor (c, yaw) in channel n_cls*n_yaw*8 + c*n_yaw + yaw.  Selection, the other six box components, NMS (a
+// rectangle turned by pi is the same rectangle) and the score cut are those of v3d_proposals_flag / _topk: same launches, same workspace.
+extern "C" int v3d_proposals_dir_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                                      const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                                      int64_t* out_class_idx, float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace,
+                                      size_t workspace_bytes, v3d_stream_t stream, float dir_offset) {
+  if (!score_thresh_host || !out_boxes || !out_batch_idx || !out_class_idx || !out_scores || !n_out) return V3D_EINVAL;
+  return prop_run(head_maps, anchors, B, n_cls, n_yaw, H, W, topk, score_thresh_host, iou_threshold, out_boxes, out_batch_idx, out_class_idx,
+                  out_scores, n_out, aux_flag, workspace, workspace_bytes, stream, nullptr, nullptr, true, dir_offset);
+}
+
+extern "C" int v3d_proposals_dir_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                                      float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
+                                      float dir_offset) {
+  if (!boxes || !scores) return V3D_EINVAL;
+  return prop_run(head_maps, anchors, B, n_cls, n_yaw, H, W, topk, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
+                  workspace_bytes, stream, boxes, scores, true, dir_offset);
+}
+
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores) {
+                    float* topk_boxes, float* topk_scores, bool dir, float dir_offset) {
   hipStream_t st = (hipStream_t)stream;
   if (!head_maps || !anchors || !workspace) return V3D_EINVAL;
   if (B < 1 || n_cls < 1 || n_cls > PROP_MAX_CLS || n_yaw < 1 || H < 1 || W < 1 || topk < 1 || topk > PROP_MAX_TOPK)
@@ -575,7 +613,8 @@ static int prop_run(const float* head_maps, const float* anchors, int B, int n_c
   if ((long long)n_yaw * H * W < topk) return V3D_EINVAL;  // torch.topk raises as well
   if (workspace_bytes < v3d_proposals_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
   PropGeom g;
-  g.B = B; g.n_cls = n_cls; g.n_yaw = n_yaw; g.HW = H * W; g.topk = topk; g.ctot = n_cls * n_yaw * 8;
+  g.B = B; g.n_cls = n_cls; g.n_yaw = n_yaw; g.HW = H * W; g.topk = topk; g.ctot = n_cls * n_yaw * (dir ? 9 : 8);
+  g.dir_base = dir ? n_cls * n_yaw * 8 : -1; g.dir_offset = dir_offset;
   for (int c = 0; c < PROP_MAX_CLS; c++) g.thresh[c] = (c < n_cls && score_thresh_host) ? score_thresh_host[c] : 0.f;
   const size_t N = (size_t)B * n_cls * topk;
   char* p = (char*)workspace;
@@ -652,7 +691,7 @@ extern "C" int v3d_refine_nms(const float* deltas, const float* proposals, const
   if ((long long)B * n_cls * topk > PROP_THREADS) return V3D_EUNSUPPORTED;  // one workgroup decodes and sorts all candidates
   if (workspace_bytes < v3d_refine_nms_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
   PropGeom g;
-  g.B = B; g.n_cls = n_cls; g.n_yaw = 1; g.HW = 1; g.topk = topk; g.ctot = 0;
+  g.B = B; g.n_cls = n_cls; g.n_yaw = 1; g.HW = 1; g.topk = topk; g.ctot = 0; g.dir_base = -1; g.dir_offset = 0.f;
   for (int c = 0; c < PROP_MAX_CLS; c++) g.thresh[c] = c < n_cls ? score_thresh_host[c] : 0.f;
   const size_t N = (size_t)B * n_cls * topk;
   char* p = (char*)workspace;

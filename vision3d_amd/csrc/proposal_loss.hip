@@ -7,8 +7,11 @@
 // 7.4 ms step); here: count the positives, one pass that writes the gradient of both terms with respect to the FUSED head maps
 // (B, n_cls * n_yaw * (1 + 7), H, W) and per-workgroup partial sums, one merge in a fixed order.  fp32, bit-repeatable.  The focal
 // and smooth-L1 expressions and the workgroup sum are those of loss_device.h.
+// With a direction classifier (cfg.DIRECTION, v3d_proposal_dir_loss_*): the same chain over (B, n_cls * n_yaw * 9, H, W) maps with a
+// third term, BCE-with-logits of the direction logit over M_reg, and optionally the sine yaw argument -- pl_main_kernel<true>.
 //   class channel of anchor (cls, yaw):            cls * n_yaw + yaw
 //   box channel d of anchor (cls, yaw):  n_anchor + (cls * 7 + d) * n_yaw + yaw          (ProposalLayer.reshape_cls / reshape_reg)
+//   direction channel of anchor (cls, yaw):        n_anchor * 8 + cls * n_yaw + yaw      (ProposalLayer.dir_from_fused)
 #include "loss_device.h"
 #include "v3d_internal.h"
 
@@ -33,17 +36,23 @@ __global__ void pl_count_merge_kernel(const int* __restrict__ partial, int block
 }
 
 // thread = anchor (b, a = cls * n_yaw + yaw, pixel); dmaps gets d(cls_loss)/d(map) in the class channels and d(reg_loss)/d(map) in
-// the box channels (each already divided by the normalizer); partial[block] = (sum of focal terms, sum of box terms) of the block
+// the box channels (each already divided by the normalizer); partial[block] = (sum of focal terms, sum of box terms) of the block.
+// DIR (cfg.DIRECTION, v3d_proposal_dir_loss_fwd_bwd): the maps carry one direction logit per anchor behind the box channels
+// (channel n_anchor * 8 + a); its BCE-with-logits against g_dir over M_reg is the third term of dmaps and of partial[block], and with
+// sin_yaw the yaw column's smooth-L1 argument is sin(P_yaw - G_yaw) (gradient: the clamped argument times cos) -- nothing else differs.
+template <bool DIR>
 __global__ __launch_bounds__(V3D_BLOCK) void pl_main_kernel(const float* __restrict__ maps, const signed char* __restrict__ g_cls,
                                                             const unsigned char* __restrict__ m_cls, const float* __restrict__ g_reg,
-                                                            const unsigned char* __restrict__ m_reg, int B, int n_cls, int n_yaw, int HW,
-                                                            float alpha, float gamma, const float* __restrict__ normalizer,
-                                                            float* __restrict__ dmaps, float* __restrict__ partial) {
+                                                            const unsigned char* __restrict__ m_reg, const signed char* __restrict__ g_dir,
+                                                            int sin_yaw, int B, int n_cls, int n_yaw, int HW, float alpha, float gamma,
+                                                            const float* __restrict__ normalizer, float* __restrict__ dmaps,
+                                                            float* __restrict__ partial) {
   __shared__ float red[PL_WAVES];
-  const int n_anchor = n_cls * n_yaw, O = n_anchor * (1 + PL_DOF);
+  constexpr int NT = DIR ? 3 : 2;  // loss terms
+  const int n_anchor = n_cls * n_yaw, O = n_anchor * (1 + PL_DOF + (DIR ? 1 : 0));
   const long long total = (long long)B * n_anchor * HW;
   const float inv_n = 1.f / *normalizer;
-  float s_cls = 0.f, s_reg = 0.f;
+  float s_cls = 0.f, s_reg = 0.f, s_dir = 0.f;
   for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * V3D_BLOCK) {
     const int pix = (int)(i % HW);
     const int a = (int)((i / HW) % n_anchor), b = (int)(i / ((long long)HW * n_anchor));
@@ -69,24 +78,47 @@ __global__ __launch_bounds__(V3D_BLOCK) void pl_main_kernel(const float* __restr
       if (pos) {
         const float wd = d == PL_DOF - 1 ? 3.f / 3.14159265358979323846f : 1.f;
         float clamped;
-        s_reg += wd * v3d_smooth_l1(maps[ir] - g[d], clamped);
+        if (DIR && d == PL_DOF - 1 && sin_yaw) {
+          const float diff = maps[ir] - g[d];
+          s_reg += wd * v3d_smooth_l1(sinf(diff), clamped);
+          clamped *= cosf(diff);
+        } else {
+          s_reg += wd * v3d_smooth_l1(maps[ir] - g[d], clamped);
+        }
         gd = wd * clamped * inv_n;
       }
       dmaps[ir] = gd;
     }
+    // ---- direction term
+    if constexpr (DIR) {
+      const size_t id = mb + ((size_t)n_anchor * (1 + PL_DOF) + a) * HW + pix;
+      float gq = 0.f;
+      if (pos) {
+        const float xd = maps[id], t = g_dir[i] > 0 ? 1.f : 0.f;
+        float e;
+        const float prob = v3d_sigmoid(xd, e);
+        s_dir += v3d_bce_logits(xd, t, e);
+        gq = (prob - t) * inv_n;
+      }
+      dmaps[id] = gq;
+    }
   }
   const float t_cls = v3d_block_sum<PL_WAVES>(s_cls, red);
   const float t_reg = v3d_block_sum<PL_WAVES>(s_reg, red);
-  if (threadIdx.x < 2) partial[blockIdx.x * 2 + threadIdx.x] = threadIdx.x == 0 ? t_cls : t_reg;
+  float t_dir = 0.f;
+  if constexpr (DIR) t_dir = v3d_block_sum<PL_WAVES>(s_dir, red);
+  if (threadIdx.x < NT) partial[blockIdx.x * NT + threadIdx.x] = threadIdx.x == 0 ? t_cls : (threadIdx.x == 1 ? t_reg : t_dir);
 }
 
+// losses[0 .. NT) = the terms' sums over the blocks (fixed order, double) / normalizer; losses[NT] = the normalizer
+template <int NT>
 __global__ void pl_finalize_kernel(const float* __restrict__ partial, int blocks, const float* __restrict__ normalizer,
                                    float* __restrict__ losses) {
-  if (blockIdx.x == 0 && threadIdx.x < 2) {
+  if (blockIdx.x == 0 && threadIdx.x < NT) {
     double t = 0.0;
-    for (int i = 0; i < blocks; i++) t += (double)partial[i * 2 + threadIdx.x];
+    for (int i = 0; i < blocks; i++) t += (double)partial[i * NT + threadIdx.x];
     losses[threadIdx.x] = (float)(t / (double)*normalizer);
-    if (threadIdx.x == 0) losses[2] = *normalizer;
+    if (threadIdx.x == 0) losses[NT] = *normalizer;
   }
 }
 
@@ -130,9 +162,9 @@ extern "C" int v3d_proposal_loss_fwd_bwd(const float* maps, const int8_t* g_cls,
   const int blocks = (int)std::min<long long>(PL_BLOCKS, (n + V3D_BLOCK - 1) / V3D_BLOCK);
   hipLaunchKernelGGL(pl_count_kernel, dim3(blocks), dim3(V3D_BLOCK), 0, st, m_reg, n, counts);
   hipLaunchKernelGGL(pl_count_merge_kernel, dim3(1), dim3(64), 0, st, counts, blocks, normalizer);
-  hipLaunchKernelGGL(pl_main_kernel, dim3(blocks), dim3(V3D_BLOCK), 0, st, maps, (const signed char*)g_cls, m_cls, g_reg, m_reg, B, n_cls,
-                     n_yaw, H * W, alpha, gamma, normalizer, dmaps, partial);
-  hipLaunchKernelGGL(pl_finalize_kernel, dim3(1), dim3(64), 0, st, partial, blocks, normalizer, losses);
+  hipLaunchKernelGGL(pl_main_kernel<false>, dim3(blocks), dim3(V3D_BLOCK), 0, st, maps, (const signed char*)g_cls, m_cls, g_reg, m_reg,
+                     (const signed char*)nullptr, 0, B, n_cls, n_yaw, H * W, alpha, gamma, normalizer, dmaps, partial);
+  hipLaunchKernelGGL(pl_finalize_kernel<2>, dim3(1), dim3(64), 0, st, partial, blocks, normalizer, losses);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }
@@ -142,4 +174,47 @@ extern "C" int v3d_proposal_loss_scale(float* dmaps, int B, int n_cls, int n_yaw
   if (!dmaps || !g_cls || !g_reg || B < 1 || n_cls < 1 || n_yaw < 1 || H < 1 || W < 1) return V3D_EINVAL;
   const long long head = (long long)n_cls * n_yaw * H * W, period = head * (1 + PL_DOF);
   return v3d_i_loss_scale(dmaps, B, period, head, g_cls, g_reg, 2048, (hipStream_t)stream);
+}
+
+// ---- the same loss of a head with a direction classifier (cfg.DIRECTION): maps (B, n_cls * n_yaw * 9, H, W) = [cls | reg | dir]
+extern "C" size_t v3d_proposal_dir_loss_workspace(void) { return (size_t)PL_BLOCKS * (3 * sizeof(float) + sizeof(int)) + 256; }
+
+// g_dir int8 (> 0 = bit 1) in the layout of g_cls; sin_yaw != 0: the sine yaw term.  losses[4] = cls_loss, reg_loss, dir_loss, normalizer
+extern "C" int v3d_proposal_dir_loss_fwd_bwd(const float* maps, const int8_t* g_cls, const uint8_t* m_cls, const float* g_reg,
+                                             const uint8_t* m_reg, const int8_t* g_dir, int sin_yaw, int B, int n_cls, int n_yaw, int H, int W,
+                                             float alpha, float gamma, float* losses, float* dmaps, void* workspace, size_t workspace_bytes,
+                                             v3d_stream_t stream) {
+  if (!maps || !g_cls || !m_cls || !g_reg || !m_reg || !g_dir || !losses || !dmaps || !workspace || B < 1 || n_cls < 1 || n_yaw < 1 || H < 1 ||
+      W < 1)
+    return V3D_EINVAL;
+  if (workspace_bytes < v3d_proposal_dir_loss_workspace()) return V3D_EWORKSPACE;
+  const long long n = (long long)B * n_cls * n_yaw * H * W;
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = (float*)workspace;
+  int* counts = (int*)(partial + 3 * PL_BLOCKS);
+  float* normalizer = losses + 3;
+  const int blocks = (int)std::min<long long>(PL_BLOCKS, (n + V3D_BLOCK - 1) / V3D_BLOCK);
+  hipLaunchKernelGGL(pl_count_kernel, dim3(blocks), dim3(V3D_BLOCK), 0, st, m_reg, n, counts);
+  hipLaunchKernelGGL(pl_count_merge_kernel, dim3(1), dim3(64), 0, st, counts, blocks, normalizer);
+  hipLaunchKernelGGL(pl_main_kernel<true>, dim3(blocks), dim3(V3D_BLOCK), 0, st, maps, (const signed char*)g_cls, m_cls, g_reg, m_reg,
+                     (const signed char*)g_dir, sin_yaw, B, n_cls, n_yaw, H * W, alpha, gamma, normalizer, dmaps, partial);
+  hipLaunchKernelGGL(pl_finalize_kernel<3>, dim3(1), dim3(64), 0, st, partial, blocks, normalizer, losses);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+// Three channel groups, three upstream gradients, on the two-way loss_scale_kernel: each call multiplies one group by its factor and
+// the rest by *one (a device 1.0f of the caller: x * 1 is exact), so every element meets exactly one factor other than 1.  The class
+// and direction groups are the head and the tail of a frame's period.  The box group lies in between: it is the head of the periods
+// that start one class group later, of which the last one would end behind the buffer -- that frame's box group is a call of its own.
+extern "C" int v3d_proposal_dir_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
+                                           const float* g_dir, const float* one, v3d_stream_t stream) {
+  if (!dmaps || !g_cls || !g_reg || !g_dir || !one || B < 1 || n_cls < 1 || n_yaw < 1 || H < 1 || W < 1) return V3D_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const long long a = (long long)n_cls * n_yaw * H * W, box = a * PL_DOF, period = a + box + a;
+  int rc = v3d_i_loss_scale(dmaps, B, period, a, g_cls, one, 2048, st);
+  if (rc == V3D_OK) rc = v3d_i_loss_scale(dmaps, B, period, a + box, one, g_dir, 2048, st);
+  if (rc == V3D_OK && B > 1) rc = v3d_i_loss_scale(dmaps + a, B - 1, period, box, g_reg, one, 2048, st);
+  if (rc == V3D_OK) rc = v3d_i_loss_scale(dmaps + (B - 1) * period + a, 1, box, box, g_reg, g_reg, 2048, st);
+  return rc;
 }

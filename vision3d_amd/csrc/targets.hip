@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/vision3d_hip.h"
 #include "rotated_iou.h"
 #include "v3d_common.h"
@@ -167,6 +169,31 @@ extern "C" int v3d_assign_targets(const float* gt_boxes, const int64_t* gt_class
                      best_gt, gt_max);
   hipLaunchKernelGGL(ta_label_kernel, grid, dim3(V3D_BLOCK), 0, st, gt_boxes, (const long long*)gt_class, anchors, p, best_iou,
                      best_gt, gt_max, (signed char*)G_cls, M_cls, G_reg, M_reg, (long long*)matches);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+// Direction targets of the anchor head (cfg.DIRECTION; detector/proposal.py): at a positive anchor the direction bit of its matched
+// ground truth's ABSOLUTE yaw t, bit(t) = floor(remainder(t - offset, 2 pi) / pi) in {0, 1}; 0 everywhere else.  One elementwise
+// launch over the `matches` / M_reg outputs of v3d_assign_targets.
+__global__ __launch_bounds__(V3D_BLOCK) void ta_direction_kernel(const float* __restrict__ gt, int n_gt, const long long* __restrict__ matches,
+                                                                 const unsigned char* __restrict__ M_reg, long long n, float offset,
+                                                                 signed char* __restrict__ G_dir) {
+  const float pi = 3.14159274101257324f;
+  for (long long i = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; i < n; i += (long long)gridDim.x * V3D_BLOCK) {
+    signed char bit = 0;
+    const long long g = matches[i];
+    if (M_reg[i] && g >= 0 && g < n_gt) bit = ta_remainder(gt[7 * g + 6] - offset, 2.f * pi) >= pi ? 1 : 0;
+    G_dir[i] = bit;
+  }
+}
+
+extern "C" int v3d_direction_targets(const float* gt_boxes, int n_gt, const int64_t* matches, const uint8_t* M_reg, int64_t n, float offset,
+                                     int8_t* G_dir, v3d_stream_t stream) {
+  if (n_gt < 0 || n < 1 || !matches || !M_reg || !G_dir || (n_gt > 0 && !gt_boxes)) return V3D_EINVAL;
+  const int blocks = (int)std::min<long long>(1024, (n + V3D_BLOCK - 1) / V3D_BLOCK);
+  hipLaunchKernelGGL(ta_direction_kernel, dim3(blocks), dim3(V3D_BLOCK), 0, (hipStream_t)stream, gt_boxes, n_gt, (const long long*)matches,
+                     M_reg, (long long)n, offset, (signed char*)G_dir);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

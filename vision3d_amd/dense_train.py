@@ -80,15 +80,17 @@ def why_unsupported(rpn, head, bev, precision="bf16"):
                 return f"RPN BatchNorm {i}: running statistics are not fp32 tensors on the input's device"
         if b.weight.dtype != torch.float32 or off_device(b.weight) or off_device(c.weight):
             return f"RPN layer {i}: parameters are not fp32 tensors on the input's device"
-    for conv in (head.conv_cls, head.conv_reg):
+    from .detector.proposal import fused_convs
+    for conv in fused_convs(head):
         if conv.kernel_size != (1, 1) or conv.in_channels != 128 or conv.bias is None or conv.stride != (1, 1):
             return "head convolutions are not biased 1x1 convolutions on 128 channels"
         if (conv.weight.dtype != torch.float32 or conv.bias.dtype != torch.float32 or off_device(conv.weight)
                 or off_device(conv.bias)):
             return "head parameters are not fp32 tensors on the input's device"
-    if (head.conv_cls.out_channels + head.conv_reg.out_channels) not in (8, 16, 24, 32, 48, 64):
-        return "fused head width is not one of 8, 16, 24, 32, 48, 64"
-    if precision == "bf16x3" and head.conv_cls.out_channels + head.conv_reg.out_channels > 16:
+    width = sum(conv.out_channels for conv in fused_convs(head))
+    if width not in (8, 16, 24, 32, 48, 64):  # (18 and 54, a head with a direction classifier, among them: it trains through torch)
+        return f"fused head width {width} is not one of 8, 16, 24, 32, 48, 64"
+    if precision == "bf16x3" and width > 16:
         return "fused head wider than 16 channels (the split path's head kernel)"
     return None
 
@@ -100,7 +102,9 @@ class DenseTrainPlan(object):
         self.rpn, self.head = rpn, head
         self.convs, self.bns, _ = rpn_pairs(rpn)
         self.B, self.H, self.W, self.device = int(B), int(H), int(W), device
-        self.O = head.conv_cls.out_channels + head.conv_reg.out_channels
+        from .detector.proposal import fused_convs
+        self.head_convs = fused_convs(head)  # the head's 1x1 convolutions in the channel order of the fused map
+        self.O = sum(c.out_channels for c in self.head_convs)
         self.split = precision == "bf16x3"
         arena_bytes = getattr(L.lib(), "v3d_dense_train_arena_bytes_split" if self.split else "v3d_dense_train_arena_bytes")
         n = int(arena_bytes(self.B, self.H, self.W, len(self.convs), self.O))
@@ -111,7 +115,7 @@ class DenseTrainPlan(object):
         ps = []
         for c, b in zip(self.convs, self.bns):
             ps += [c.weight, b.weight, b.bias]
-        return ps + [self.head.conv_cls.weight, self.head.conv_cls.bias, self.head.conv_reg.weight, self.head.conv_reg.bias]
+        return ps + [t for c in self.head_convs for t in (c.weight, c.bias)]
 
     def _io(self, grads=None):
         io = (L.DenseTrainLayer * len(self.convs))()
@@ -138,8 +142,8 @@ class DenseTrainPlan(object):
         return io
 
     def _head(self):
-        w = torch.cat((self.head.conv_cls.weight.detach().reshape(-1, 128), self.head.conv_reg.weight.detach().reshape(-1, 128)), 0)
-        b = torch.cat((self.head.conv_cls.bias.detach(), self.head.conv_reg.bias.detach()), 0)
+        w = torch.cat([c.weight.detach().reshape(-1, 128) for c in self.head_convs], 0)
+        b = torch.cat([c.bias.detach() for c in self.head_convs], 0)
         return w.float().contiguous(), b.float().contiguous()
 
     def _planes(self, t):
@@ -192,8 +196,10 @@ class DenseTrainPlan(object):
                 dbev = torch.empty((self.B, 128, self.H, self.W), dtype=torch.float32, device=self.device)  # what the sparse plan takes
                 L.check(L.lib().v3d_split_nhwc_to_nchw(L.ptr(out[0]), L.ptr(out[1]), self.B, 128, self.H, self.W, L.ptr(dbev),
                                                        L.stream_ptr()), "split_nhwc_to_nchw")
-        nc = self.head.conv_cls.out_channels
-        grads += [dhw[:nc].reshape(self.head.conv_cls.weight.shape), dhb[:nc], dhw[nc:].reshape(self.head.conv_reg.weight.shape), dhb[nc:]]
+        lo = 0
+        for c in self.head_convs:  # the fused head's gradient rows, split back in the order of parameters()
+            grads += [dhw[lo:lo + c.out_channels].reshape(c.weight.shape), dhb[lo:lo + c.out_channels]]
+            lo += c.out_channels
         return dbev, grads
 
 

@@ -85,6 +85,8 @@ class CenterHead(nn.Module):
         if pkw_config(cfg)["ENABLED"] or voxelpool_config(cfg)["ENABLED"]:
             raise ValueError("cfg.CENTERHEAD.ENABLED with cfg.PKW.ENABLED or cfg.VOXELPOOL.ENABLED: both belong to PV_RCNN, which does "
                              "not take the centre head yet")
+        from .proposal import refuse_direction
+        refuse_direction(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED regresses sin / cos of the yaw itself)")
         self.cfg = cfg
         self.opt = centerhead_config(cfg)
         if len(self.opt["CODE_WEIGHTS"]) != 8:

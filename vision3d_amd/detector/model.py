@@ -47,6 +47,7 @@ class PV_RCNN(nn.Module):
         super().__init__()
         from .center_head import refuse_centerhead
         refuse_centerhead(cfg, "PV_RCNN")
+        proposal.refuse_direction(cfg, "PV_RCNN (stage 2 refines the yaw it is given)")
         self.cfg = cfg
         self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
         if self.voxel_pool and vector_pool.vectorpool_config(cfg)["ENABLED"]:

@@ -4,6 +4,11 @@ ProposalLayer: 1x1 class/box heads -> (B, n_cls, n_yaw, ny, nx[, 7]); inference 
 (frame, class), VoxelNet decode, multi-class rotated NMS (IoU 0.01) and per-class score threshold.
 Index bookkeeping tensors are created on the scores' device (the reference mixes CPU and GPU tensors,
 legal only in torch 1.4 -- SURVEY.md H9).
+
+cfg.DIRECTION (opt-in, not in the reference): the direction classifier and sine yaw loss of the SECOND paper.  The encoded yaw
+residual is right only modulo pi; one more 1x1 head, conv_dir, gives a logit per anchor that says which half turn (fused map
+[cls | reg | dir], forward returns a third map, the decode applies `direction_yaw`), ProposalLoss gains dir_loss and, with SIN_YAW,
+takes sin(P_yaw - G_yaw) as the yaw column's smooth-L1 argument.  Definition: DESIGN.md section 7, tests/direction_ref.py.
 """
 import math
 
@@ -13,8 +18,36 @@ from torch import nn
 
 from .. import _lib as L
 from ..core.box_encode import decode
+from ..core.proposal_targets import direction_config
 from ..ops import batched_nms_rotated, batched_nms_rotated_padded, sigmoid_focal_loss
 from .fused_loss import scale_gradient, take_gradient
+
+
+def direction_enabled(cfg):
+    return bool(direction_config(cfg)["ENABLED"])
+
+
+def refuse_direction(cfg, what):
+    """The models that do not know the direction classifier yet (follow-ups) say so instead of building a head that ignores it."""
+    if direction_enabled(cfg):
+        raise ValueError(f"cfg.DIRECTION.ENABLED: {what} does not support the direction classifier yet (Second with the anchor head "
+                         "does)")
+
+
+def fused_convs(head):
+    """The 1x1 convolutions of a head in the channel order of its fused map: [conv_cls | conv_reg], and [conv_cls | conv_reg | conv_dir]
+    for a ProposalLayer with a direction classifier.  The one statement of that order for runtime.DenseHeadPlan,
+    ProposalLayer.native_head and dense_train.DenseTrainPlan."""
+    convs = [head.conv_cls, head.conv_reg]
+    conv_dir = getattr(head, "conv_dir", None)
+    return convs + [conv_dir] if conv_dir is not None else convs
+
+
+def direction_yaw(raw, dir_logit, offset):
+    """The decode rule of cfg.DIRECTION: remainder(raw - OFFSET, pi) + OFFSET + pi * [dir_logit > 0] (strict: +-0 and NaN give 0), in
+    the dtype of `raw`; the result lies in [OFFSET, OFFSET + 2 pi)."""
+    pi, off = raw.new_tensor(math.pi), raw.new_tensor(offset)
+    return torch.remainder(raw - off, pi) + off + pi * (dir_logit > 0).to(raw.dtype)
 
 
 _PINNED = {}
@@ -53,7 +86,16 @@ class ProposalLayer(nn.Module):
         self.conv_cls = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor, 1)
         self.conv_reg = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor * cfg.BOX_DOF, 1)
         self.TOPK, self.DOF = cfg.PROPOSAL.TOPK, cfg.BOX_DOF
+        self.direction = direction_config(cfg)
         self._init_weights()
+        if self.direction["ENABLED"]:
+            # cfg.DIRECTION (opt-in): one more logit per anchor, the half turn the wrapped yaw residual cannot carry.  Built behind the
+            # reference's two heads, so that their initial values do not depend on it
+            if cfg.BOX_DOF != 7:
+                raise ValueError("cfg.DIRECTION.ENABLED: the direction classifier is defined for 7-DOF boxes")
+            self.conv_dir = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor, 1)
+            nn.init.constant_(self.conv_dir.bias, 0)
+            nn.init.normal_(self.conv_dir.weight, std=0.01)
 
     def _init_weights(self):
         # focal-prior bias exactly as the reference writes it: +1.005 (proposal.py:27)
@@ -83,24 +125,44 @@ class ProposalLayer(nn.Module):
         mask = self._above_score_thresh(scores, class_idx)
         return [x[mask] for x in (boxes, batch_idx, class_idx, scores)]
 
-    def _decode(self, reg_map, anchors, anchor_idx):
+    def _dir_map(self, dir_map):
+        """The direction map a decode of this head needs: None for a head without the classifier, else required."""
+        if not self.direction["ENABLED"]:
+            return None
+        if dir_map is None:
+            raise RuntimeError("cfg.DIRECTION.ENABLED: the decode needs the direction map (dir_from_fused) beside the class and box maps")
+        return dir_map
+
+    def _decode(self, reg_map, anchors, anchor_idx, dir_map=None):
         B, n_cls = reg_map.shape[:2]
         gidx = anchor_idx[..., None].expand(-1, -1, -1, self.DOF)
         deltas = reg_map.reshape(B, n_cls, -1, self.DOF).gather(2, gidx)
         anc = anchors.reshape(1, n_cls, -1, self.DOF).expand(B, -1, -1, -1).gather(2, gidx)
-        return decode(deltas, anc)
+        boxes = decode(deltas, anc)
+        dir_map = self._dir_map(dir_map)
+        if dir_map is not None:
+            logit = dir_map.reshape(B, n_cls, -1).gather(2, anchor_idx)
+            boxes = torch.cat((boxes[..., :6], direction_yaw(boxes[..., 6], logit, self.direction["OFFSET"])[..., None]), -1)
+        return boxes
 
     def inference(self, feature_map, anchors):
         """-> (boxes (K,7), batch_idx (K,), class_idx (K,), scores (K,)), by decreasing score."""
-        cls_map, reg_map = self(feature_map)
-        return self.inference_from_maps(cls_map, reg_map, anchors)
+        maps = self(feature_map)  # (cls_map, reg_map[, dir_map])
+        return self.inference_from_maps(maps[0], maps[1], anchors, *maps[2:])
 
     def maps_from_fused(self, maps):
-        """(B, n_anchor*(1+DOF), H, W) = [cls | reg] channels of the fused 1x1 head -> (cls_map, reg_map)."""
+        """(B, n_anchor*(1+DOF)[+ n_anchor], H, W) = [cls | reg (| dir)] channels of the fused 1x1 head -> (cls_map, reg_map)."""
         n_anchor = self.cfg.NUM_CLASSES * self.cfg.NUM_YAW
-        return self.reshape_cls(maps[:, :n_anchor].contiguous()), self.reshape_reg(maps[:, n_anchor:].contiguous())
+        return (self.reshape_cls(maps[:, :n_anchor].contiguous()),
+                self.reshape_reg(maps[:, n_anchor:n_anchor * (1 + self.DOF)].contiguous()))
 
-    def proposals_padded(self, cls_map, reg_map, anchors):
+    def dir_from_fused(self, maps):
+        """The direction logits of a fused [cls | reg | dir] map in the shape of cls_map; None for a head without the classifier."""
+        if not self.direction["ENABLED"]:
+            return None
+        return self.reshape_cls(maps[:, self.cfg.NUM_CLASSES * self.cfg.NUM_YAW * (1 + self.DOF):].contiguous())
+
+    def proposals_padded(self, cls_map, reg_map, anchors, dir_map=None):
         """Everything up to (and including) NMS with NO host synchronisation: returns the B*n_cls*TOPK
         candidates (boxes, batch_idx, class_idx, scores) plus (keep padded, n_keep) on the device.  This is
         the part that can live inside a captured HIP graph; `finalize` does the variable-length selection.
@@ -108,7 +170,7 @@ class ProposalLayer(nn.Module):
         score_map = cls_map.sigmoid()
         B, n_cls = score_map.shape[:2]
         scores, anchor_idx = score_map.reshape(B, n_cls, -1).topk(self.TOPK, -1)
-        boxes = self._decode(reg_map, anchors, anchor_idx).reshape(-1, self.DOF)
+        boxes = self._decode(reg_map, anchors, anchor_idx, dir_map).reshape(-1, self.DOF)
         scores = scores.reshape(-1)
         batch_idx, class_idx, group_idx = self._generate_group_idx(B, n_cls, scores.device)
         # column select without a host-built index tensor (an H2D copy is illegal during graph capture)
@@ -140,7 +202,8 @@ class ProposalLayer(nn.Module):
         maps, anc = L.as_f32("proposals", head_maps), L.as_f32("proposals", anchors)
         B, ctot, H, W = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
-        if ctot != n_cls * n_yaw * (1 + self.DOF) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
+        with_dir = bool(self.direction["ENABLED"])  # [cls | reg | dir] maps: v3d_proposals_dir_flag applies the direction decode rule
+        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
             raise RuntimeError("proposals: head map / anchor grid shapes disagree")
         N = B * n_cls * self.TOPK
         dev = maps.device
@@ -157,10 +220,11 @@ class ProposalLayer(nn.Module):
         lib = L.lib()
         ws = L.workspace(lib.v3d_proposals_workspace(B, n_cls, self.TOPK), dev)
         thresh = L.host_f32([a["score_thresh"] for a in cfg.ANCHORS[:n_cls]])
+        entry, extra = (lib.v3d_proposals_dir_flag, (float(self.direction["OFFSET"]),)) if with_dir else (lib.v3d_proposals_flag, ())
         with L.device_guard(dev):
-            L.check(lib.v3d_proposals_flag(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, thresh, 0.01, L.ptr(boxes),
-                                           L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(overflow_flag),
-                                           L.ptr(ws), ws.numel(), L.stream_ptr()), "proposals")
+            L.check(entry(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, thresh, 0.01, L.ptr(boxes),
+                          L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(overflow_flag),
+                          L.ptr(ws), ws.numel(), L.stream_ptr(), *extra), "proposals")
         return boxes, batch_idx, class_idx, scores, n_out
 
     def native_topk(self, head_maps, anchors):
@@ -171,16 +235,18 @@ class ProposalLayer(nn.Module):
         maps, anc = L.as_f32("proposals_topk", head_maps), L.as_f32("proposals_topk", anchors)
         B, ctot, H, W = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
-        if ctot != n_cls * n_yaw * (1 + self.DOF) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
+        with_dir = bool(self.direction["ENABLED"])
+        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
             raise RuntimeError("proposals_topk: head map / anchor grid shapes disagree")
         N = B * n_cls * self.TOPK
         boxes = torch.empty((B, n_cls * self.TOPK, 7), dtype=torch.float32, device=maps.device)
         scores = torch.empty((B, n_cls * self.TOPK), dtype=torch.float32, device=maps.device)
         lib = L.lib()
         ws = L.workspace(lib.v3d_proposals_workspace(B, n_cls, self.TOPK), maps.device)
+        entry, extra = (lib.v3d_proposals_dir_topk, (float(self.direction["OFFSET"]),)) if with_dir else (lib.v3d_proposals_topk, ())
         with L.device_guard(maps.device):
-            L.check(lib.v3d_proposals_topk(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, L.ptr(boxes), L.ptr(scores), L.ptr(ws),
-                                           ws.numel(), L.stream_ptr()), "proposals_topk")
+            L.check(entry(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, L.ptr(boxes), L.ptr(scores), L.ptr(ws),
+                          ws.numel(), L.stream_ptr(), *extra), "proposals_topk")
         assert N == boxes.shape[0] * boxes.shape[1]
         return boxes, scores
 
@@ -244,7 +310,7 @@ class ProposalLayer(nn.Module):
     def inference_native(self, head_maps, anchors, overflow_flag=None):
         if not self.native_supported(head_maps.shape[0], anchors.numel() // (7 * self.cfg.NUM_CLASSES)):  # too large: op-by-op
             cls_map, reg_map = self.maps_from_fused(head_maps)
-            out = self.inference_from_maps(cls_map, reg_map, anchors)
+            out = self.inference_from_maps(cls_map, reg_map, anchors, self.dir_from_fused(head_maps))
             if overflow_flag is not None:
                 _raise_on_flag(int(overflow_flag.item()))
             return out
@@ -256,11 +322,11 @@ class ProposalLayer(nn.Module):
         mask = self._above_score_thresh(scores, class_idx)
         return [x[mask] for x in (boxes, batch_idx, class_idx, scores)]
 
-    def inference_from_maps(self, cls_map, reg_map, anchors):
+    def inference_from_maps(self, cls_map, reg_map, anchors, dir_map=None):
         score_map = cls_map.sigmoid_()
         B, n_cls = score_map.shape[:2]
         scores, anchor_idx = score_map.view(B, n_cls, -1).topk(self.TOPK, -1)
-        boxes = self._decode(reg_map, anchors, anchor_idx)
+        boxes = self._decode(reg_map, anchors, anchor_idx, dir_map)
         return self._multiclass_batch_nms(boxes, scores)
 
     def reshape_cls(self, cls_map):
@@ -272,9 +338,21 @@ class ProposalLayer(nn.Module):
         return reg_map.view(B, self.cfg.NUM_CLASSES, self.cfg.BOX_DOF, -1, ny, nx).permute(0, 1, 3, 4, 5, 2)
 
     def forward(self, feature_map):
+        """-> (cls_map, reg_map), and (cls_map, reg_map, dir_map) for a head with a direction classifier."""
         if not self.training and not torch.is_grad_enabled() and feature_map.is_cuda:
-            return self.maps_from_fused(self.native_head(feature_map))  # inference on the GPU: csrc/dense_conv.hip, not MIOpen
-        return self.reshape_cls(self.conv_cls(feature_map)), self.reshape_reg(self.conv_reg(feature_map))
+            maps = self.native_head(feature_map)  # inference on the GPU: csrc/dense_conv.hip, not MIOpen
+            return self.maps_from_fused(maps) + ((self.dir_from_fused(maps),) if self.direction["ENABLED"] else ())
+        out = self.reshape_cls(self.conv_cls(feature_map)), self.reshape_reg(self.conv_reg(feature_map))
+        return out + ((self.reshape_cls(self.conv_dir(feature_map)),) if self.direction["ENABLED"] else ())
+
+    def fuse(self, cls_map, reg_map, dir_map=None):
+        """The module outputs back in the fused layout [cls | reg (| dir)] (B, n_anchor * 8 (9), H, W), fp32 and contiguous: what
+        maps_from_fused / dir_from_fused split and the native loss reads."""
+        B, _, _, H, W = cls_map.shape
+        parts = [cls_map.reshape(B, -1, H, W), reg_map.permute(0, 1, 5, 2, 3, 4).reshape(B, -1, H, W)]
+        if dir_map is not None:
+            parts.append(dir_map.reshape(B, -1, H, W))
+        return torch.cat([p.float() for p in parts], 1)
 
     def native_head(self, feature_map):
         """fp32 (B, C_IN, H, W) cuda -> fused [cls | reg] maps (B, n_anchor * (1 + DOF), H, W) fp32 on the streaming split-precision
@@ -283,13 +361,14 @@ class ProposalLayer(nn.Module):
         head tensor changes.  (Second's inference paths get the same maps from DenseHeadPlan, which feeds the kernel split planes
         directly; this entry is for callers that hold an fp32 feature map: PV_RCNN.proposal, `model.head(features)`.)"""
         from ..runtime import conv2d_split, pack_conv_weight, to_split_nhwc
-        tensors = (self.conv_cls.weight, self.conv_cls.bias, self.conv_reg.weight, self.conv_reg.bias)
+        convs = fused_convs(self)
+        tensors = tuple(t for c in convs for t in (c.weight, c.bias))
         stamp = tuple((t.data_ptr(), t._version) for t in tensors)
         cache = self.__dict__.get("_native_head")
         if cache is None or cache[0] != stamp:
             with torch.no_grad():
-                w = torch.cat((self.conv_cls.weight, self.conv_reg.weight), 0)
-                bias = torch.cat((self.conv_cls.bias, self.conv_reg.bias), 0).float().contiguous()
+                w = torch.cat([c.weight for c in convs], 0)
+                bias = torch.cat([c.bias for c in convs], 0).float().contiguous()
                 cache = (stamp, pack_conv_weight(w, None, "fp32"), bias, w.shape[1], w.shape[0])
             self.__dict__["_native_head"] = cache
         _, img, bias, cin, cout = cache
@@ -325,13 +404,45 @@ class FusedProposalLossFunction(torch.autograd.Function):
         return (dmaps,) + (None,) * 8
 
 
+class FusedProposalDirLossFunction(torch.autograd.Function):
+    """The same for a head with a direction classifier (cfg.DIRECTION; v3d_proposal_dir_loss_fwd_bwd): (maps [cls | reg | dir], G_cls,
+    M_cls, G_reg, M_reg, G_dir int8) -> (cls_loss, reg_loss, dir_loss); backward scales the three channel groups with their upstream
+    gradients."""
+
+    @staticmethod
+    def forward(ctx, maps, g_cls, m_cls, g_reg, m_reg, g_dir, sin_yaw, n_cls, n_yaw, alpha, gamma):
+        from .. import _lib as L
+        b, _, h, w = maps.shape
+        losses = torch.empty(4, dtype=torch.float32, device=maps.device)
+        dmaps = torch.empty_like(maps)
+        lib = L.lib()
+        ws = L.workspace(lib.v3d_proposal_dir_loss_workspace(), maps.device)
+        with L.device_guard(maps.device):
+            L.check(lib.v3d_proposal_dir_loss_fwd_bwd(L.ptr(maps), L.ptr(g_cls), L.ptr(m_cls), L.ptr(g_reg), L.ptr(m_reg), L.ptr(g_dir),
+                                                      int(bool(sin_yaw)), b, n_cls, n_yaw, h, w, float(alpha), float(gamma), L.ptr(losses),
+                                                      L.ptr(dmaps), L.ptr(ws), ws.numel(), L.stream_ptr()), "proposal_dir_loss_fwd_bwd")
+        ctx.grad, ctx.geom = dmaps, (b, n_cls, n_yaw, h, w)
+        return losses[0], losses[1], losses[2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls_loss, g_reg_loss, g_dir_loss):
+        dmaps = take_gradient(ctx, "proposal")
+        # (the fourth scalar is the 1.0f the two-way scale kernel multiplies the other groups with: csrc/proposal_loss.hip)
+        scale_gradient("proposal_dir_loss_scale", dmaps, (dmaps, *ctx.geom), (g_cls_loss, g_reg_loss, g_dir_loss, torch.ones_like(g_cls_loss)))
+        return (dmaps,) + (None,) * 10
+
+
 class ProposalLoss(nn.Module):
     """Focal classification + smooth-L1 box loss, both divided by max(#positives, 1)
-    (proposal.py:100-141).  (P, G, M) = (predicted, ground truth, mask)."""
+    (proposal.py:100-141).  (P, G, M) = (predicted, ground truth, mask).  With cfg.DIRECTION.ENABLED: the yaw column's smooth-L1
+    argument is sin(P_yaw - G_yaw) (SIN_YAW) and dir_loss = BCE-with-logits(P_dir, G_dir) over M_reg / max(#positives, 1) joins the
+    sum times LOSS_WEIGHT."""
 
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
+        self.direction = direction_config(cfg)
 
     @staticmethod
     def masked_sum(loss, mask):
@@ -339,11 +450,22 @@ class ProposalLoss(nn.Module):
 
     def reg_loss(self, P_reg, G_reg, M_reg):
         per = F.smooth_l1_loss(P_reg, G_reg, reduction="none")
-        total = per[..., 0:3] + per[..., 3:6] + per[..., 6:7] / math.pi
+        yaw = per[..., 6:7]
+        if self.direction["ENABLED"] and self.direction["SIN_YAW"]:
+            s = torch.sin(P_reg[..., 6:7] - G_reg[..., 6:7])
+            yaw = F.smooth_l1_loss(s, torch.zeros_like(s), reduction="none")
+        total = per[..., 0:3] + per[..., 3:6] + yaw / math.pi
         return self.masked_sum(total, M_reg)
 
+    def dir_loss(self, P_dir, G_dir, M_reg):
+        x, g = P_dir, G_dir.to(P_dir.dtype)
+        bce = x.clamp(min=0) - x * g + torch.log1p(torch.exp(-x.abs()))
+        return self.masked_sum(bce, M_reg[..., 0])
+
     def cls_loss(self, P_cls, G_cls, M_cls):
-        return self.masked_sum(sigmoid_focal_loss(P_cls, G_cls.float(), reduction="none"), M_cls)
+        # (float64 logits keep float64 targets: torch's BCE takes the dtype of its TARGET, so fp32 targets made the float64 statement fp32)
+        target = G_cls.double() if P_cls.dtype == torch.float64 else G_cls.float()
+        return self.masked_sum(sigmoid_focal_loss(P_cls, target, reduction="none"), M_cls)
 
     def _fused(self, item):
         """The native pass applies when the model left its FUSED head maps in the item (`_head_maps`: Second.forward on the native
@@ -352,26 +474,40 @@ class ProposalLoss(nn.Module):
         if isinstance(maps, tuple):
             # (maps, P_cls, P_reg) as Second.forward leaves them: the fused maps only speak for this item while its P_cls / P_reg
             # are still the views made from them -- outputs that were replaced or post-processed go through the torch expressions
-            maps, p_cls, p_reg = maps
-            if item.get("P_cls") is not p_cls or item.get("P_reg") is not p_reg:
+            maps, p_cls, p_reg, *p_dir = maps
+            if item.get("P_cls") is not p_cls or item.get("P_reg") is not p_reg or (p_dir and item.get("P_dir") is not p_dir[0]):
                 return None
         cfg = self.cfg
+        with_dir = bool(self.direction["ENABLED"])
         if maps is None or not maps.is_cuda or maps.dtype != torch.float32 or not maps.is_contiguous() or cfg.BOX_DOF != 7:
             return None
         G_cls, M_cls, G_reg, M_reg = (item[k] for k in ("G_cls", "M_cls", "G_reg", "M_reg"))
         b, o, h, w = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
         shape = (b, n_cls, n_yaw, h, w)
-        if o != n_cls * n_yaw * 8 or tuple(G_cls.shape) != shape or tuple(M_cls.shape) != shape \
+        if o != n_cls * n_yaw * (8 + with_dir) or tuple(G_cls.shape) != shape or tuple(M_cls.shape) != shape \
                 or tuple(G_reg.shape) != shape + (7,) or tuple(M_reg.shape) != shape + (1,) or G_reg.dtype != torch.float32:
             return None
         if any(t.device != maps.device for t in (G_cls, M_cls, G_reg, M_reg)):
             return None
         g_cls = G_cls if G_cls.dtype == torch.int8 else G_cls.to(torch.int8)
         as_u8 = lambda m: (m if m.dtype in (torch.bool, torch.uint8) else m.ne(0)).contiguous().view(torch.uint8)
+        if with_dir:
+            G_dir = item["G_dir"]
+            if tuple(G_dir.shape) != shape or G_dir.device != maps.device:
+                return None
+            g_dir = G_dir if G_dir.dtype == torch.int8 else G_dir.to(torch.int8)
+            cls_loss, reg_loss, dir_loss = FusedProposalDirLossFunction.apply(
+                maps, g_cls.contiguous(), as_u8(M_cls), G_reg.contiguous(), as_u8(M_reg), g_dir.contiguous(), bool(self.direction["SIN_YAW"]),
+                n_cls, n_yaw, 0.25, 2.0)
+            return self._total(cls_loss, reg_loss, dir_loss)
         cls_loss, reg_loss = FusedProposalLossFunction.apply(maps, g_cls.contiguous(), as_u8(M_cls), G_reg.contiguous(), as_u8(M_reg),
                                                              n_cls, n_yaw, 0.25, 2.0)
         return dict(cls_loss=cls_loss, reg_loss=reg_loss, loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss)
+
+    def _total(self, cls_loss, reg_loss, dir_loss):
+        return dict(cls_loss=cls_loss, reg_loss=reg_loss, dir_loss=dir_loss,
+                    loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss + self.direction["LOSS_WEIGHT"] * dir_loss)
 
     def forward(self, item):
         fused = self._fused(item)
@@ -381,4 +517,6 @@ class ProposalLoss(nn.Module):
         normalizer = M_reg.type_as(P_reg).sum().clamp_(min=1)
         cls_loss = self.cls_loss(P_cls, G_cls, M_cls) / normalizer
         reg_loss = self.reg_loss(P_reg, G_reg, M_reg) / normalizer
+        if self.direction["ENABLED"]:
+            return self._total(cls_loss, reg_loss, self.dir_loss(item["P_dir"], item["G_dir"], M_reg) / normalizer)
         return dict(cls_loss=cls_loss, reg_loss=reg_loss, loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss)

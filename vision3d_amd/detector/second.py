@@ -312,6 +312,9 @@ class Second(nn.Module):
     def forward(self, item):
         # the fused maps of an EARLIER training forward must never reach ProposalLoss through a re-used item dict
         item.pop("_head_maps", None)
+        item.pop("P_dir", None)
+        with_dir = not self.center_head and self.head.direction["ENABLED"]  # cfg.DIRECTION: a third map, P_dir, beside P_cls / P_reg
+        direction = None
         if self._native_item(item):
             state = {}
 
@@ -319,16 +322,28 @@ class Second(nn.Module):
                 maps, state["plan"] = self._head_maps_from_item(item)
                 state["plan"].check_overflow()  # no count is read on this path: one blocking word
                 return maps
-            scores, boxes = self.head.maps_from_fused(self._with_recalibration(run, lambda: state["plan"]))
+            maps = self._with_recalibration(run, lambda: state["plan"])
+            scores, boxes = self.head.maps_from_fused(maps)
+            if with_dir:
+                direction = self.head.dir_from_fused(maps)
         elif (maps := self._train_head_maps(item)) is not None:
-            scores, boxes = maps if isinstance(maps, tuple) else self.head.maps_from_fused(maps)
+            if with_dir and isinstance(maps, tuple) and maps[0].is_cuda:
+                # the dense half of a head with a direction classifier trains through the torch modules (dense_train.supported
+                # refuses its width): their three outputs, concatenated, are the fused map the native loss reads
+                maps = self.head.fuse(*maps)
+            scores, boxes = maps[:2] if isinstance(maps, tuple) else self.head.maps_from_fused(maps)
+            if with_dir:
+                direction = maps[2] if isinstance(maps, tuple) else self.head.dir_from_fused(maps)
             if not isinstance(maps, tuple):
                 # ProposalLoss takes its native pass on the fused maps (detector/proposal.py) -- only while P_cls / P_reg are
                 # still the views made here (it compares identities): post-processed outputs go through the torch expressions
-                item["_head_maps"] = (maps, scores, boxes)
+                item["_head_maps"] = (maps, scores, boxes) + ((direction,) if with_dir else ())
         else:
-            scores, boxes = self.head(self.feature_extract(item))
+            scores, boxes, *rest = self.head(self.feature_extract(item))
+            direction = rest[0] if with_dir else None
         item.update(dict(P_cls=scores, P_reg=boxes))
+        if with_dir:
+            item["P_dir"] = direction
         return item
 
     def inference(self, item):
@@ -454,5 +469,6 @@ class Second(nn.Module):
         if self.center_head:
             raise ValueError("inference_points: cfg.CENTERHEAD.ENABLED has one proposal stage (proposals='native'; CenterHead.decode_torch "
                              "is its op-by-op statement)")
-        cls_map, reg_map = self.head_maps_from_points(clouds)
-        return self.head.inference_from_maps(cls_map, reg_map, anchors)
+        maps = self.fused_head_from_points(clouds)
+        cls_map, reg_map = self.head.maps_from_fused(maps)
+        return self.head.inference_from_maps(cls_map, reg_map, anchors, self.head.dir_from_fused(maps))

@@ -757,7 +757,8 @@ class DenseHeadPlan(object):
     def _param_stamp(self):
         tensors = [t for c, b in self._pairs() for t in (c.weight, b.running_mean, b.running_var, b.weight, b.bias)]
         if self.head is not None:
-            tensors += [self.head.conv_cls.weight, self.head.conv_cls.bias, self.head.conv_reg.weight, self.head.conv_reg.bias]
+            from .detector.proposal import fused_convs
+            tensors += [t for c in fused_convs(self.head) for t in (c.weight, c.bias)]
         return tuple((t.data_ptr(), t._version) for t in tensors) + (self.precision,)
 
     def weights_changed(self):
@@ -785,8 +786,9 @@ class DenseHeadPlan(object):
                 layers.append(dict(img=pack_conv_weight(conv.weight, scale, self.precision), bias=shift, relu=True,
                                    cin=conv.in_channels, cout=conv.out_channels, k=k, l1=l1, bmax=shift.abs().max()))
             if self.head is not None:
-                w = torch.cat((self.head.conv_cls.weight, self.head.conv_reg.weight), 0)
-                bias = torch.cat((self.head.conv_cls.bias, self.head.conv_reg.bias), 0).float().contiguous()
+                from .detector.proposal import fused_convs
+                w = torch.cat([c.weight for c in fused_convs(self.head)], 0)
+                bias = torch.cat([c.bias for c in fused_convs(self.head)], 0).float().contiguous()
                 layers.append(dict(img=pack_conv_weight(w, None, self.precision), bias=bias, relu=False, cin=w.shape[1], cout=w.shape[0], k=1))
             else:
                 layers.append(None)  # RPN only (RPN.native_forward): no head layer
