@@ -98,7 +98,7 @@ def test_query_of_a_database_elsewhere_and_of_an_empty_one():
 
 
 def test_query_of_two_corner_clusters_and_an_empty_frame():
-    """The scan over the cells of a frame's grid (16 384 cells, 1 024 threads of 16 cells) where a base can go wrong: the support rows
+    """The scan over the cells of a frame's grid (16 384 cells, 17 to each of the build's 1 024 threads) where a base can go wrong: the support rows
     in two clusters at opposite corners of their bounds, 127.5 reaches apart along x and y, so that the grid has 128 x 128 cells of
     which the first and the last are occupied -- the last thread's base is every row before its own --; the second frame holds no
     finite row.  idx exactly against the restatement on the decidable centres; the empty frame finds nothing."""
@@ -122,6 +122,53 @@ def test_query_of_two_corner_clusters_and_an_empty_frame():
     for half in (slice(0, n // 2), slice(n // 2, n)):  # both corners are found
         assert ((idx[0] >= half.start) & (idx[0] < half.stop)).any()
     assert (idx[1] == -1).all() and (w[1].view(np.uint32) == 0).all()
+
+
+# ---- the search over the shared cell grid (csrc/cell_grid.hip): every instantiation of the build, the growth loop, the single cell
+def _assert_equals_the_restatement(xyz, q, voxels, radius):
+    """As test_query_equals_the_restatement_exactly: idx (the -1 patterns included) on every decidable centre, no index of a
+    duplicate's higher row, the weights within 16 ulp of float64 on the native neighbours, two runs bit-equal."""
+    want, _, und = R.query(xyz, q, voxels, radius)
+    assert und.mean() <= C.GRID_CAP
+    idx, w = _native(xyz, q, voxels, radius)
+    assert idx.min() >= -1 and idx.max() < xyz.shape[1]
+    np.testing.assert_array_equal(idx[~und], want[~und])
+    canon = np.stack([R.canonical(f) for f in xyz])
+    frames = np.broadcast_to(np.arange(xyz.shape[0])[:, None, None, None], idx.shape)
+    assert (canon[frames[idx >= 0], idx[idx >= 0]] == idx[idx >= 0]).all(), "a duplicate's higher row was returned"
+    w64 = R.weights(xyz, q, voxels, radius, idx)
+    ulps = np.abs(w.astype(np.float64) - w64) / np.spacing(np.maximum(np.abs(w64), 1e-30).astype(np.float32)).astype(np.float64)
+    found = np.bincount((idx >= 0).sum(-1).reshape(-1), minlength=4).tolist()
+    print(f"[vector pool grid N={xyz.shape[1]} {voxels} R={radius}] neighbours found 0/1/2/3: {found}, undecidable {und.mean():.4f}, "
+          f"largest weight error {ulps[idx >= 0].max() if (idx >= 0).any() else 0.0:.2f} ulp")
+    assert (w[idx < 0] == 0.0).all() and (not (idx >= 0).any() or ulps[idx >= 0].max() <= 16.0)
+    idx2, w2 = _native(xyz, q, voxels, radius)
+    assert np.array_equal(idx, idx2) and np.array_equal(w.view(np.uint32), w2.view(np.uint32))
+    return idx
+
+
+@pytest.mark.parametrize("voxels,radius", C.GRID_GROUPS)
+@pytest.mark.parametrize("n", C.GRID_BUILD_N)
+def test_query_through_every_instantiation_of_the_grid_build(n, voxels, radius):
+    """The build keeps 4, 12 or 20 points per thread in registers or reads them again (more than 20 480): the last size of the first
+    kind, and the first size of each of the others."""
+    idx = _assert_equals_the_restatement(*C.grid_build_case(n), voxels, radius)
+    assert (idx[0] >= 0).any() and (idx[1] >= 0).any()
+
+
+def test_query_where_the_grid_has_to_grow():
+    xyz, q = C.grid_growth_case()
+    idx = _assert_equals_the_restatement(xyz, q, (2, 2, 2), 0.2)
+    assert ((idx >= 0).sum(-1) == 3).any()
+
+
+@pytest.mark.parametrize("kind", C.GRID_SINGLE_KINDS)
+def test_query_of_a_single_cell(kind):
+    xyz, q = C.grid_single_cell_case(kind)
+    idx = _assert_equals_the_restatement(xyz, q, (2, 2, 2), 0.2)
+    assert (idx[..., 0] >= 0).any()
+    if kind == "equal":  # one canonical row per centre at most
+        assert (idx[..., 0] <= 0).all() and (idx[..., 1:] == -1).all()
 
 
 @pytest.mark.parametrize("cr,cl,g", [(1, 16, 0), (4, 32, 1), (32, 16, 2), (32, 32, 3), (4, 16, 3), (1, 32, 2)])

@@ -89,6 +89,29 @@ def test_cases_cover_every_neighbour_count(kind):
         assert (canon[frames, picked] == picked).all()  # no index refers to a duplicate's higher row
 
 
+def test_grid_cases_are_decidable_and_shaped_as_stated():
+    """The cases of the search over the shared cell grid (tests/test_gpu_vector_pool.py): the restatement alone leaves at most
+    GRID_CAP of a case's centres undecided, and each case has the shape its test is about."""
+    reach = lambda voxels, radius: radius * (2.0 - 1.0 / max(voxels[:2])) * (1.0 + 1e-5) + 1e-3  # the cell edge vector_pool.hip asks for
+    cases = [(f"build N={n}", C.grid_build_case(n), g) for n in C.GRID_BUILD_N for g in C.GRID_GROUPS]
+    cases += [("growth", C.grid_growth_case(), ((2, 2, 2), 0.2))]
+    cases += [(f"single cell, {k}", C.grid_single_cell_case(k), ((2, 2, 2), 0.2)) for k in C.GRID_SINGLE_KINDS]
+    for name, (xyz, q), (voxels, radius) in cases:
+        idx, _, und = R.query(xyz, q, voxels, radius)
+        counts = np.bincount((idx >= 0).sum(-1).reshape(-1), minlength=4)
+        extent = (xyz[:, :, :2].max(1) - xyz[:, :, :2].min(1)).astype(np.float64)
+        cells = np.prod(np.floor(extent / reach(voxels, radius)) + 1, axis=1)
+        print(f"[{name} {voxels} R={radius}] centres by neighbour count {counts.tolist()}, undecidable {und.mean():.4f}, cells at the first try {cells.tolist()}")
+        assert und.mean() <= C.GRID_CAP and (idx >= 0).any()
+        assert (np.abs(q[:, :4, None, :] - xyz[:, None, :, :]).max(-1).min(-1) == 0).all()  # (queries on support rows)
+        if name == "growth":
+            assert (cells > 400000).all() and xyz.shape == (2, 2320, 3) and q.shape == (2, 16, 3)
+        elif name.startswith("single"):
+            assert (cells == 1).all()
+        else:
+            assert (cells <= 32768).all() and (cells > 1).all() and q.shape == (2, 8, 3)
+
+
 @pytest.mark.parametrize("kind", C.KINDS)
 def test_query_torch_equals_the_restatement(kind):
     from vision3d_amd.detector import vector_pool as V

@@ -71,7 +71,7 @@ def kernel_times(fn, needles, calls=5):
             say(f"  kernel {ev.key.split('(')[0].split()[-1]}: {total / max(ev.count, 1):8.1f} us per launch, {ev.count // calls} per call")
 
 
-KERNELS = ("vpq_bounds_kernel", "vpq_bin_kernel", "vpq_scan_kernel", "vpq_query_kernel", "vp_embed_kernel", "vp_reduce_kernel", "linear_rows_kernel")
+KERNELS = ("bq_grid_build_kernel", "vpq_query_kernel", "vp_embed_kernel", "vp_reduce_kernel", "linear_rows_kernel")
 
 
 def time_module(name, mod, xyz, feat, q, args):

@@ -14,8 +14,9 @@
 #include <algorithm>
 #include <cmath>
 
-#include "v3d_common.h"
+#include "v3d_internal.h"
 #include "dpp_device.h"
+#include "cell_grid_device.h"
 
 // ------------------------------------------------------------------------------------------ FPS
 #define FPS_THREADS 1024  // (the DPP max / min reductions of the kernels below: dpp_device.h)
@@ -502,17 +503,14 @@ extern "C" int v3d_ball_query(const float* xyz, const float* new_xyz, int B, int
 // LDS histogram, scan, scatter of (x, y, z, index) records), and a query looks at the 3 x 3 cells around its own only:
 //   * which points are inside the ball is decided by the scan kernels' own expression on the same operands (-ffp-contract=off),
 //     so the hit SET is theirs bit for bit -- the cells only have to be a superset, which the 1 % margin on the cell edge
-//     guarantees against the rounding of the two cell computations (see bq_cell);
+//     guarantees against the rounding of the two cell computations (see cg_cell);
 //   * "the first nsample hits in INDEX order" does not depend on the order the candidates are met in: every hit sets bit
 //     `index` of a per-wave LDS bitmap (N bits per radius), and the answer is read off the bitmap in ascending order --
 //     popcount prefix over the lanes' word runs, the lanes below nsample emit their bits.
 // Same results as v3d_ball_query for every input (tests/test_gpu_pointops.py: equality with the scan kernel at full size, with the
 // CPU oracle at small sizes, non-finite coordinates, queries far outside the database).
-#define BQG_MAX_KEYS 32768  // (index chunk, cell) keys of the LDS histogram: 128 KB of the build workgroup's LDS
 #define BQG_MAX_CHUNKS 8
-#define BQG_MAX_JOBS 8
-#define BQG_BUILD_THREADS 1024
-#define BQG_HEADER_BYTES 32
+#define BQG_MAX_JOBS V3D_CELL_GRID_MAX_JOBS
 #define BQG_WAVES 4
 #define BQG_RPL 8                  // records per lane requested before the first is looked at
 #define BQG_BATCH (BQG_RPL * 64)
@@ -520,142 +518,7 @@ extern "C" int v3d_ball_query(const float* xyz, const float* new_xyz, int B, int
 // INDEX CHUNKS.  A ball in a dense region holds hundreds of points but only the `nsample` lowest indices are wanted.  The records are
 // therefore sorted by (index chunk, cell): chunk = index / ceil(N / nch), nch <= 8 as the histogram allows.  A query walks the chunks
 // in order and stops once every radius has nsample hits among the chunks it has finished -- later chunks hold larger indices only.
-struct BqGrid {  // first words of a frame's workspace, written by the build kernel
-  float x0, y0, inv_c;
-  int nx, ny, nch, chunk;  // cells along x / y, index chunks, points per chunk
-};
-
-__host__ __device__ static inline size_t bqg_sorted_offset() { return (BQG_HEADER_BYTES + (BQG_MAX_KEYS + 1) * 4 + 15) / 16 * 16; }
-__host__ __device__ static inline size_t bqg_frame_bytes(int N) { return bqg_sorted_offset() + (size_t)N * 16; }
-
-// Cell coordinate of x along an axis that starts at x0: the SAME expression for database points and queries.  Two values less
-// than r apart differ by less than r * inv_c <= 1 / 1.01 before rounding and by at most 2 * 32768 * 2^-23 ~ 0.008 more after it
-// (two roundings each, at most BQG_MAX_KEYS cells along an axis): their floors differ by at most one.
-__device__ __forceinline__ float bq_cell(float x, float x0, float inv_c) { return floorf((x - x0) * inv_c); }
-
-struct BqBuildJob {
-  const float* xyz;   // (B, N, 3)
-  unsigned char* ws;  // B frames of bqg_frame_bytes(N)
-  int N;
-  float cell_min;
-};
-struct BqBuildJobs {
-  BqBuildJob j[BQG_MAX_JOBS];
-};
-
-// One workgroup per (database, frame).  PPT > 0: N <= PPT * BQG_BUILD_THREADS for every job and a thread keeps its points in
-// registers (ONE trip to memory instead of three: a workgroup alone on its compute unit has nothing to hide a trip behind);
-// PPT == 0: any N, the points are read again in every pass.
-template <int PPT>
-__global__ __launch_bounds__(BQG_BUILD_THREADS) void bq_grid_build_kernel(const BqBuildJobs jobs) {
-  extern __shared__ int bq_cnt[];  // [BQG_MAX_KEYS]
-  __shared__ float red[4][BQG_BUILD_THREADS / V3D_WAVE];
-  __shared__ int wsum[BQG_BUILD_THREADS / V3D_WAVE];
-  __shared__ BqGrid g;
-  int* cnt = bq_cnt;
-  const BqBuildJob job = jobs.j[blockIdx.x];
-  const int N = job.N;
-  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* p = job.xyz + (size_t)b * N * 3;
-  unsigned char* w = job.ws + (size_t)b * bqg_frame_bytes(N);
-  int* cell_start = reinterpret_cast<int*>(w + BQG_HEADER_BYTES);
-  float4* sorted = reinterpret_cast<float4*>(w + bqg_sorted_offset());
-  const float inf = __builtin_huge_valf();
-  [[maybe_unused]] float px[PPT ? PPT : 1], py[PPT ? PPT : 1], pz[PPT ? PPT : 1];
-  if constexpr (PPT > 0) {
-#pragma unroll
-    for (int k = 0; k < PPT; k++) {
-      const int i = tid + k * BQG_BUILD_THREADS;
-      px[k] = i < N ? p[3 * (size_t)i] : inf;  // (a slot beyond N reads as a non-finite point: left out like one)
-      py[k] = i < N ? p[3 * (size_t)i + 1] : inf;
-      pz[k] = i < N ? p[3 * (size_t)i + 2] : inf;
-    }
-  }
-  // body(i, x, y, z) for every point with finite x and y (a point with a non-finite x or y can be in no ball: it is left out of the grid)
-  auto for_points = [&](auto body) {
-    if constexpr (PPT > 0) {
-#pragma unroll
-      for (int k = 0; k < PPT; k++)
-        if (fabsf(px[k]) < inf && fabsf(py[k]) < inf) body(tid + k * BQG_BUILD_THREADS, px[k], py[k], pz[k]);
-    } else {
-      for (int i = tid; i < N; i += BQG_BUILD_THREADS) {
-        const float x = p[3 * (size_t)i], y = p[3 * (size_t)i + 1], z = p[3 * (size_t)i + 2];
-        if (fabsf(x) < inf && fabsf(y) < inf) body(i, x, y, z);
-      }
-    }
-  };
-  // (a) bounds
-  float xlo = inf, xhi = -inf, ylo = inf, yhi = -inf;
-  for_points([&](int, float x, float y, float) {
-    xlo = fminf(xlo, x), xhi = fmaxf(xhi, x);
-    ylo = fminf(ylo, y), yhi = fmaxf(yhi, y);
-  });
-  xlo = -v3d_dpp_max_f32<true>(-xlo), xhi = v3d_dpp_max_f32<true>(xhi);
-  ylo = -v3d_dpp_max_f32<true>(-ylo), yhi = v3d_dpp_max_f32<true>(yhi);
-  if (lane == 0) red[0][wave] = xlo, red[1][wave] = xhi, red[2][wave] = ylo, red[3][wave] = yhi;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < BQG_BUILD_THREADS / V3D_WAVE; i++) {
-      xlo = fminf(xlo, red[0][i]), xhi = fmaxf(xhi, red[1][i]);
-      ylo = fminf(ylo, red[2][i]), yhi = fmaxf(yhi, red[3][i]);
-    }
-    BqGrid t;
-    t.x0 = xlo, t.y0 = ylo, t.inv_c = 0.f, t.nx = 0, t.ny = 0, t.nch = 1, t.chunk = N > 0 ? N : 1;
-    if (xlo <= xhi) {  // at least one finite point
-      float c = job.cell_min;
-      for (;;) {  // cells no smaller than asked for, grown until the grid fits the LDS histogram
-        t.inv_c = 1.f / c;
-        const float fx = bq_cell(xhi, xlo, t.inv_c), fy = bq_cell(yhi, ylo, t.inv_c);  // (the largest cell along each axis)
-        if (fx < (float)BQG_MAX_KEYS && fy < (float)BQG_MAX_KEYS && ((long long)fx + 1) * ((long long)fy + 1) <= BQG_MAX_KEYS) {
-          t.nx = (int)fx + 1, t.ny = (int)fy + 1;
-          break;
-        }
-        c *= 1.5f;
-      }
-      t.nch = min(BQG_MAX_CHUNKS, BQG_MAX_KEYS / (t.nx * t.ny));
-      t.chunk = (N + t.nch - 1) / t.nch;
-    }
-    g = t;
-    *reinterpret_cast<BqGrid*>(w) = t;
-  }
-  __syncthreads();
-  const BqGrid gg = g;
-  const int ncell = gg.nx * gg.ny, nkeys = ncell * gg.nch;
-  // keys per thread of the scan below: covers nkeys + 1, odd (thread t walks the words [t * kpt, (t + 1) * kpt): an odd stride is
-  // conflict-free)
-  const int kpt = ((nkeys + BQG_BUILD_THREADS) / BQG_BUILD_THREADS) | 1;
-  for (int i = tid; i < kpt * BQG_BUILD_THREADS; i += BQG_BUILD_THREADS)
-    if (i < BQG_MAX_KEYS) cnt[i] = 0;
-  __syncthreads();
-  auto key_of = [&](int i, float x, float y) {
-    return (i / gg.chunk) * ncell + (int)bq_cell(y, gg.y0, gg.inv_c) * gg.nx + (int)bq_cell(x, gg.x0, gg.inv_c);
-  };
-  // (b) histogram
-  for_points([&](int i, float x, float y, float) { atomicAdd(&cnt[key_of(i, x, y)], 1); });
-  __syncthreads();
-  // (c) exclusive scan over the keys: kpt consecutive keys per thread, in place (the counts become the keys' write cursors)
-  const int k_lo = tid * kpt;
-  int sum = 0;
-  for (int k = 0; k < kpt; k++)
-    if (k_lo + k < BQG_MAX_KEYS) sum += cnt[k_lo + k];
-  int binned;  // the number of binned points
-  int run = v3d_block_scan_incl<BQG_BUILD_THREADS / V3D_WAVE>(sum, binned, wsum) - sum;
-  for (int k = 0; k < kpt; k++) {
-    const int c = k_lo + k;
-    if (c < BQG_MAX_KEYS) {
-      const int own = cnt[c];
-      cnt[c] = run;
-      run += own;
-    }
-  }
-  __syncthreads();
-  // the table as the queries read it: coalesced, not a thread's kpt consecutive words (the scan's layout: one 64-byte line per lane
-  // and store instruction -- 30 us of a 45 us build at 26 000 keys); entry nkeys = the number of binned points
-  for (int c = tid; c <= nkeys; c += BQG_BUILD_THREADS) cell_start[c] = c < nkeys ? cnt[c] : binned;
-  __syncthreads();
-  // (d) scatter (the order inside a key's run is whatever the atomics give: the queries do not depend on it)
-  for_points([&](int i, float x, float y, float z) { sorted[atomicAdd(&cnt[key_of(i, x, y)], 1)] = make_float4(x, y, z, __int_as_float(i)); });
-}
+// (the frame layout, the cell coordinate and the grid's shape: cell_grid_device.h; the build: cell_grid.hip)
 
 // the first `ns` set bits of a wave's bitmap in ascending order -> o[0, ns) (empty slots repeat the first hit; no hit: 0), the
 // bitmap left all zero.  Lane l owns the words [l * wpl, (l + 1) * wpl) (wpl odd: conflict-free).
@@ -687,7 +550,7 @@ __device__ __forceinline__ void bq_bitmap_emit(unsigned* __restrict__ bm, int wp
 }
 
 struct BqQueryJob {
-  const unsigned char* ws;  // B frames of bqg_frame_bytes(N)
+  const unsigned char* ws;  // B frames of cg_frame_bytes(N)
   int* idxa;
   int* idxb;                // nullable: one radius
   size_t ws_stride;
@@ -713,15 +576,15 @@ __global__ __launch_bounds__(BQG_WAVES * 64) void bq_grid_query_kernel(const flo
   unsigned* bb = ba + 64 * wpl;
   for (int k = lane; k < 2 * 64 * wpl; k += 64) ba[k] = 0u;
   const unsigned char* w = job.ws + (size_t)b * job.ws_stride;
-  const BqGrid g = *reinterpret_cast<const BqGrid*>(w);
-  const int* cell_start = reinterpret_cast<const int*>(w + BQG_HEADER_BYTES);
-  const float4* sorted = reinterpret_cast<const float4*>(w + bqg_sorted_offset());
+  const CgHeader g = *reinterpret_cast<const CgHeader*>(w);
+  const int* cell_start = reinterpret_cast<const int*>(w + CG_HEADER_BYTES);
+  const float4* sorted = reinterpret_cast<const float4*>(w + cg_record_offset());
   const int ncell = g.nx * g.ny;
   const float nanf_ = __builtin_nanf("");
   for (int q = blockIdx.x * waves + wave; q < M; q += gridDim.x * waves) {
     const float* qp = new_xyz + ((size_t)b * M + q) * 3;
     const float qx = qp[0], qy = qp[1], qz = qp[2];
-    const float tx = bq_cell(qx, g.x0, g.inv_c), ty = bq_cell(qy, g.y0, g.inv_c);
+    const float tx = cg_cell(qx, g.x0, g.inv_c), ty = cg_cell(qy, g.y0, g.inv_c);
     // (a query more than a cell outside the grid, or with a non-finite coordinate, has no candidates; the comparisons are
     //  false for NaN)
     if (tx >= -1.f && tx <= (float)g.nx && ty >= -1.f && ty <= (float)g.ny) {
@@ -786,7 +649,7 @@ __global__ __launch_bounds__(BQG_WAVES * 64) void bq_grid_query_kernel(const flo
 
 extern "C" size_t v3d_ball_query_grid_workspace(int B, int N) {
   if (B < 1 || N < 1) return 0;
-  return (size_t)B * bqg_frame_bytes(N);
+  return (size_t)B * cg_frame_bytes(N);
 }
 
 // per-wave bitmaps of the query kernel: words per lane (odd) and waves per workgroup that fit 64 KB of LDS; waves = 0: N too large
@@ -800,29 +663,14 @@ extern "C" int v3d_ball_query_grid_build(int n_db, const float* const* xyz, cons
   if (n_db < 0 || n_db > BQG_MAX_JOBS || B < 0) return V3D_EINVAL;
   if (n_db == 0 || B == 0) return V3D_OK;
   if (!xyz || !N || !radius_max || !workspace || !workspace_bytes) return V3D_EINVAL;
-  BqBuildJobs jobs;
-  int n_max = 0;
+  V3dCellGridJob jobs[BQG_MAX_JOBS];
   for (int i = 0; i < n_db; i++) {
     const float r = fabsf(radius_max[i]);
     if (N[i] < 1 || !xyz[i] || !(r > 0.f) || !(r < 1e30f)) return V3D_EINVAL;
     if (!workspace[i] || ((uintptr_t)workspace[i] & 15) || workspace_bytes[i] < v3d_ball_query_grid_workspace(B, N[i])) return V3D_EINVAL;
-    jobs.j[i] = BqBuildJob{xyz[i], (unsigned char*)workspace[i], N[i], r * 1.01f};
-    n_max = std::max(n_max, N[i]);
+    jobs[i] = V3dCellGridJob{xyz[i], workspace[i], N[i], r * 1.01f, BQG_MAX_CHUNKS};
   }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)BQG_MAX_KEYS * sizeof(int);
-#define BQG_BUILD(PPT)                                                                                                        \
-  {                                                                                                                           \
-    V3D_CHECK_HIP(hipFuncSetAttribute((const void*)bq_grid_build_kernel<PPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    hipLaunchKernelGGL(bq_grid_build_kernel<PPT>, dim3(n_db, B), dim3(BQG_BUILD_THREADS), lds, st, jobs);                      \
-  }
-  if (n_max <= 4 * BQG_BUILD_THREADS) BQG_BUILD(4)
-  else if (n_max <= 12 * BQG_BUILD_THREADS) BQG_BUILD(12)
-  else if (n_max <= 20 * BQG_BUILD_THREADS) BQG_BUILD(20)
-  else BQG_BUILD(0)
-#undef BQG_BUILD
-  V3D_CHECK_LAUNCH();
-  return V3D_OK;
+  return v3d_i_cell_grid_build(n_db, jobs, B, (hipStream_t)stream);
 }
 
 extern "C" int v3d_ball_query_grid_query_many(int n_jobs, const float* new_xyz, int B, int M, const int32_t* N, const float* radius_a,
@@ -842,7 +690,7 @@ extern "C" int v3d_ball_query_grid_query_many(int n_jobs, const float* new_xyz, 
     bqg_bitmap_shape(N[i], wp, wv);
     if (wv < 1) return V3D_EUNSUPPORTED;
     wpl = std::max(wpl, wp), waves = std::min(waves, wv);  // (a bitmap of the largest database serves every job)
-    jobs.j[i] = BqQueryJob{(const unsigned char*)workspace[i], idx_a[i], two ? idx_b[i] : nullptr, bqg_frame_bytes(N[i]),
+    jobs.j[i] = BqQueryJob{(const unsigned char*)workspace[i], idx_a[i], two ? idx_b[i] : nullptr, cg_frame_bytes(N[i]),
                            radius_a[i] * radius_a[i], two ? radius_b[i] * radius_b[i] : 0.f, nsample_a[i], two ? nsample_b[i] : 0};
   }
   const size_t per_wave = (size_t)2 * 64 * wpl * sizeof(unsigned);

@@ -75,6 +75,18 @@ int v3d_i_nms_sorted(const void* prep_sorted, const int* order, int N, float iou
 
 int v3d_i_nms_mask_sorted(const void* prep_sorted, int N, float iou_threshold, unsigned long long* mask, hipStream_t st);
 
+// cell_grid.hip: the points of every (job, frame) binned into a cell grid (cell_grid_device.h: layout, shape rule), one launch.
+// The caller has checked its arguments: 1 <= n_jobs <= V3D_CELL_GRID_MAX_JOBS, B >= 1, N >= 1, cell_min > 0 and finite.
+#define V3D_CELL_GRID_MAX_JOBS 8
+struct V3dCellGridJob {
+  const float* xyz;  // (B, N, 3)
+  void* ws;          // B frames of cg_frame_bytes(N), 16-byte aligned
+  int N;
+  float cell_min;    // cells no smaller than this
+  int max_chunks;    // index chunks at most: 8 = the ball query's, 1 = records sorted by cell alone
+};
+int v3d_i_cell_grid_build(int n_jobs, const V3dCellGridJob* jobs, int B, hipStream_t st);
+
 // proposal_loss.hip: the backward of the fused losses (v3d_*_loss_scale).  buf = `groups` groups of `period` fp32 elements: the first
 // `head` of every group *= *g_head, the rest *= *g_tail (device scalars); about max_blocks workgroups at most.  groups, period > 0.
 int v3d_i_loss_scale(float* buf, int groups, long long period, long long head, const float* g_head, const float* g_tail, int max_blocks,

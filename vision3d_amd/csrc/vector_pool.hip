@@ -3,13 +3,12 @@
 // sub-voxel, and every sub-voxel multiplies its row with a weight of its own.  Upstream has no statement of it: the definition is this
 // repository's (detector/vector_pool.py in torch, tests/vector_pool_ref.py in numpy float64).
 //
-// v3d_vector_pool_query: the support points of every frame are binned into (x, y) cells of the call's own grid (the bounding box of
-//   the frame's finite points, cells of the reach R (2 - 1 / max(vx, vy)) or a power of two times it until at most VPQ_CELLS cells; a
-//   counting sort through the workspace: count, scan, fill -- four small launches, no host read).  A WAVE per query then walks the
-//   cell rows its reach touches, keeps the records inside the reach box in LDS (ballot compaction, VPQ_STAGE at a time) and one LANE
-//   per sub-voxel centre inserts the staged candidates into its sorted list of three.  The list is ordered by (d^2, row index) and
-//   holds one row per set of bit-equal coordinates (the lowest index), so it is the same whatever order the candidates arrive in:
-//   the fill's atomics place the records of a cell, they decide no result.
+// v3d_vector_pool_query: the support points of every frame are binned into (x, y) cells by the shared builder (cell_grid.hip; layout
+//   and shape rule: cell_grid_device.h) with cells no smaller than the reach R (2 - 1 / max(vx, vy)) and no index chunks: one launch,
+//   no host read.  A WAVE per query then walks the cell rows its reach touches, keeps the records inside the reach box in LDS (ballot
+//   compaction, VPQ_STAGE at a time) and one LANE per sub-voxel centre inserts the staged candidates into its sorted list of three.
+//   The list is ordered by (d^2, row index) and holds one row per set of bit-equal coordinates (the lowest index), so it is the same
+//   whatever order the candidates arrive in: the scatter's atomics place the records of a cell, they decide no result.
 // v3d_vector_pool_embed: a workgroup per (block of queries, sub-voxel): the sub-voxel's weight (Cr + 9, CL) and shift in LDS, the
 //   rows [sum_k w_k fr[idx_k] | c - p_1 | c - p_2 | c - p_3] of 256 / CL queries at a time built in LDS, then a thread per (query,
 //   column): an fmaf chain over the row in index order, + shift, ReLU, written into the sub-voxel's column block.
@@ -22,9 +21,9 @@
 #include <cmath>
 
 #include "../../include/vision3d_hip.h"
-#include "v3d_common.h"
+#include "v3d_internal.h"
+#include "cell_grid_device.h"
 
-#define VPQ_CELLS 16384        // (x, y) cells of a frame's grid at most
 #define VPQ_MAX_AXIS 3         // sub-voxels per axis
 #define VPQ_MAX_NV 27
 #define VPQ_MAX_B 64
@@ -33,124 +32,12 @@
 #define VPQ_MAX_CENTRES (1 << 22)
 #define VPQ_STAGE 512          // staged candidates of a wave
 #define VPQ_WAVES (V3D_BLOCK / V3D_WAVE)
-#define VPQ_SCAN_THREADS 1024
 #define VPE_MAX_CR 32
 #define VPE_MAX_K (VPE_MAX_CR + 9)
-
-struct VpqHeader {  // one per frame, first in the workspace; written by vpq_bounds_kernel
-  float min_x, min_y, inv_cell;
-  int nx, ny;
-  int pad[3];
-};
 
 struct VpqOffsets {
   float o[VPQ_MAX_NV][3];  // sub-voxel centre offsets: computed in double on the host, rounded once
 };
-
-struct VpqLayout {
-  VpqHeader* header;  // [B]
-  int* start;         // [B][VPQ_CELLS + 1]
-  int* cursor;        // [B][VPQ_CELLS]
-  float4* sorted;     // [B][N]: x, y, z, row index (bits)
-};
-
-static size_t vpq_workspace_bytes(int B, int N) {
-  return v3d_align((size_t)B * sizeof(VpqHeader)) + v3d_align((size_t)B * (VPQ_CELLS + 1) * 4) + v3d_align((size_t)B * VPQ_CELLS * 4) +
-         v3d_align((size_t)B * (size_t)N * 16);
-}
-
-__device__ __forceinline__ int vpq_cell_axis(float p, float lo, float inv, int n) {
-  const float f = floorf((p - lo) * inv);
-  return (int)fminf(fmaxf(f, 0.f), (float)(n - 1));
-}
-
-// One workgroup per frame: bounding box of the finite points, the grid's shape, the frame's counters cleared.
-__global__ __launch_bounds__(VPQ_SCAN_THREADS) void vpq_bounds_kernel(const float* __restrict__ xyz, int N, float reach, VpqLayout L) {
-  __shared__ float red[4][VPQ_SCAN_THREADS / V3D_WAVE];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float inf = __builtin_inff();
-  float lo_x = inf, lo_y = inf, hi_x = -inf, hi_y = -inf;
-  const float* p = xyz + (size_t)b * N * 3;
-  for (int i = tid; i < N; i += VPQ_SCAN_THREADS) {
-    const float x = p[3 * (size_t)i], y = p[3 * (size_t)i + 1];
-    if (fabsf(x) < inf && fabsf(y) < inf) {
-      lo_x = fminf(lo_x, x), hi_x = fmaxf(hi_x, x);
-      lo_y = fminf(lo_y, y), hi_y = fmaxf(hi_y, y);
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    lo_x = fminf(lo_x, __shfl_xor(lo_x, off)), hi_x = fmaxf(hi_x, __shfl_xor(hi_x, off));
-    lo_y = fminf(lo_y, __shfl_xor(lo_y, off)), hi_y = fmaxf(hi_y, __shfl_xor(hi_y, off));
-  }
-  if ((tid & 63) == 0) red[0][tid >> 6] = lo_x, red[1][tid >> 6] = hi_x, red[2][tid >> 6] = lo_y, red[3][tid >> 6] = hi_y;
-  __syncthreads();
-  if (tid == 0) {
-    for (int i = 1; i < VPQ_SCAN_THREADS / V3D_WAVE; i++) {
-      lo_x = fminf(lo_x, red[0][i]), hi_x = fmaxf(hi_x, red[1][i]);
-      lo_y = fminf(lo_y, red[2][i]), hi_y = fmaxf(hi_y, red[3][i]);
-    }
-    VpqHeader h = {};
-    if (lo_x <= hi_x && lo_y <= hi_y) {  // (a frame with a finite point)
-      float cell = reach;
-      for (int it = 0; it < 200; it++) {
-        const float fx = floorf((hi_x - lo_x) / cell) + 1.f, fy = floorf((hi_y - lo_y) / cell) + 1.f;
-        if (fx * fy <= (float)VPQ_CELLS) {
-          h.nx = (int)fx, h.ny = (int)fy;
-          break;
-        }
-        cell *= 2.f;
-      }
-      h.min_x = lo_x, h.min_y = lo_y, h.inv_cell = 1.f / cell;
-    }
-    L.header[b] = h;  // (nx = ny = 0: nothing is binned, every query of the frame comes back empty)
-  }
-  int* start = L.start + (size_t)b * (VPQ_CELLS + 1);
-  for (int c = tid; c <= VPQ_CELLS; c += VPQ_SCAN_THREADS) start[c] = 0;
-}
-
-__device__ __forceinline__ int vpq_cell_of(const VpqHeader& h, float x, float y) {
-  const float inf = __builtin_inff();
-  if (h.nx == 0 || !(fabsf(x) < inf) || !(fabsf(y) < inf)) return -1;
-  return vpq_cell_axis(y, h.min_y, h.inv_cell, h.ny) * h.nx + vpq_cell_axis(x, h.min_x, h.inv_cell, h.nx);
-}
-
-// fill = 0: count the rows of every cell (into start[cell + 1]); fill = 1: place the records behind the cell's cursor
-template <int FILL>
-__global__ __launch_bounds__(V3D_BLOCK) void vpq_bin_kernel(const float* __restrict__ xyz, int B, int N, VpqLayout L) {
-  const long long t = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x;
-  if (t >= (long long)B * N) return;
-  const int b = (int)(t / N), i = (int)(t - (long long)b * N);
-  const VpqHeader h = L.header[b];
-  const float x = xyz[3 * (size_t)t], y = xyz[3 * (size_t)t + 1], z = xyz[3 * (size_t)t + 2];
-  const int c = vpq_cell_of(h, x, y);
-  if (c < 0) return;
-  if (FILL == 0) {
-    atomicAdd(L.start + (size_t)b * (VPQ_CELLS + 1) + c + 1, 1);
-  } else {
-    const int slot = atomicAdd(L.cursor + (size_t)b * VPQ_CELLS + c, 1);
-    if ((unsigned)slot < (unsigned)N) L.sorted[(size_t)b * N + slot] = make_float4(x, y, z, __int_as_float(i));
-  }
-}
-
-// One workgroup per frame: start[c + 1] (counts) -> inclusive sums in place (start[0] = 0), cursor[c] = start[c].
-__global__ __launch_bounds__(VPQ_SCAN_THREADS) void vpq_scan_kernel(VpqLayout L) {
-  constexpr int PER = VPQ_CELLS / VPQ_SCAN_THREADS;
-  __shared__ int wsum[VPQ_SCAN_THREADS / V3D_WAVE];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int* start = L.start + (size_t)b * (VPQ_CELLS + 1);
-  int* cursor = L.cursor + (size_t)b * VPQ_CELLS;
-  int v[PER], run = 0;
-#pragma unroll
-  for (int k = 0; k < PER; k++) v[k] = start[1 + tid * PER + k], run += v[k];
-  int rows;
-  int base = v3d_block_scan_incl<VPQ_SCAN_THREADS / V3D_WAVE>(run, rows, wsum) - run;  // rows before this thread's cells
-#pragma unroll
-  for (int k = 0; k < PER; k++) {
-    cursor[tid * PER + k] = base;
-    base += v[k];
-    start[1 + tid * PER + k] = base;
-  }
-}
 
 // the sorted list of three of one centre: (d, i) ascending, empty slots (inf, INT_MAX); x / y / z bits of the chosen rows
 struct VpqTop {
@@ -198,14 +85,17 @@ __device__ __forceinline__ void vpq_insert(VpqTop& t, float d, int i, int xb, in
 
 __global__ __launch_bounds__(V3D_BLOCK) void vpq_query_kernel(const float* __restrict__ new_xyz, int rows, int M, int N, int nv,
                                                               const VpqOffsets offs, float reach_x, float reach_y, float reach_z,
-                                                              float r2, const VpqLayout L, int* __restrict__ idx, float* __restrict__ w) {
+                                                              float r2, const unsigned char* __restrict__ ws /*B frames of cg_frame_bytes(N)*/,
+                                                              int* __restrict__ idx, float* __restrict__ w) {
   __shared__ float4 stage[VPQ_WAVES][VPQ_STAGE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * VPQ_WAVES + wave;
   if (row >= rows) return;  // (wave-uniform; the LDS stage is a wave's own: no barrier below)
   const int b = row / M;
   const float qx = new_xyz[3 * (size_t)row], qy = new_xyz[3 * (size_t)row + 1], qz = new_xyz[3 * (size_t)row + 2];
-  const VpqHeader h = L.header[b];
+  const unsigned char* frame = ws + (size_t)b * cg_frame_bytes(N);
+  CgHeader h = {};  // (N = 0: nothing was built, nx = 0)
+  if (N > 0) h = *reinterpret_cast<const CgHeader*>(frame);
   const float inf = __builtin_inff();
   const int v = min(lane, nv - 1);
   const float cx = qx + offs.o[v][0], cy = qy + offs.o[v][1], cz = qz + offs.o[v][2];
@@ -230,15 +120,15 @@ __global__ __launch_bounds__(V3D_BLOCK) void vpq_query_kernel(const float* __res
   };
   const bool live = h.nx > 0 && fabsf(qx) < inf && fabsf(qy) < inf && fabsf(qz) < inf;
   if (live) {
-    const float fx0 = floorf((qx - reach_x - h.min_x) * h.inv_cell), fx1 = floorf((qx + reach_x - h.min_x) * h.inv_cell);
-    const float fy0 = floorf((qy - reach_y - h.min_y) * h.inv_cell), fy1 = floorf((qy + reach_y - h.min_y) * h.inv_cell);
-    // (a point's cell index is clamped into the grid, so a window beyond the last cell still reads the last cell; a window that ends
-    // before the first cell holds no point: every point lies at or above the frame's minimum)
+    const float fx0 = cg_cell(qx - reach_x, h.x0, h.inv_c), fx1 = cg_cell(qx + reach_x, h.x0, h.inv_c);
+    const float fy0 = cg_cell(qy - reach_y, h.y0, h.inv_c), fy1 = cg_cell(qy + reach_y, h.y0, h.inv_c);
+    // (the window is clamped into the grid, which holds every point; a window that ends before the first cell holds no point: every
+    // point lies at or above the frame's minimum)
     if (fx1 >= 0.f && fy1 >= 0.f) {
       const int x0 = (int)fminf(fmaxf(fx0, 0.f), (float)(h.nx - 1)), x1 = (int)fminf(fx1, (float)(h.nx - 1));
       const int y0 = (int)fminf(fmaxf(fy0, 0.f), (float)(h.ny - 1)), y1 = (int)fminf(fy1, (float)(h.ny - 1));
-      const int* start = L.start + (size_t)b * (VPQ_CELLS + 1);
-      const float4* sorted = L.sorted + (size_t)b * N;
+      const int* start = reinterpret_cast<const int*>(frame + CG_HEADER_BYTES);
+      const float4* sorted = reinterpret_cast<const float4*>(frame + cg_record_offset());
       for (int y = y0; y <= y1; y++) {
         const int beg = start[y * h.nx + x0], end = min(start[y * h.nx + x1 + 1], N);  // the cells of a row lie back to back
         for (int r0 = beg; r0 < end; r0 += V3D_WAVE) {
@@ -353,7 +243,7 @@ static int vp_offsets(VpqOffsets& o, int vx, int vy, int vz, float radius) {
 
 extern "C" size_t v3d_vector_pool_query_workspace(int B, int N) {
   if (B < 0 || N < 0) return 0;
-  return vpq_workspace_bytes(B, N);
+  return (size_t)B * cg_frame_bytes(N);
 }
 
 extern "C" int v3d_vector_pool_query(const float* xyz, const float* new_xyz, int B, int N, int M, int vx, int vy, int vz, float radius,
@@ -366,34 +256,21 @@ extern "C" int v3d_vector_pool_query(const float* xyz, const float* new_xyz, int
   if (B > VPQ_MAX_B || N > VPQ_MAX_N || (long long)B * N > VPQ_MAX_BN || (long long)B * M * nv > VPQ_MAX_CENTRES) return V3D_EUNSUPPORTED;
   if (B == 0 || M == 0) return V3D_OK;
   if (!new_xyz || !idx || !w || !workspace || (N > 0 && !xyz) || ((uintptr_t)workspace & 15)) return V3D_EINVAL;
-  if (workspace_bytes < vpq_workspace_bytes(B, N)) return V3D_EWORKSPACE;
+  if (workspace_bytes < v3d_vector_pool_query_workspace(B, N)) return V3D_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  V3dArena arena(workspace, workspace_bytes);
-  VpqLayout L;
-  L.header = arena.take<VpqHeader>(B);
-  L.start = arena.take<int>((size_t)B * (VPQ_CELLS + 1));
-  L.cursor = arena.take<int>((size_t)B * VPQ_CELLS);
-  L.sorted = arena.take<float4>((size_t)B * N);
-  if (!arena.ok()) return V3D_EWORKSPACE;
   // a neighbour of a centre lies within R of it and the centre within (1 - 1 / v) R of the query, per axis; the slack covers the
   // roundings of q + off and of the differences (coordinates of a few hundred metres: 3e-5 m)
   float reach[3];
   const int vs[3] = {vx, vy, vz};
   for (int a = 0; a < 3; a++) reach[a] = (float)((double)radius * (2.0 - 1.0 / vs[a]) * (1.0 + 1e-5) + 1e-3);
-  hipLaunchKernelGGL(vpq_bounds_kernel, dim3(B), dim3(VPQ_SCAN_THREADS), 0, st, xyz, N, std::max(reach[0], reach[1]), L);
-  V3D_CHECK_LAUNCH();
-  if (N > 0) {
-    const int blocks = v3d_ceil_div((long long)B * N, V3D_BLOCK);
-    hipLaunchKernelGGL(vpq_bin_kernel<0>, dim3(blocks), dim3(V3D_BLOCK), 0, st, xyz, B, N, L);
-    V3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vpq_scan_kernel, dim3(B), dim3(VPQ_SCAN_THREADS), 0, st, L);
-    V3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(vpq_bin_kernel<1>, dim3(blocks), dim3(V3D_BLOCK), 0, st, xyz, B, N, L);
-    V3D_CHECK_LAUNCH();
+  if (N > 0) {  // cells of the reach, records sorted by cell alone
+    const V3dCellGridJob job = {xyz, workspace, N, std::max(reach[0], reach[1]), 1};
+    rc = v3d_i_cell_grid_build(1, &job, B, st);
+    if (rc) return rc;
   }
   const int rows = B * M;
   hipLaunchKernelGGL(vpq_query_kernel, dim3(v3d_ceil_div(rows, VPQ_WAVES)), dim3(V3D_BLOCK), 0, st, new_xyz, rows, M, N, nv, offs, reach[0],
-                     reach[1], reach[2], radius * radius, L, idx, w);
+                     reach[1], reach[2], radius * radius, (const unsigned char*)workspace, idx, w);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

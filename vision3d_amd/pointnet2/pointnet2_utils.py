@@ -127,7 +127,7 @@ BALL_QUERY_ALGO = "grid"
 
 
 class BallQueryGrid:
-    """The cell grid of one database (csrc/pointops.hip: records sorted by (index chunk, (x, y) cell)), built for radii up to
+    """The cell grid of one database (csrc/cell_grid.hip: records sorted by (index chunk, (x, y) cell)), built for radii up to
     `radius_max`; holds its workspace.  `matches(xyz)`: was it built from this tensor as it is now."""
 
     def __init__(self, xyz, radius_max, workspace):
