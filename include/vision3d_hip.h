@@ -248,7 +248,10 @@ int v3d_points_in_boxes(const float* points, int N, int C, const float* boxes, i
  * Outputs sized for B*max_voxels rows: voxels (.,max_pts,C) f32 zero padded [may be NULL],
  * coords (.,4) i32 = (b,z,y,x), occupancy (.) i32, mean (.,C) f32 [may be NULL]; *n_voxels (device i32).
  * Order: frame-major, first-touch order of the input points within a frame; the first max_pts points
- * of a voxel (in input order) are kept -- identical to the sequential reference loop. */
+ * of a voxel (in input order) are kept -- identical to the sequential reference loop.
+ * max_pts <= 8 keeps a voxel's points in registers; 9 <= max_pts <= 64 (pillars) takes a wide path of two more launches (a
+ * thread per point ranks it inside its voxel; the mean is summed from the slots) that needs `voxels` (else V3D_EUNSUPPORTED)
+ * and zero-fills min(n_points, B*max_voxels) rows of it. */
 size_t v3d_voxelize_workspace(int n_points);
 int v3d_voxelize(const float* points, int n_points, int C, const int32_t* frame_offsets_host, int B,
                  const float* voxel_size_host, const float* bounds_host, int max_pts, int max_voxels, float* voxels,
@@ -827,6 +830,34 @@ int v3d_center_loss_scale(float* dmaps, int B, int n_cls, int H, int W, const fl
 size_t v3d_center_decode_workspace(int B, int n_cls, int H, int W);
 int v3d_center_decode(const float* maps, int B, int n_cls, int H, int W, const double* geom_host, int topk, float* boxes,
                       float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+
+/* ---- Pillar feature encoder (the PFN layer of PointPillars, arXiv 1812.05784; opt-in, cfg.PILLAR; no upstream counterpart).  The
+ * definition is this repository's: csrc/pillar_device.h states the arithmetic, detector/pillar.py:forward_torch restates it in torch,
+ * tests/pillar_ref.py in float64.  features (M, P, C) f32 point slots (x, y, z first), occupancy (M) i32 in [1, P], coordinates (M, 4)
+ * i32 (b, z, y, x); geometry_host = 6 floats (vx, vy, vz, vx / 2 + x0, vy / 2 + y0, vz / 2 + z0); W (channels, K = C + 6) f32.
+ * Row p < occupancy of a pillar: f = [point | xyz - mean xyz of the pillar's points | xyz - pillar centre], rows beyond are zero;
+ * y = W f (fmaf chain, k ascending); out[m][c] = max over ALL P rows of relu(fmaf(y, scale[c], shift[c])), so a pillar with fewer than
+ * P points also offers relu(shift[c]).  winner (M, channels) i32: the lowest row that reaches the maximum, or -1 where the padded
+ * candidate is strictly above every real row.  Limits: 1 <= P <= 64, 3 <= C <= 8, channels 64 or 128 -- beyond them V3D_EUNSUPPORTED
+ * before any launch.  The caller's stream, no host read, no atomics: bit-repeatable.
+ * _encode (eval, one launch): scale / shift = the folded BatchNorm (channels each) -> rows (M, channels).
+ * _train_fwd (three launches): batch statistics over all M * P rows (the padded rows count, with y = 0) from the K + K (K + 1) / 2 input
+ * moments accumulated in double, then the same encode.  bn (4, channels) f32 = mean, biased variance, scale = gamma / sqrt(var + eps),
+ * shift = beta - mean * scale; moments (K + K (K + 1) / 2) f64 is kept for the backward.  The running statistics are the caller's.
+ * _train_bwd (two launches): d_rows (M, channels) plus rows / winner / moments of the forward -> dW (channels, K), d_gamma, d_beta.
+ * workspace: 8-byte aligned, v3d_pillar_train_workspace bytes (either call). */
+int v3d_pillar_encode(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                      const float* geometry_host, const float* W, int channels, const float* scale, const float* shift, float* rows,
+                      v3d_stream_t stream);
+size_t v3d_pillar_train_workspace(int M, int P, int C, int channels);
+int v3d_pillar_train_fwd(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                         const float* geometry_host, const float* W, int channels, const float* gamma, const float* beta, float eps,
+                         float* rows, int32_t* winner, float* bn, double* moments, void* workspace, size_t workspace_bytes,
+                         v3d_stream_t stream);
+int v3d_pillar_train_bwd(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                         const float* geometry_host, const float* W, int channels, const float* gamma, float eps, const float* rows,
+                         const int32_t* winner, const float* d_rows, const double* moments, float* dW, float* d_gamma, float* d_beta,
+                         void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.

@@ -104,6 +104,11 @@ def _defaults():
         # > 0].  SIN_YAW: the yaw column of the box loss takes sin(P_yaw - G_yaw) as its smooth-L1 argument (no cliff between residuals 0
         # and pi).  The default OFFSET puts the bin edges on the diagonals, away from the axis-aligned headings and both anchor yaws
         DIRECTION=dict(ENABLED=False, OFFSET=0.7853981634, SIN_YAW=True, LOSS_WEIGHT=0.2),
+        # pillar feature encoder for SECOND (detector/pillar.py; the PFN layer of PointPillars, not in the reference), opt-in: with a voxel
+        # as tall as the grid the voxelizer's slots are pillars; every point becomes [channels | xyz - pillar mean | xyz - pillar centre],
+        # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
+        # straight into the map the dense RPN reads (no sparse 3-D backbone; the dense plans are 128 wide, so Second takes CHANNELS=128)
+        PILLAR=dict(ENABLED=False, CHANNELS=128),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",
@@ -147,9 +152,17 @@ SECOND_CAR = dict(
 # BASELINE.json configs[4]: Waymo-range sweep; MAX_VOXELS lifted.
 WAYMO_RANGE = dict(GRID_BOUNDS=[-75.2, -75.2, -2.0, 75.2, 75.2, 4.0], MAX_VOXELS=400000)
 
+# PointPillars' KITTI grid on the bounds above: 0.4 m pillars over the whole z extent, map stride 1 -- the same 200 x 176 map the RPN
+# sees behind the sparse backbone (0.05 m voxels, stride 8).
+PILLAR_KITTI = dict(VOXEL_SIZE=[0.4, 0.4, 4.0], STRIDES=[1], MAX_OCCUPANCY=32, MAX_VOXELS=12000, PILLAR=dict(ENABLED=True))
+
 
 def second_car_cfg():
     return _defaults().merge_from_dict(copy.deepcopy(SECOND_CAR))
+
+
+def pillar_car_cfg():
+    return second_car_cfg().merge_from_dict(copy.deepcopy(PILLAR_KITTI))
 
 
 def waymo_range_cfg():

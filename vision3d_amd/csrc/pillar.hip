@@ -1,0 +1,370 @@
+// pillar.hip -- the pillar feature encoder (PointPillars' PFN layer: linear, BatchNorm, ReLU, max over a pillar's points), forward
+// and backward; pillar_device.h states the arithmetic.  No upstream counterpart: the definition is this repository's
+// (detector/pillar.py:forward_torch in torch, tests/pillar_ref.py in float64).
+//
+// Every kernel gives a pillar to a wave: lane p loads point slot p, the pillar's xyz go through a 16-float LDS row per slot for the
+// mean in row order, then lane p writes its feature row there.
+//   pillar_encode_kernel   a lane owns channels lane (+ 64), their K weights in registers; it sweeps the pillar's n feature rows as
+//                          LDS broadcasts and stores its channels: the wave writes the pillar's output row as 256-byte runs.
+//   pillar_moments_kernel  training: lane p adds its row into K + K (K + 1) / 2 double moments in registers; one partial per workgroup.
+//   pillar_stats_kernel    one workgroup: partials in workgroup order -> moments -> mean, biased variance, scale, shift per channel.
+//   pillar_bwd_kernel      a lane reads its channels' winner rows from LDS and adds g, g y, g f into doubles it alone owns (no
+//                          reduction across lanes); the four waves' sums are added in wave order: one partial per workgroup.
+//   pillar_bwd_final_kernel  a workgroup per channel: partials in workgroup order, then the closed forms of pillar_device.h.
+// No atomics: every sum has one fixed order for a given M, so two runs agree bit for bit.  No host synchronisation.
+#include "pillar_device.h"
+#include "scan_device.h"
+#include "v3d_internal.h"
+
+#define PL_WAVES (V3D_BLOCK / V3D_WAVE)
+#define PL_ROW 16            // floats of a slot's LDS row (K <= 14), so a row is read as float4s
+#define PL_MAX_GROUPS 256    // workgroups of the two kernels that leave per-workgroup partials
+#define PL_MAX_ENCODE_GROUPS 4096
+
+namespace {
+
+using v3d::PillarGeom;
+
+// The pillar of this wave: n (0 for a wave without one), the lane's point and the pillar's centre.  Returns with the lane's feature
+// row in `f` (lanes >= n: untouched) and every live row in slab[p * PL_ROW ..].  Called by all threads of the workgroup at a
+// workgroup-uniform point; on return the rows may be read, and the caller puts a barrier behind its reads.
+template <int C>
+__device__ __forceinline__ int pl_stage(const float* __restrict__ feat, const int32_t* __restrict__ occ, const int32_t* __restrict__ coords,
+                                        int m, int M, int P, const PillarGeom& g, float* slab, float* f) {
+  const int lane = threadIdx.x & 63;
+  int n = 0;
+  float pt[C], centre[3];
+  if (m < M) {
+    n = min(max(occ[m], 0), P);
+#pragma unroll
+    for (int k = 0; k < 3; k++) centre[k] = v3d::pillar_centre(coords[(size_t)m * 4 + 3 - k], g.v[k], g.o[k]);
+  }
+  if (lane < n) {
+#pragma unroll
+    for (int k = 0; k < C; k++) pt[k] = feat[((size_t)m * P + lane) * C + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) slab[lane * PL_ROW + k] = pt[k];
+  }
+  __syncthreads();
+  float mean[3] = {0.f, 0.f, 0.f};
+  if (n > 0) v3d::pillar_mean(slab, PL_ROW, n, mean);
+  __syncthreads();
+  if (lane < n) {
+    v3d::pillar_feature_row<C>(pt, mean, centre, f);
+#pragma unroll
+    for (int k = 0; k < C + 6; k++) slab[lane * PL_ROW + k] = f[k];
+  }
+  __syncthreads();
+  return n;
+}
+
+template <int K>
+__device__ __forceinline__ void pl_read_row(const float* slab, int p, float* f) {
+  const float4* row = reinterpret_cast<const float4*>(slab + p * PL_ROW);
+  float t[PL_ROW];
+#pragma unroll
+  for (int q = 0; q < (K + 3) / 4; q++) {
+    const float4 v = row[q];
+    t[4 * q] = v.x;
+    t[4 * q + 1] = v.y;
+    t[4 * q + 2] = v.z;
+    t[4 * q + 3] = v.w;
+  }
+#pragma unroll
+  for (int k = 0; k < K; k++) f[k] = t[k];
+}
+
+template <int C, int NCH>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_encode_kernel(const float* __restrict__ feat, const int32_t* __restrict__ occ,
+                                                                  const int32_t* __restrict__ coords, int M, int P, PillarGeom g,
+                                                                  const float* __restrict__ W, const float* __restrict__ scale,
+                                                                  const float* __restrict__ shift, float* __restrict__ rows,
+                                                                  int32_t* __restrict__ winner) {
+  constexpr int K = C + 6, CH = 64 * NCH;
+  __shared__ float4 slabs[PL_WAVES][64 * PL_ROW / 4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* slab = reinterpret_cast<float*>(slabs[wave]);
+  float w[NCH][K], sc[NCH], sh[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    const int c = lane + 64 * j;
+#pragma unroll
+    for (int k = 0; k < K; k++) w[j][k] = W[c * K + k];
+    sc[j] = scale[c];
+    sh[j] = shift[c];
+  }
+  for (int base = blockIdx.x * PL_WAVES; base < M; base += gridDim.x * PL_WAVES) {
+    const int m = base + wave;
+    float f[K];
+    const int n = pl_stage<C>(feat, occ, coords, m, M, P, g, slab, f);
+    if (m < M) {
+      float best[NCH];
+      int win[NCH];
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+        best[j] = -1.f;
+        win[j] = -1;
+      }
+      for (int p = 0; p < n; p++) {
+        pl_read_row<K>(slab, p, f);
+        v3d::pillar_offer_row<K, NCH>(f, p, w, sc, sh, best, win);
+      }
+      if (n < P) {
+#pragma unroll
+        for (int j = 0; j < NCH; j++) v3d::pillar_offer(v3d::pillar_activation(0.f, sc[j], sh[j]), -1, best[j], win[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+        rows[(size_t)m * CH + lane + 64 * j] = best[j];
+        if (winner) winner[(size_t)m * CH + lane + 64 * j] = win[j];
+      }
+    }
+    __syncthreads();  // the next pillar's rows overwrite the slab
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_moments_kernel(const float* __restrict__ feat, const int32_t* __restrict__ occ,
+                                                                   const int32_t* __restrict__ coords, int M, int P, PillarGeom g,
+                                                                   double* __restrict__ partials) {
+  constexpr int K = C + 6, NM = K + K * (K + 1) / 2;
+  __shared__ float4 slabs[PL_WAVES][64 * PL_ROW / 4];
+  __shared__ double red[PL_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* slab = reinterpret_cast<float*>(slabs[wave]);
+  double S[NM];
+#pragma unroll
+  for (int i = 0; i < NM; i++) S[i] = 0.0;
+  for (int base = blockIdx.x * PL_WAVES; base < M; base += gridDim.x * PL_WAVES) {
+    float f[K];
+    const int n = pl_stage<C>(feat, occ, coords, base + wave, M, P, g, slab, f);
+    if (lane < n) v3d::pillar_moments_add<K>(f, S);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < NM; i++) {
+    const double t = v3d_block_sum<PL_WAVES>(S[i], red);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * NM + i] = t;
+  }
+}
+
+// One workgroup.  bn (4, CH): mean, biased variance, scale, shift.
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_stats_kernel(const double* __restrict__ partials, int groups, int K, int CH, double N,
+                                                                 const float* __restrict__ W, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float eps, double* __restrict__ moments,
+                                                                 float* __restrict__ bn) {
+  __shared__ double S[V3D_PILLAR_MAX_MOMENTS];
+  const int nm = v3d::pillar_moments(K);
+  for (int i = threadIdx.x; i < nm; i += V3D_BLOCK) {
+    double t = 0.0;
+    for (int b = 0; b < groups; b++) t += partials[(size_t)b * nm + i];
+    S[i] = t;
+    moments[i] = t;
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < CH; c += V3D_BLOCK) {
+    double mean, var, scale, shift;
+    v3d::pillar_bn_stats(K, S, N, W + (size_t)c * K, mean, var);
+    v3d::pillar_fold(mean, var, (double)gamma[c], (double)beta[c], (double)eps, scale, shift);
+    bn[c] = (float)mean;
+    bn[CH + c] = (float)var;
+    bn[2 * CH + c] = (float)scale;
+    bn[3 * CH + c] = (float)shift;
+  }
+}
+
+// partials (groups, CH, K + 2) double: G0, Gy, Gf[0..K) per channel.
+template <int C, int NCH>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_bwd_kernel(const float* __restrict__ feat, const int32_t* __restrict__ occ,
+                                                               const int32_t* __restrict__ coords, int M, int P, PillarGeom g,
+                                                               const float* __restrict__ W, const float* __restrict__ rows,
+                                                               const int32_t* __restrict__ winner, const float* __restrict__ d_rows,
+                                                               double* __restrict__ partials) {
+  constexpr int K = C + 6, CH = 64 * NCH, Q = K + 2;
+  __shared__ float4 slabs[PL_WAVES][64 * PL_ROW / 4];
+  __shared__ double red[PL_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* slab = reinterpret_cast<float*>(slabs[wave]);
+  float w[NCH][K];
+  double G[NCH][Q];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+#pragma unroll
+    for (int k = 0; k < K; k++) w[j][k] = W[(lane + 64 * j) * K + k];
+#pragma unroll
+    for (int q = 0; q < Q; q++) G[j][q] = 0.0;
+  }
+  for (int base = blockIdx.x * PL_WAVES; base < M; base += gridDim.x * PL_WAVES) {
+    const int m = base + wave;
+    float f[K];
+    const int n = pl_stage<C>(feat, occ, coords, m, M, P, g, slab, f);
+    if (m < M) {
+#pragma unroll
+      for (int j = 0; j < NCH; j++) {
+        const size_t at = (size_t)m * CH + lane + 64 * j;
+        const int win = winner[at];
+        const float go = rows[at] > 0.f && win >= -1 && win < n ? d_rows[at] : 0.f;  // (an index outside the pillar: no gradient)
+        float y = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++) f[k] = 0.f;
+        if (win >= 0 && win < n) {
+          pl_read_row<K>(slab, win, f);
+          y = v3d::pillar_dot<K>(w[j], f);
+        }
+        const double gd = (double)go;
+        G[j][0] += gd;
+        G[j][1] += gd * (double)y;
+#pragma unroll
+        for (int k = 0; k < K; k++) G[j][2 + k] += gd * (double)f[k];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      __syncthreads();
+      red[wave][lane] = G[j][q];
+      __syncthreads();
+      if (wave == 0) {
+        double t = red[0][lane];
+#pragma unroll
+        for (int v = 1; v < PL_WAVES; v++) t += red[v][lane];
+        partials[((size_t)blockIdx.x * CH + lane + 64 * j) * Q + q] = t;
+      }
+    }
+  }
+}
+
+// A workgroup of 64 threads per channel.
+__global__ __launch_bounds__(64) void pillar_bwd_final_kernel(const double* __restrict__ partials, int groups, int K, int CH, double N,
+                                                              const double* __restrict__ moments, const float* __restrict__ W,
+                                                              const float* __restrict__ gamma, float eps, float* __restrict__ dW,
+                                                              float* __restrict__ d_gamma, float* __restrict__ d_beta) {
+  __shared__ double Gs[V3D_PILLAR_MAX_K + 2];
+  const int c = blockIdx.x, Q = K + 2;
+  if ((int)threadIdx.x < Q) {
+    double t = 0.0;
+    for (int b = 0; b < groups; b++) t += partials[((size_t)b * CH + c) * Q + threadIdx.x];
+    Gs[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double dw[V3D_PILLAR_MAX_K], dg, db;
+    v3d::pillar_bwd_channel(K, moments, N, W + (size_t)c * K, (double)gamma[c], (double)eps, Gs[0], Gs[1], Gs + 2, dw, dg, db);
+    for (int k = 0; k < K; k++) dW[(size_t)c * K + k] = (float)dw[k];
+    d_gamma[c] = (float)dg;
+    d_beta[c] = (float)db;
+  }
+}
+
+int pl_groups(int M, int cap) { return std::min(v3d_ceil_div(M, PL_WAVES), cap); }
+
+bool pl_supported(int P, int C, int CH) {
+  return P >= 1 && P <= V3D_PILLAR_MAX_P && C >= V3D_PILLAR_MIN_C && C <= V3D_PILLAR_MAX_C && (CH == 64 || CH == 128);
+}
+
+PillarGeom pl_geom(const float* h) {
+  PillarGeom g;
+  for (int k = 0; k < 3; k++) {
+    g.v[k] = h[k];
+    g.o[k] = h[3 + k];
+  }
+  return g;
+}
+
+// Runs the statements with PC = the compile-time C.
+#define PL_DISPATCH_C(C_, ...)                            \
+  switch (C_) {                                           \
+    case 3: { constexpr int PC = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int PC = 4; __VA_ARGS__; } break; \
+    case 5: { constexpr int PC = 5; __VA_ARGS__; } break; \
+    case 6: { constexpr int PC = 6; __VA_ARGS__; } break; \
+    case 7: { constexpr int PC = 7; __VA_ARGS__; } break; \
+    default: { constexpr int PC = 8; __VA_ARGS__; } break; \
+  }
+
+int pl_launch_encode(const float* feat, const int32_t* occ, const int32_t* coords, int M, int P, int C, const PillarGeom& g, const float* W,
+                     int CH, const float* scale, const float* shift, float* rows, int32_t* winner, hipStream_t st) {
+  const dim3 grid(pl_groups(M, PL_MAX_ENCODE_GROUPS)), block(V3D_BLOCK);
+  PL_DISPATCH_C(C, {
+    if (CH == 64)
+      hipLaunchKernelGGL((pillar_encode_kernel<PC, 1>), grid, block, 0, st, feat, occ, coords, M, P, g, W, scale, shift, rows, winner);
+    else
+      hipLaunchKernelGGL((pillar_encode_kernel<PC, 2>), grid, block, 0, st, feat, occ, coords, M, P, g, W, scale, shift, rows, winner);
+  });
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+size_t pl_fwd_partials_bytes(int M, int C) { return v3d_align((size_t)pl_groups(M, PL_MAX_GROUPS) * v3d::pillar_moments(C + 6) * sizeof(double)); }
+
+}  // namespace
+
+extern "C" int v3d_pillar_encode(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                                 const float* geometry_host, const float* W, int channels, const float* scale, const float* shift,
+                                 float* rows, v3d_stream_t stream) {
+  if (M < 0 || !geometry_host) return V3D_EINVAL;
+  if (!pl_supported(P, C, channels)) return V3D_EUNSUPPORTED;
+  if (M == 0) return V3D_OK;
+  if (!features || !occupancy || !coordinates || !W || !scale || !shift || !rows) return V3D_EINVAL;
+  return pl_launch_encode(features, occupancy, coordinates, M, P, C, pl_geom(geometry_host), W, channels, scale, shift, rows, nullptr,
+                          (hipStream_t)stream);
+}
+
+extern "C" size_t v3d_pillar_train_workspace(int M, int P, int C, int channels) {
+  if (M <= 0 || !pl_supported(P, C, channels)) return 256;
+  const size_t fwd = pl_fwd_partials_bytes(M, C);
+  const size_t bwd = v3d_align((size_t)pl_groups(M, PL_MAX_GROUPS) * channels * (C + 8) * sizeof(double));
+  return std::max(fwd, bwd);
+}
+
+extern "C" int v3d_pillar_train_fwd(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                                    const float* geometry_host, const float* W, int channels, const float* gamma, const float* beta,
+                                    float eps, float* rows, int32_t* winner, float* bn, double* moments, void* workspace,
+                                    size_t workspace_bytes, v3d_stream_t stream) {
+  if (M < 0 || !geometry_host) return V3D_EINVAL;
+  if (!pl_supported(P, C, channels)) return V3D_EUNSUPPORTED;
+  if (M == 0) return V3D_OK;
+  if (!features || !occupancy || !coordinates || !W || !gamma || !beta || !rows || !winner || !bn || !moments || !workspace) return V3D_EINVAL;
+  if (workspace_bytes < pl_fwd_partials_bytes(M, C) || ((uintptr_t)workspace & 7) || ((uintptr_t)moments & 7)) return V3D_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const PillarGeom g = pl_geom(geometry_host);
+  const int groups = pl_groups(M, PL_MAX_GROUPS);
+  double* partials = (double*)workspace;
+  PL_DISPATCH_C(C, { hipLaunchKernelGGL((pillar_moments_kernel<PC>), dim3(groups), dim3(V3D_BLOCK), 0, st, features, occupancy, coordinates, M, P, g, partials); });
+  V3D_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pillar_stats_kernel, dim3(1), dim3(V3D_BLOCK), 0, st, (const double*)partials, groups, C + 6, channels,
+                     (double)M * (double)P, W, gamma, beta, eps, moments, bn);
+  V3D_CHECK_LAUNCH();
+  return pl_launch_encode(features, occupancy, coordinates, M, P, C, g, W, channels, bn + 2 * channels, bn + 3 * channels, rows, winner, st);
+}
+
+extern "C" int v3d_pillar_train_bwd(const float* features, const int32_t* occupancy, const int32_t* coordinates, int M, int P, int C,
+                                    const float* geometry_host, const float* W, int channels, const float* gamma, float eps,
+                                    const float* rows, const int32_t* winner, const float* d_rows, const double* moments, float* dW,
+                                    float* d_gamma, float* d_beta, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
+  if (M <= 0 || !geometry_host) return V3D_EINVAL;
+  if (!pl_supported(P, C, channels)) return V3D_EUNSUPPORTED;
+  if (!features || !occupancy || !coordinates || !W || !gamma || !rows || !winner || !d_rows || !moments || !dW || !d_gamma || !d_beta ||
+      !workspace)
+    return V3D_EINVAL;
+  const int groups = pl_groups(M, PL_MAX_GROUPS);
+  if (workspace_bytes < (size_t)groups * channels * (C + 8) * sizeof(double) || ((uintptr_t)workspace & 7) || ((uintptr_t)moments & 7))
+    return V3D_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const PillarGeom g = pl_geom(geometry_host);
+  double* partials = (double*)workspace;
+  PL_DISPATCH_C(C, {
+    if (channels == 64)
+      hipLaunchKernelGGL((pillar_bwd_kernel<PC, 1>), dim3(groups), dim3(V3D_BLOCK), 0, st, features, occupancy, coordinates, M, P, g, W, rows, winner, d_rows, partials);
+    else
+      hipLaunchKernelGGL((pillar_bwd_kernel<PC, 2>), dim3(groups), dim3(V3D_BLOCK), 0, st, features, occupancy, coordinates, M, P, g, W, rows, winner, d_rows, partials);
+  });
+  V3D_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pillar_bwd_final_kernel, dim3(channels), dim3(64), 0, st, (const double*)partials, groups, C + 6, channels,
+                     (double)M * (double)P, moments, W, gamma, eps, dW, d_gamma, d_beta);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}

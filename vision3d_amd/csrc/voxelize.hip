@@ -15,11 +15,15 @@
 //               sequential loop.  The same thread walks its voxel's list, keeps the max_pts smallest
 //               point indices (== first-come order), writes coords/occupancy/points and the mean.
 //   (K2 + K3 share a launch; for ONE frame K2 + K3 + K4 are a single-pass chained scan in one launch.)
+//   WIDE      : max_pts above VOX_MAX_PTS (pillars: up to VOX_MAX_PTS_WIDE slots).  K4 keeps no point list in registers: it only
+//               counts its voxel's points and records the voxel's row; K5 (a thread per POINT) ranks its point among the voxel's by
+//               walking the same list and writes it into its slot of the zero-filled output; K6 sums the slots in order for the mean.
 // No host synchronisation: the voxel count stays in device memory.
 #include "v3d_internal.h"
 
 #define VOX_MAX_FRAMES 64
 #define VOX_MAX_PTS 8
+#define VOX_MAX_PTS_WIDE 64
 // points per block of the count/emit kernels: ONE 256-thread round, so the per-voxel list walks of a
 // whole frame run concurrently (a 2048-point chunk serialised 8 latency-bound rounds per block)
 #define VOX_CHUNK 256
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_count_scan_kernel(const int* __
 // is running or done) and emits at prefix + rank; the highest-index block writes the voxel count.  The same single-pass chained
 // scan as rb_scan_emit_kernel (rulebook.hip); replaces vox_count_scan_kernel + this kernel's unchained form, which stay for
 // batches (B > 1: the per-frame bases need every earlier frame's total).
-template <bool CHAINED>
+template <bool CHAINED, bool WIDE = false>
 __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __restrict__ pts, const VoxParams p,
                                                              const int* __restrict__ pt_slot,
                                                              const unsigned* __restrict__ first,
@@ -147,7 +151,8 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
                                                              float* __restrict__ voxels, int* __restrict__ coords,
                                                              int* __restrict__ occupancy, float* __restrict__ mean,
                                                              const V3dHash site_hash, int* __restrict__ site_vals,
-                                                             int site_d, int site_h, int site_w, int* __restrict__ n_voxels) {
+                                                             int site_d, int site_h, int site_w, int* __restrict__ n_voxels,
+                                                             int* __restrict__ row_of_first /*WIDE: row of the voxel point i opens, or -1*/) {
   __shared__ int lds[4];
   static_assert(VOX_CHUNK == V3D_BLOCK, "one round per block");
   const int i = blockIdx.x * VOX_CHUNK + threadIdx.x;
@@ -171,17 +176,19 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
     for (int j = 0; j < 3; j++) c[j] = (int)floorf((q[j] - p.lo[j]) / p.vs[j]);
     for (int j = head[pt_slot[i]], guard = 0; j >= 0 && guard < p.n_points; j = next[j], guard++) {
       cnt++;
-      int x = j;
+      if constexpr (!WIDE) {
+        int x = j;
 #pragma unroll
-      for (int k = 0; k < VOX_MAX_PTS; k++) {  // sorted insert by compare-exchange
-        const int lo_ = min(best[k], x);
-        x = max(best[k], x);
-        best[k] = lo_;
+        for (int k = 0; k < VOX_MAX_PTS; k++) {  // sorted insert by compare-exchange
+          const int lo_ = min(best[k], x);
+          x = max(best[k], x);
+          best[k] = lo_;
+        }
       }
     }
   }
   const int occ = min(cnt, p.max_pts);
-  if (p.C == 4) {
+  if (!WIDE && p.C == 4) {
     // four channels (x, y, z, intensity): the points as 16-byte loads, all in flight at once (the generic loop below issues
     // max_pts x C scalar loads); same sums in the same order
 #pragma unroll
@@ -200,7 +207,10 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
   if (!flag) return;
   const int b = CHAINED ? 0 : frame_of(p, i);
   const int local = CHAINED ? rank : rank - frame_base[b];
-  if (local >= p.max_voxels) return;  // `continue` variant of the max_voxels rule
+  if (local >= p.max_voxels) {  // `continue` variant of the max_voxels rule
+    if constexpr (WIDE) row_of_first[i] = -1;
+    return;
+  }
   const int v = CHAINED ? local : out_base[b] + local;
   reinterpret_cast<int4*>(coords)[v] = make_int4(b, c[2], c[1], c[0]);
   if (site_vals) {  // the coordinate hash the first submanifold rulebook needs (saves the rb_hash_build launch)
@@ -210,6 +220,10 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
     if (hs >= 0) site_vals[hs] = v;
   }
   occupancy[v] = occ;
+  if constexpr (WIDE) {  // the points and the mean: vox_fill_wide_kernel, vox_mean_wide_kernel
+    row_of_first[i] = v;
+    return;
+  }
   if (p.C == 4) {
     float4 sm = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
@@ -237,12 +251,45 @@ __global__ __launch_bounds__(V3D_BLOCK) void vox_emit_kernel(const float* __rest
   }
 }
 
+// WIDE K5: point i goes to slot (number of its voxel's points with a smaller index) of its voxel's row, when that is below max_pts:
+// the first max_pts points in input order, as the register list of the narrow kernel keeps them.  voxels is zero on entry.
+__global__ __launch_bounds__(V3D_BLOCK) void vox_fill_wide_kernel(const float* __restrict__ pts, const VoxParams p,
+                                                                  const int* __restrict__ pt_slot, const unsigned* __restrict__ first,
+                                                                  const int* __restrict__ head, const int* __restrict__ next,
+                                                                  const int* __restrict__ row_of_first, float* __restrict__ voxels) {
+  const int i = blockIdx.x * V3D_BLOCK + threadIdx.x;
+  if (i >= p.n_points) return;
+  const int s = pt_slot[i];
+  if (s < 0) return;
+  const unsigned f = first[s];
+  if (f >= (unsigned)p.n_points) return;
+  const int v = row_of_first[f];
+  if (v < 0) return;
+  int rank = 0;
+  for (int j = head[s], guard = 0; j >= 0 && guard < p.n_points; j = next[j], guard++) rank += j < i;
+  if (rank >= p.max_pts) return;
+  for (int ch = 0; ch < p.C; ch++) voxels[((size_t)v * p.max_pts + rank) * p.C + ch] = pts[(size_t)i * p.C + ch];
+}
+
+// WIDE K6: mean[v][ch] = (slot 0 + slot 1 + ... in order, the zero slots included) / occupancy -- the narrow kernel's sum.
+__global__ __launch_bounds__(V3D_BLOCK) void vox_mean_wide_kernel(const float* __restrict__ voxels, const int* __restrict__ occupancy,
+                                                                  const int* __restrict__ n_voxels, int rows_cap, int max_pts, int C,
+                                                                  float* __restrict__ mean) {
+  const long long total = (long long)min(*n_voxels, rows_cap) * C;
+  for (long long t = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x; t < total; t += (long long)gridDim.x * V3D_BLOCK) {
+    const int v = (int)(t / C), ch = (int)(t % C);
+    float sacc = 0.f;
+    for (int k = 0; k < max_pts; k++) sacc += voxels[((size_t)v * max_pts + k) * C + ch];
+    mean[t] = sacc / (float)occupancy[v];
+  }
+}
+
 extern "C" size_t v3d_voxelize_workspace(int n_points) {
   const size_t n = (size_t)(n_points > 0 ? n_points : 1);
   const size_t cap = v3d_hash_capacity((long long)n);
   const size_t chunks = (n + VOX_CHUNK - 1) / VOX_CHUNK;
   return v3d_align(cap * 8) + 2 * v3d_align(cap * 4) + 2 * v3d_align(n * 4) + v3d_align(chunks * 4) +
-         2 * v3d_align((VOX_MAX_FRAMES + 1) * 4) + 256;
+         2 * v3d_align((VOX_MAX_FRAMES + 1) * 4) + v3d_align(n * 4) /*WIDE: row_of_first*/ + 256;
 }
 
 extern "C" int v3d_voxelize(const float* points, int n_points, int C, const int32_t* frame_offsets_host, int B,
@@ -261,8 +308,10 @@ int v3d_i_voxelize(const float* points, int n_points, int C, const int32_t* fram
                    int32_t* coords, int32_t* occupancy, float* mean, int32_t* n_voxels, void* workspace,
                    size_t workspace_bytes, int clear_tables, const V3dRbHash* site_hash, const int32_t* site_shape,
                    hipStream_t st) {
-  if (n_points < 0 || C < 3 || B < 1 || B > VOX_MAX_FRAMES || max_pts < 1 || max_pts > VOX_MAX_PTS || max_voxels < 1)
+  if (n_points < 0 || C < 3 || B < 1 || B > VOX_MAX_FRAMES || max_pts < 1 || max_pts > VOX_MAX_PTS_WIDE || max_voxels < 1)
     return V3D_EINVAL;
+  const bool wide = max_pts > VOX_MAX_PTS;
+  if (wide && !voxels) return V3D_EUNSUPPORTED;  // (the mean of the wide path is summed from the point slots)
   if (!frame_offsets_host || !voxel_size_host || !bounds_host || !coords || !occupancy || !n_voxels) return V3D_EINVAL;
   if (frame_offsets_host[0] != 0 || frame_offsets_host[B] != n_points) return V3D_EINVAL;
   if (n_points == 0) {
@@ -299,6 +348,7 @@ int v3d_i_voxelize(const float* points, int n_points, int C, const int32_t* fram
   int* chunk_counts = ar.take<int>(chunks);
   int* frame_base = ar.take<int>(VOX_MAX_FRAMES + 1);
   int* out_base = ar.take<int>(VOX_MAX_FRAMES + 1);
+  int* row_of_first = wide ? ar.take<int>(n_points) : (int*)nullptr;
   if (!ar.ok()) return V3D_EWORKSPACE;
   if (clear_tables) {
     V3D_CHECK_HIP(v3d_fill_async(keys, 0xFF, (size_t)((char*)head - (char*)keys) + (size_t)cap * 4, st));
@@ -311,14 +361,38 @@ int v3d_i_voxelize(const float* points, int n_points, int C, const int32_t* fram
   V3dHash sh = v3d_make_hash(site_hash ? site_hash->keys : keys, site_hash ? site_hash->hcap : cap);
   int* site_vals = (site_hash && site_shape) ? site_hash->vals : (int*)nullptr;
   const int sd = site_shape ? site_shape[0] : 0, shh = site_shape ? site_shape[1] : 0, sw = site_shape ? site_shape[2] : 0;
+  if (wide) {
+    const long long rows_cap = std::min<long long>(n_points, (long long)B * max_voxels);  // *n_voxels never exceeds either
+    V3D_CHECK_HIP(v3d_fill_async(voxels, 0, (size_t)rows_cap * max_pts * C * sizeof(float), st));
+    if (B == 1) {
+      hipLaunchKernelGGL((vox_emit_kernel<true, true>), dim3(chunks), dim3(V3D_BLOCK), 0, st, points, p, pt_slot, first, head, next,
+                         chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels,
+                         row_of_first);
+    } else {
+      hipLaunchKernelGGL(vox_count_scan_kernel, dim3(chunks), dim3(V3D_BLOCK), 0, st, pt_slot, first, p, chunk_counts, chunks,
+                         frame_base, out_base, n_voxels);
+      hipLaunchKernelGGL((vox_emit_kernel<false, true>), dim3(chunks), dim3(V3D_BLOCK), 0, st, points, p, pt_slot, first, head, next,
+                         chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels,
+                         row_of_first);
+    }
+    hipLaunchKernelGGL(vox_fill_wide_kernel, dim3(chunks), dim3(V3D_BLOCK), 0, st, points, p, pt_slot, first, head, next, row_of_first,
+                       voxels);
+    if (mean)
+      hipLaunchKernelGGL(vox_mean_wide_kernel, dim3(std::min(v3d_ceil_div(rows_cap * C, V3D_BLOCK), 2048)), dim3(V3D_BLOCK), 0, st, voxels,
+                         occupancy, n_voxels, (int)rows_cap, max_pts, C, mean);
+    V3D_CHECK_LAUNCH();
+    return V3D_OK;
+  }
   if (B == 1) {  // one frame: count + scan + emit as a single-pass chained scan, 2 launches per voxelization instead of 3
     hipLaunchKernelGGL(vox_emit_kernel<true>, dim3(chunks), dim3(V3D_BLOCK), 0, st, points, p, pt_slot, first, head, next,
-                       chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels);
+                       chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels,
+                       (int*)nullptr);
   } else {
     hipLaunchKernelGGL(vox_count_scan_kernel, dim3(chunks), dim3(V3D_BLOCK), 0, st, pt_slot, first, p, chunk_counts, chunks,
                        frame_base, out_base, n_voxels);
     hipLaunchKernelGGL(vox_emit_kernel<false>, dim3(chunks), dim3(V3D_BLOCK), 0, st, points, p, pt_slot, first, head, next,
-                       chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels);
+                       chunk_counts, frame_base, out_base, voxels, coords, occupancy, mean, sh, site_vals, sd, shh, sw, n_voxels,
+                       (int*)nullptr);
   }
   V3D_CHECK_LAUNCH();
   return V3D_OK;

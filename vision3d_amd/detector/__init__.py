@@ -15,6 +15,7 @@ _EXPORTS = {
     "VectorPoolAggregationMSG": "vector_pool",
     "CenterHead": "center_head",
     "CenterLoss": "center_head",
+    "PillarFeatureNet": "pillar",
 }
 __all__ = sorted(_EXPORTS)
 

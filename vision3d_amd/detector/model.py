@@ -48,6 +48,8 @@ class PV_RCNN(nn.Module):
         from .center_head import refuse_centerhead
         refuse_centerhead(cfg, "PV_RCNN")
         proposal.refuse_direction(cfg, "PV_RCNN (stage 2 refines the yaw it is given)")
+        from .pillar import refuse_pillar
+        refuse_pillar(cfg, "PV_RCNN (its keypoints read the sparse backbone's levels)")
         self.cfg = cfg
         self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
         if self.voxel_pool and vector_pool.vectorpool_config(cfg)["ENABLED"]:

@@ -1,0 +1,253 @@
+"""Pillar feature encoder for SECOND (the PFN layer of PointPillars, arXiv 1812.05784), opt-in: cfg.PILLAR.
+
+No upstream counterpart; the definition is this repository's (csrc/pillar_device.h, restated in float64 by tests/pillar_ref.py).
+With a voxel as tall as the grid the Preprocessor's voxels are pillars: `features` (M, P, C) point slots, `occupancy` (M),
+`coordinates` (M, 4) = (b, 0, y, x).  Per pillar: every real point becomes [its C channels | xyz - mean xyz of the pillar's points |
+xyz - pillar centre] (K = C + 6), the padded slots stay zero; linear (no bias) -> BatchNorm1d over ALL M * P rows (the padded rows
+count, as in the published encoder, so its checkpoints keep their meaning) -> ReLU -> maximum over all P rows.  The rows are
+scattered into the (B, CHANNELS, H, W) canvas the dense RPN reads; no 3-D convolution runs.
+
+PillarFeatureNet.forward runs csrc/pillar.hip (one launch in eval mode; three forwards and two backwards in training, through
+PillarEncodeFunction); forward_torch is the op-by-op statement of the same arithmetic, and the path of CPU tensors and of shapes
+beyond the native limits (P <= 64, 3 <= C <= 8, CHANNELS 64 or 128).  Gradients reach linear.weight, norm.weight and norm.bias, never
+the points.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from .. import _lib as L
+from .. import spconv
+
+PILLAR_DEFAULTS = dict(ENABLED=False, CHANNELS=128)
+MAX_P, MIN_C, MAX_C, WIDTHS = 64, 3, 8, (64, 128)  # the native limits (csrc/pillar_device.h)
+
+
+def pillar_config(cfg):
+    """-> the keys of cfg.PILLAR over their defaults (a config written before the key existed means "disabled")."""
+    out = dict(PILLAR_DEFAULTS)
+    out.update(cfg.get("PILLAR") or {})
+    return out
+
+
+def pillar_enabled(cfg):
+    return bool(pillar_config(cfg)["ENABLED"])
+
+
+def refuse_pillar(cfg, what):
+    """The entry points that do not know the pillar encoder yet (follow-ups) say so instead of running the sparse backbone beside it."""
+    if pillar_enabled(cfg):
+        raise ValueError(f"cfg.PILLAR.ENABLED: {what} does not support the pillar encoder yet (Second.forward / inference on a "
+                         "Preprocessor item do)")
+
+
+def pillar_geometry(cfg):
+    """-> (six fp32 numbers vx, vy, vz, vx / 2 + x0, vy / 2 + y0, vz / 2 + z0 -- each offset ONE fp32 sum --, (H, W)); refuses a grid
+    that is not one pillar tall."""
+    voxel, bounds = np.asarray(cfg.VOXEL_SIZE, np.float64), np.asarray(cfg.GRID_BOUNDS, np.float64).reshape(2, 3)
+    cells = np.round((bounds[1] - bounds[0]) / voxel).astype(np.int64)  # the voxelizer's grid (x, y, z): spconv/utils.py
+    if cells[2] != 1 or abs(voxel[2] - (bounds[1, 2] - bounds[0, 2])) > 1e-6 * (bounds[1, 2] - bounds[0, 2]):
+        raise ValueError(f"cfg.PILLAR.ENABLED: VOXEL_SIZE[2] = {voxel[2]} must span the z extent of GRID_BOUNDS exactly once "
+                         f"({bounds[0, 2]} .. {bounds[1, 2]}): a pillar is one voxel tall")
+    v = voxel.astype(np.float32)
+    o = v / np.float32(2) + bounds[0].astype(np.float32)
+    return tuple(float(x) for x in np.concatenate([v, o])), (int(cells[1]), int(cells[0]))
+
+
+def _native_shape(features, channels):
+    return features.dim() == 3 and 1 <= features.shape[1] <= MAX_P and MIN_C <= features.shape[2] <= MAX_C and channels in WIDTHS
+
+
+def pillar_encode(features, occupancy, coordinates, geom, weight, scale, shift):
+    """v3d_pillar_encode (eval): -> rows (M, CHANNELS) f32; one launch, no host read."""
+    L.require_gpu("pillar_encode", features, occupancy, coordinates, weight, scale, shift)
+    features, weight = L.as_f32("pillar_encode", features), L.as_f32("pillar_encode", weight)
+    occupancy, coordinates = L.as_i32("pillar_encode", occupancy), L.as_i32("pillar_encode", coordinates)
+    scale, shift = L.as_f32("pillar_encode", scale), L.as_f32("pillar_encode", shift)
+    M, P, C = features.shape
+    CH = weight.shape[0]
+    rows = torch.empty((M, CH), dtype=torch.float32, device=features.device)
+    with L.device_guard(features.device):
+        L.check(L.lib().v3d_pillar_encode(L.ptr(features), L.ptr(occupancy), L.ptr(coordinates), M, P, C, L.host_f32(geom), L.ptr(weight), CH,
+                                          L.ptr(scale), L.ptr(shift), L.ptr(rows), L.stream_ptr()), "pillar_encode")
+    return rows
+
+
+def pillar_train_forward(features, occupancy, coordinates, geom, weight, gamma, beta, eps):
+    """v3d_pillar_train_fwd: -> rows (M, CH) f32, winner (M, CH) i32, bn (4, CH) f32 = batch mean, biased variance, scale, shift,
+    moments f64 (kept for the backward); three launches, no host read.  M >= 1."""
+    L.require_gpu("pillar_train_forward", features, occupancy, coordinates, weight, gamma, beta)
+    features, weight = L.as_f32("pillar_train_forward", features), L.as_f32("pillar_train_forward", weight)
+    occupancy, coordinates = L.as_i32("pillar_train_forward", occupancy), L.as_i32("pillar_train_forward", coordinates)
+    gamma, beta = L.as_f32("pillar_train_forward", gamma), L.as_f32("pillar_train_forward", beta)
+    M, P, C = features.shape
+    CH, K = weight.shape
+    dev = features.device
+    rows = torch.empty((M, CH), dtype=torch.float32, device=dev)
+    winner = torch.empty((M, CH), dtype=torch.int32, device=dev)
+    bn = torch.empty((4, CH), dtype=torch.float32, device=dev)
+    moments = torch.empty(K + K * (K + 1) // 2, dtype=torch.float64, device=dev)
+    lib = L.lib()
+    ws = L.workspace(lib.v3d_pillar_train_workspace(M, P, C, CH), dev)
+    with L.device_guard(dev):
+        L.check(lib.v3d_pillar_train_fwd(L.ptr(features), L.ptr(occupancy), L.ptr(coordinates), M, P, C, L.host_f32(geom), L.ptr(weight), CH,
+                                         L.ptr(gamma), L.ptr(beta), float(eps), L.ptr(rows), L.ptr(winner), L.ptr(bn), L.ptr(moments),
+                                         L.ptr(ws), ws.numel(), L.stream_ptr()), "pillar_train_forward")
+    return rows, winner, bn, moments
+
+
+def pillar_train_backward(features, occupancy, coordinates, geom, weight, gamma, eps, rows, winner, d_rows, moments):
+    """v3d_pillar_train_bwd: -> dW (CH, K), d_gamma (CH), d_beta (CH) f32; two launches, no host read."""
+    L.require_gpu("pillar_train_backward", features, d_rows)
+    d_rows = L.as_f32("pillar_train_backward", d_rows)
+    winner = L.as_i32("pillar_train_backward", winner)
+    M, P, C = features.shape
+    CH, K = weight.shape
+    dev = features.device
+    dW = torch.empty((CH, K), dtype=torch.float32, device=dev)
+    d_gamma = torch.empty(CH, dtype=torch.float32, device=dev)
+    d_beta = torch.empty(CH, dtype=torch.float32, device=dev)
+    lib = L.lib()
+    ws = L.workspace(lib.v3d_pillar_train_workspace(M, P, C, CH), dev)
+    with L.device_guard(dev):
+        L.check(lib.v3d_pillar_train_bwd(L.ptr(features), L.ptr(occupancy), L.ptr(coordinates), M, P, C, L.host_f32(geom), L.ptr(weight), CH,
+                                         L.ptr(gamma), float(eps), L.ptr(rows), L.ptr(winner), L.ptr(d_rows), L.ptr(moments), L.ptr(dW),
+                                         L.ptr(d_gamma), L.ptr(d_beta), L.ptr(ws), ws.numel(), L.stream_ptr()), "pillar_train_backward")
+    return dW, d_gamma, d_beta
+
+
+class PillarEncodeFunction(torch.autograd.Function):
+    """Training forward / backward of the encoder on csrc/pillar.hip: (features, occupancy, coordinates, geom, eps, weight, gamma,
+    beta) -> rows, winner, bn (mean, biased variance, scale, shift); only `rows` carries a gradient, to weight, gamma and beta."""
+
+    @staticmethod
+    def forward(ctx, features, occupancy, coordinates, geom, eps, weight, gamma, beta):
+        features, occupancy, coordinates = features.contiguous(), occupancy.contiguous(), coordinates.contiguous()
+        weight, gamma = weight.detach().contiguous(), gamma.detach().contiguous()
+        rows, winner, bn, moments = pillar_train_forward(features, occupancy, coordinates, geom, weight, gamma, beta.detach(), eps)
+        ctx.save_for_backward(features, occupancy, coordinates, weight, gamma, rows, winner, moments)
+        ctx.geom, ctx.eps = geom, eps
+        ctx.mark_non_differentiable(winner, bn)
+        return rows, winner, bn
+
+    @staticmethod
+    def backward(ctx, d_rows, _d_winner, _d_bn):
+        features, occupancy, coordinates, weight, gamma, rows, winner, moments = ctx.saved_tensors
+        dW, d_gamma, d_beta = pillar_train_backward(features, occupancy, coordinates, ctx.geom, weight, gamma, ctx.eps, rows, winner,
+                                                    d_rows.contiguous(), moments)
+        return None, None, None, None, None, dW, d_gamma, d_beta
+
+
+class PillarFeatureNet(nn.Module):
+    """item (features, occupancy, coordinates, batch_size of the Preprocessor) -> BEV map (B, CHANNELS, H, W) f32."""
+
+    native = True  # False: forward_torch for every call (A/B measurements, the cross-check of the tests)
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.opt = pillar_config(cfg)
+        self.channels = int(self.opt["CHANNELS"])
+        self.geom, self.map_shape = pillar_geometry(cfg)
+        self.linear = nn.Linear(int(cfg.C_IN) + 6, self.channels, bias=False)
+        self.norm = nn.BatchNorm1d(self.channels, eps=1e-3, momentum=0.01)
+        self.last_winner = None  # (M, CHANNELS) i32 of the last native training forward (diagnostics, tests)
+
+    # ---- the canvas
+    def canvas(self, rows, coordinates, batch_size):
+        H, W = self.map_shape
+        if rows.is_cuda:
+            # the canvas is one cell tall: the z index is written as 0 whatever a hand-built item holds (one small elementwise launch;
+            # no host read -- check_coordinates is the loud form), so no row can land outside its (b, y, x) column
+            mask = self.__dict__.get("_z_mask")
+            if mask is None or mask.device != coordinates.device:
+                mask = self.__dict__["_z_mask"] = torch.tensor([1, 0, 1, 1], dtype=torch.int32, device=coordinates.device)
+            flat = coordinates.int() * mask
+            dense = spconv.SparseConvTensor(rows, flat, [1, H, W], batch_size).dense()  # differentiable where rows need it
+            return dense.reshape(int(batch_size), rows.shape[1], H, W)
+        out = rows.new_zeros((int(batch_size), H, W, rows.shape[1]))
+        co = coordinates.long()
+        return out.index_put((co[:, 0], co[:, 2], co[:, 3]), rows).permute(0, 3, 1, 2).contiguous()
+
+    @staticmethod
+    def check_coordinates(coordinates):
+        """Pillars have z index 0 (pillar_geometry refuses every grid that could give another).  One host read: for callers that
+        build `coordinates` themselves; forward() does not stall on it."""
+        if coordinates.numel() and int(coordinates[:, 1].abs().max()) != 0:
+            raise ValueError("PillarFeatureNet: coordinates[:, 1] (the z index) must be 0: a pillar spans the whole z extent")
+
+    def _check(self, item):
+        features, coordinates = item["features"], item["coordinates"]
+        if features.dim() != 3 or features.shape[2] + 6 != self.linear.in_features:
+            raise ValueError(f"PillarFeatureNet: features must be (M, P, {self.linear.in_features - 6}), got {tuple(features.shape)}")
+        if item["occupancy"].shape[0] != features.shape[0] or coordinates.shape != (features.shape[0], 4):
+            raise ValueError("PillarFeatureNet: occupancy (M) and coordinates (M, 4) must match features (M, P, C)")
+
+    # ---- eval-mode BatchNorm folded to scale / shift, cached until a tensor changes (as RPN._folded)
+    def _folded(self):
+        n = self.norm
+        stamp = tuple((t.data_ptr(), t._version) for t in (n.running_mean, n.running_var, n.weight, n.bias))
+        cache = self.__dict__.get("_fold_cache")
+        if cache is None or cache[0] != stamp:
+            with torch.no_grad():
+                scale = torch.rsqrt(n.running_var + n.eps) * n.weight
+                cache = (stamp, (scale.contiguous(), (n.bias - n.running_mean * scale).contiguous()))
+            self.__dict__["_fold_cache"] = cache
+        return cache[1]
+
+    def forward(self, item):
+        self._check(item)
+        features = item["features"]
+        if not (self.native and features.is_cuda and features.dtype == torch.float32 and _native_shape(features, self.channels)
+                and item["occupancy"].dtype == torch.int32 and item["coordinates"].dtype == torch.int32):
+            return self.forward_torch(item)
+        occupancy, coordinates, B = item["occupancy"], item["coordinates"], int(item["batch_size"])
+        if features.shape[0] == 0:
+            return features.new_zeros((B, self.channels) + self.map_shape)
+        if not self.training:
+            if torch.is_grad_enabled():  # (autograd through an eval-mode encoder: the torch statement carries it, as RPN.forward)
+                return self.forward_torch(item)
+            scale, shift = self._folded()
+            rows = pillar_encode(features, occupancy, coordinates, self.geom, self.linear.weight.detach(), scale, shift)
+            return self.canvas(rows, coordinates, B)
+        rows, winner, bn = PillarEncodeFunction.apply(features, occupancy, coordinates, self.geom, float(self.norm.eps), self.linear.weight,
+                                                      self.norm.weight, self.norm.bias)
+        self.last_winner = winner
+        self._update_running(bn[0], bn[1], features.shape[0] * features.shape[1])
+        return self.canvas(rows, coordinates, B)
+
+    def _update_running(self, mean, var, rows):
+        """nn.BatchNorm1d's update from the batch mean and BIASED variance over `rows` rows: unbiased variance, momentum."""
+        n = self.norm
+        if not n.track_running_stats or n.running_mean is None:
+            return
+        with torch.no_grad():
+            n.num_batches_tracked += 1
+            mom = n.momentum if n.momentum is not None else 1.0 / float(n.num_batches_tracked)
+            n.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
+            n.running_var.mul_(1 - mom).add_(var * (rows / max(rows - 1, 1)), alpha=mom)
+
+    def forward_torch(self, item, winner=None):
+        """The op-by-op torch statement of the encoder (any device, any P / C / CHANNELS).  winner (M, CHANNELS) integer: the maximum
+        is READ at these rows instead of searched (-1 = the padded candidate, read at the pillar's last slot, a zero-feature row) --
+        the statement of what PillarEncodeFunction differentiates, for cross-checks that must not depend on near-tied maxima."""
+        self._check(item)
+        dtype = self.linear.weight.dtype  # (fp32; a .double() module states the same in float64)
+        features, occupancy, coordinates, B = item["features"].to(dtype), item["occupancy"], item["coordinates"], int(item["batch_size"])
+        M, P, C = features.shape
+        if M == 0:
+            return features.new_zeros((B, self.channels) + self.map_shape)
+        g = torch.tensor(self.geom, dtype=dtype, device=features.device)
+        real = (torch.arange(P, device=features.device)[None, :] < occupancy[:, None]).unsqueeze(-1)  # (M, P, 1)
+        xyz = features[..., :3]
+        mean = (xyz * real).sum(dim=1, keepdim=True) / occupancy.to(dtype).view(M, 1, 1)
+        centre = (coordinates[:, [3, 2, 1]].to(dtype) * g[:3] + g[3:]).unsqueeze(1)
+        f = torch.cat([features, xyz - mean, xyz - centre], dim=-1) * real
+        y = self.norm(self.linear(f).view(M * P, self.channels)).view(M, P, self.channels)
+        if winner is None:
+            rows = torch.max(F.relu(y), dim=1).values
+        else:
+            at = torch.where(winner < 0, P - 1, winner).long()
+            rows = torch.take_along_dim(F.relu(y), at.unsqueeze(1), dim=1).squeeze(1)
+        return self.canvas(rows, coordinates, B)

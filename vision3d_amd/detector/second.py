@@ -159,14 +159,23 @@ class Second(nn.Module):
 
     def __init__(self, cfg):
         super().__init__()
-        self.vfe = VoxelFeatureExtractor()
-        self.cnn = Middle(cfg)
-        # BEV channels = 64 x (z extent after the last sparse stage): 128 for the KITTI grid, as hard-coded in
-        # the reference (second.py:52); other ranges (e.g. the Waymo-range stress config: 3 z-slices) follow.
-        z = self.cnn.grid_shape[0]
-        for k, st, pd in ((3, 2, 1), (3, 2, 1), (3, 2, 0), (3, 2, 0)):
-            z = (z + 2 * pd - k) // st + 1
-        self.rpn = RPN(C_in=64 * z)
+        from .pillar import PillarFeatureNet, pillar_enabled
+        self.pillar = pillar_enabled(cfg)  # cfg.PILLAR (opt-in): the pillar encoder writes the BEV map itself, no sparse backbone
+        if self.pillar:
+            self.vfe = PillarFeatureNet(cfg)
+            if self.vfe.channels != 128:
+                raise ValueError(f"cfg.PILLAR.CHANNELS = {self.vfe.channels}: Second takes 128 (the native dense RPN plans, inference and "
+                                 "training, are 128 channels wide); PillarFeatureNet alone also runs 64")
+            self.rpn = RPN(C_in=self.vfe.channels)
+        else:
+            self.vfe = VoxelFeatureExtractor()
+            self.cnn = Middle(cfg)
+            # BEV channels = 64 x (z extent after the last sparse stage): 128 for the KITTI grid, as hard-coded in
+            # the reference (second.py:52); other ranges (e.g. the Waymo-range stress config: 3 z-slices) follow.
+            z = self.cnn.grid_shape[0]
+            for k, st, pd in ((3, 2, 1), (3, 2, 1), (3, 2, 0), (3, 2, 0)):
+                z = (z + 2 * pd - k) // st + 1
+            self.rpn = RPN(C_in=64 * z)
         from .center_head import CenterHead, centerhead_enabled
         self.center_head = centerhead_enabled(cfg)  # cfg.CENTERHEAD (opt-in): heat map + box regression in place of the anchor head
         self.head = CenterHead(cfg) if self.center_head else ProposalLayer(cfg)
@@ -177,6 +186,10 @@ class Second(nn.Module):
         # cost 0.25 ms of host time per frame (profiles/r06_b_*: 3 800 -> 2 900 frames/s) -- and looks at the tensors only when it moved.
         self.__dict__["_weights_epoch"] = 0
         self.register_load_state_dict_post_hook(lambda module, incompatible: (module.notify_weights_changed(), None)[1])
+
+    def _refuse_pillar(self, what):
+        from .pillar import refuse_pillar
+        refuse_pillar(self.cfg, what)
 
     def notify_weights_changed(self):
         """Tell the captured-graph runners that parameters / buffers were edited (they check the tensors themselves on their next
@@ -195,27 +208,32 @@ class Second(nn.Module):
         from .. import _lib as L
         if precision not in L.PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(L.PRECISIONS)}")
-        self.precision = self.rpn.precision = precision
+        self.precision = self.rpn.precision = precision  # (cfg.PILLAR: there is no sparse part; the encoder is fp32 FMA throughout)
         for m in self.modules():
             if isinstance(m, spconv.conv._SparseConvBase):
                 m.precision = precision
         return self
 
-    def feature_extract(self, item):
+    def _bev_from_item(self, item):
+        """item -> the BEV map the RPN reads: the pillar encoder's canvas (cfg.PILLAR), or voxel mean -> sparse backbone."""
+        if self.pillar:
+            return self.vfe(item)
         if "voxel_mean" in item:  # fused into the device voxelizer
             features = item["voxel_mean"]
         else:
             features = self.vfe(item["features"], item["occupancy"])
-        features = self.cnn(features, item["coordinates"], item["batch_size"])
-        return self.rpn(features)
+        return self.cnn(features, item["coordinates"], item["batch_size"])
+
+    def feature_extract(self, item):
+        return self.rpn(self._bev_from_item(item))
 
     # ---- the reference's entry points (train.py:63 calls forward(item), inference.py:38 calls inference(item)).  In eval mode
     #      without autograd an item of the device Preprocessor runs the native path: backbone plan fed with the item's voxels
     #      (csrc/second_plan.hip) -> bf16x3 MFMA RPN + heads (csrc/dense_conv.hip) -> device proposal stage (csrc/proposal.hip).
     #      Training (autograd) keeps the module-by-module path.
     def _native_item(self, item):
-        if self.training or torch.is_grad_enabled() or "voxel_mean" not in item:
-            return False
+        if self.pillar or self.training or torch.is_grad_enabled() or "voxel_mean" not in item:
+            return False  # (cfg.PILLAR: pillar kernel -> dense() -> RPN.native_forward -> head.inference, module by module)
         vm, co = item["voxel_mean"], item["coordinates"]
         return vm.is_cuda and co.is_cuda and co.dtype == torch.int32 and vm.dtype == torch.float32 and vm.shape[0] > 0
 
@@ -276,16 +294,14 @@ class Second(nn.Module):
 
     def _train_head_maps_split(self, item):
         from .. import dense_train
-        features = item["voxel_mean"] if "voxel_mean" in item else self.vfe(item["features"], item["occupancy"])
-        bev = self.cnn(features, item["coordinates"], item["batch_size"])
+        bev = self._bev_from_item(item)
         if not dense_train.supported(self.rpn, self.head, bev, "bf16x3"):
             return self._torch_dense_fallback(bev, dense_train.why_unsupported(self.rpn, self.head, bev, "bf16x3"))
         return dense_train.train_head_maps(self.rpn, self.head, bev, self.__dict__.setdefault("_dense_train_plans", {}), "bf16x3")
 
     def _train_head_maps_autocast(self, item):
         from .. import dense_train
-        features = item["voxel_mean"] if "voxel_mean" in item else self.vfe(item["features"], item["occupancy"])
-        bev = self.cnn(features, item["coordinates"], item["batch_size"])
+        bev = self._bev_from_item(item)
         if not bev.is_cuda or bev.dim() != 4 or bev.shape[1] != 128:
             return self._torch_dense_fallback(bev, "BEV map is not a 128-channel CUDA tensor")
         if bev.dtype != torch.bfloat16 or not bev.is_contiguous(memory_format=torch.channels_last):
@@ -306,6 +322,8 @@ class Second(nn.Module):
     def check_train_overflow(self):
         """Capacity check of the last training forward without a stall (runtime.BackbonePlan.check_deferred_overflow): call it
         between backward() and optimizer.step(), and once after the last step of a run."""
+        if self.pillar:  # (no sparse plan, no capacity to overflow)
+            return
         for plan in self.cnn.__dict__.get("_train_plans", {}).values():
             plan.check_deferred_overflow()
 
@@ -361,6 +379,7 @@ class Second(nn.Module):
         """Plans own their arena (hash tables, rulebooks, per-layer outputs): frames in flight at the same time need
         one plan each -- `slot` keys them."""
         from ..runtime import BackbonePlan, PlanCache
+        self._refuse_pillar("Second.backbone_plan (the sparse backbone's plan, behind every raw-point entry point)")
         plans = self.__dict__.setdefault("_plans", PlanCache())
         dev = next(self.parameters()).device
         key = (str(dev), int(max_batch), int(max_points)) + ((int(slot),) if slot else ())
@@ -390,6 +409,7 @@ class Second(nn.Module):
 
     def bev_from_points(self, clouds):
         """clouds: list of (N_b, C) float32 cuda tensors -> BEV map (B, 128, 200, 176); eval mode only."""
+        self._refuse_pillar("Second.bev_from_points")
         offsets = [0]
         for c in clouds:
             offsets.append(offsets[-1] + int(c.shape[0]))
@@ -416,10 +436,12 @@ class Second(nn.Module):
     def head_maps_from_points(self, clouds):
         """Fully native feature path: raw points -> (cls_map, reg_map); the BEV map never leaves the split
         bf16 NHWC format between the sparse backbone and the 8 MFMA convolutions."""
+        self._refuse_pillar("Second.head_maps_from_points")
         return self.head.maps_from_fused(self.fused_head_from_points(clouds))
 
     def fused_head_from_points(self, clouds):
         """raw points -> (B, n_anchor*(1+DOF), H, W) fp32: the [cls | reg] output of the fused 1x1 head."""
+        self._refuse_pillar("Second.fused_head_from_points")
         plan, flat, offsets = self._plan_for(clouds)
 
         def run():
@@ -439,6 +461,7 @@ class Second(nn.Module):
         from .center_head import refuse_centerhead
         from .graph import GraphedSecond
         refuse_centerhead(self.cfg, "Second.graphed_inference")
+        self._refuse_pillar("Second.graphed_inference")
         return GraphedSecond(self, anchors, frame_sizes)
 
     def pipelined_inference(self, anchors, frame_sizes, depth=2, autotune=False):
@@ -448,6 +471,7 @@ class Second(nn.Module):
         from .center_head import refuse_centerhead
         from .graph import PipelinedSecond
         refuse_centerhead(self.cfg, "Second.pipelined_inference")
+        self._refuse_pillar("Second.pipelined_inference")
         return PipelinedSecond(self, anchors, frame_sizes, depth, autotune)
 
     def inference_points(self, clouds, anchors, dense="mfma", proposals="native"):
@@ -455,6 +479,7 @@ class Second(nn.Module):
         the hand-written bf16x3 MFMA convolution (csrc/dense_conv.hip) -- there is no torch / MIOpen inference path.
         proposals = "native": top-k / decode / NMS / score cut in csrc/proposal.hip; "torch": the op-by-op
         statement of proposal.py:61-80 (ties in the top-k are then torch.topk's)."""
+        self._refuse_pillar("Second.inference_points")
         if dense != "mfma":
             raise ValueError("inference_points: the torch (MIOpen) dense path was removed; dense must be 'mfma'")
         if proposals == "native":
