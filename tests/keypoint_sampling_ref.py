@@ -7,6 +7,8 @@ Per frame: points (N, C >= 3) f32, K, S, proposals (P, 7) or None, radius ->
 which the device's atan2f and numpy's agree on every sector (synth.make_keypoint_case keeps it above 1e-3)."""
 import numpy as np
 
+from fps_ref import fps_f32
+
 F = np.float32
 
 
@@ -58,15 +60,7 @@ def quotas(n_k, K):
 
 def fps_chain(xyz, picks):
     """xyz (n, 3) f32 in original-index order -> `picks` rows: first = row 0, then the largest running distance, lowest row on ties."""
-    out = [0]
-    td = np.full(len(xyz), F(1e10), F)
-    for _ in range(picks - 1):
-        with np.errstate(over="ignore"):
-            d = xyz - xyz[out[-1]]
-            d = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
-        td = np.minimum(td, d)
-        out.append(int(np.argmax(td)))
-    return out
+    return [int(r) for r in fps_f32(np.asarray(xyz, F), picks)]  # stated once, in tests/fps_ref.py
 
 
 def sector_point_sample_frame(points, K, S, proposals=None, radius=1.6):

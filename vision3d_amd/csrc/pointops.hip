@@ -268,6 +268,18 @@ extern "C" size_t v3d_fps_workspace(int B, int N) {
   return 256;  // everything lives in registers/LDS; kept for ABI stability
 }
 
+// Which N reaches which kernel, and the runs of tests/test_gpu_fps_edges.py (cases: tests/fps_cases.py) that pin it -- every run against
+// the float32 restatement bit for bit and against float64 as "a farthest point at every step" (tests/fps_ref.py):
+//        1 ..  1 024   fps_kernel<1>         cube-n{1,2,64,65,1023,1024}, {line,road,comb,clusters}-n1024, tie_{lanes,waves}-n1024
+//    1 025 ..  4 096   fps_slab_kernel<16>   *-n1025, *-n4096, doubled-n1300-k1300
+//    4 097 ..  8 192   fps_slab_kernel<32>   *-n4097, *-n8192
+//    8 193 .. 16 384   fps_slab_kernel<64>   *-n8193, *-n16384 (and the 16 384 -> 2 048 sweeps of tests/test_gpu_pointops.py)
+//   16 385 .. 24 576   fps_kernel<24>        *-n16385, *-n24576
+//   24 577 .. 32 768   fps_kernel<32>        *-n24577, *-n32768     (spills 60 B per lane to scratch)
+//   32 769 .. 65 536   fps_kernel<64>        *-n32769, *-n65535, *-n65536     (spills 556 B per lane); above: V3D_EUNSUPPORTED
+// Ties go to the lowest original index at every level -- a thread's slots, a wave's lanes, the waves, the slabs, inside a bin (whose
+// order differs from run to run): tie_{slots,lanes,waves}-n*, tie_{slabs,bin}-n*, comb-n*.  The slab bounds: {line,comb,clusters}-n*,
+// whose picks change when the bounds are 8 bins too narrow (tests/test_host_fps_ref.py shows it on a model of the algorithm).
 extern "C" int v3d_furthest_point_sample(const float* xyz, int B, int N, int K, int32_t* idx, void* workspace,
                                          size_t workspace_bytes, v3d_stream_t stream) {
   (void)workspace;
@@ -291,7 +303,7 @@ extern "C" int v3d_furthest_point_sample(const float* xyz, int B, int N, int K, 
     V3D_CHECK_LAUNCH();                                                                              \
     return V3D_OK;                                                                                   \
   }
-  V3D_FPS(1) V3D_FPS(2) V3D_FPS(4) V3D_FPS(8) V3D_FPS(16) V3D_FPS(24) V3D_FPS(32) V3D_FPS(64)
+  V3D_FPS(1) V3D_FPS(24) V3D_FPS(32) V3D_FPS(64)  // (2 .. 16 points per thread are the slab kernel's sizes)
 #undef V3D_FPS
   return V3D_EUNSUPPORTED;  // N > 65536 per frame
 }
