@@ -133,7 +133,10 @@ int v3d_sparse_bn_relu_bwd(const float* x, const float* dy, int n, int C, const 
  * the HOST: best IoU < lo -> label 0, [lo, hi) -> ignored, >= hi -> +1; allow_low_quality: every anchor attaining
  * some ground truth's best IoU (ties included) is positive.  Outputs (n_cls, A): G_cls i8 in {0,1}, M_cls u8
  * (0 = ignored), G_reg (.,7) f32 VoxelNet encoding at positives / 0, M_reg u8 = positives; matches (nullable) i64 =
- * index of the best ground truth (first maximal).  box_ignore is not an input: the reference never applies it. */
+ * index of the best ground truth (first maximal in input order; 0 for a class without ground truth).  box_ignore is not an
+ * input: the reference never applies it.  Any n_gt >= 0 is accepted: a class's ground truths are staged 128 at a time and a
+ * larger class is walked in chunks, with the same result as one pass.  gt_class outside [0, n_cls) belongs to no class.
+ * n_cls <= 16 (else V3D_EINVAL).  The workspace may be reused from call to call: nothing in it is read before it is written. */
 size_t v3d_assign_targets_workspace(int n_gt, int n_cls, int anchors_per_class);
 int v3d_assign_targets(const float* gt_boxes, const int64_t* gt_class, int n_gt, const float* anchors, int n_cls,
                        int anchors_per_class, const float* iou_thresh_host, int allow_low_quality, int8_t* G_cls, uint8_t* M_cls,

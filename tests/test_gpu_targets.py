@@ -49,6 +49,23 @@ def test_fused_matches_torch_statement(n_cls, low_quality):
         np.testing.assert_allclose(fused["G_reg"].cpu().numpy(), ref["G_reg"].cpu().numpy(), rtol=1e-5, atol=1e-6)
 
 
+def test_129_ground_truths_take_the_fused_path(monkeypatch):
+    """more ground truths than the kernels stage at once (128): walked in chunks, no longer routed to the torch statement"""
+    from vision3d_amd.core import ProposalTargetAssigner
+    assigner = ProposalTargetAssigner(second_car_cfg().clone())
+    gt = np.concatenate([synth.make_gt_boxes(seed) for seed in range(8)])[:129]
+    assert len(gt) == 129
+    item = dict(boxes=torch.from_numpy(gt), class_idx=torch.zeros(129, dtype=torch.long), box_ignore=torch.zeros(129, dtype=torch.bool))
+    ref = assigner.forward_torch(dict(item))
+    monkeypatch.setattr(assigner, "forward_torch", lambda item: pytest.fail("the torch statement ran: not the fused path"))
+    fused = assigner(dict(item))
+    assert int(fused["M_reg"].sum()) > 0
+    for k in ("G_cls", "M_cls", "M_reg"):
+        assert fused[k].dtype == ref[k].dtype and fused[k].shape == ref[k].shape, k
+        assert torch.equal(fused[k], ref[k]), k
+    np.testing.assert_allclose(fused["G_reg"].cpu().numpy(), ref["G_reg"].cpu().numpy(), rtol=1e-5, atol=1e-6)
+
+
 def test_no_ground_truth_and_absent_class():
     from vision3d_amd.core import ProposalTargetAssigner
     cfg = three_class_cfg()

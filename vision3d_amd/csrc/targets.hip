@@ -20,7 +20,7 @@
 #include "rotated_iou.h"
 #include "v3d_common.h"
 
-#define TA_MAX_GT 128  // ground truths of ONE class staged per workgroup
+#define TA_MAX_GT 128  // ground truths of ONE class staged per workgroup at a time; a larger class is walked in chunks
 
 struct TaParams {
   int n_gt, n_cls, A;
@@ -33,13 +33,17 @@ __device__ __forceinline__ v3d::BoxPrep ta_prep7(const float* b) {  // (x, y, z,
   return v3d::prep_box(bev);
 }
 
-// stage the ground truths of class c (in input order) into LDS; returns their count (block-uniform)
+// stage the next chunk (<= TA_MAX_GT, in input order) of the ground truths of class c into LDS; returns its size (block-uniform).
+// `next` is where thread 0's scan of gt_class resumes (only thread 0's copy is used); a chunk of TA_MAX_GT means "call again".
+// Every thread of the workgroup must call it: the first barrier waits for the readers of the previous chunk.
 __device__ __forceinline__ int ta_stage(const float* gt, const long long* gt_class, int n_gt, int c, v3d::BoxPrep* sp,
-                                        int* sidx, int* s_count) {
+                                        int* sidx, int* s_count, int& next) {
+  __syncthreads();
   if (threadIdx.x == 0) {
-    int m = 0;
-    for (int g = 0; g < n_gt && m < TA_MAX_GT; g++)
+    int m = 0, g = next;
+    for (; g < n_gt && m < TA_MAX_GT; g++)
       if ((int)gt_class[g] == c) sidx[m++] = g;
+    next = g;
     *s_count = m;
   }
   __syncthreads();
@@ -59,24 +63,32 @@ __global__ __launch_bounds__(V3D_BLOCK) void ta_match_kernel(const float* __rest
   __shared__ v3d::P2 clip_pts[V3D_BLOCK / V3D_WAVE][24 * 64];  // the clipper's work arrays: LDS, not scratch (rotated_iou.h)
   __shared__ float clip_dist[V3D_BLOCK / V3D_WAVE][24 * 64];
   const int c = blockIdx.y;
-  const int m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count);
   const int a = blockIdx.x * V3D_BLOCK + threadIdx.x;
-  if (a >= p.A) return;
+  const bool live = a < p.A;  // the other threads only stage
   v3d::P2* pts = clip_pts[threadIdx.x >> 6] + (threadIdx.x & 63);
   float* dist = clip_dist[threadIdx.x >> 6] + (threadIdx.x & 63);
-  const v3d::BoxPrep ba = ta_prep7(anchors + 7 * ((size_t)c * p.A + a));
+  int next = 0;
+  int m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count, next);
+  v3d::BoxPrep ba = {};
+  if (live) ba = ta_prep7(anchors + 7 * ((size_t)c * p.A + a));
   float best = -1.f;
-  int arg = 0;
-  for (int i = 0; i < m; i++) {
-    const float q = v3d::iou_prepped_lds(sp[i], ba, pts, dist);  // box_iou_rotated(gt, anchors)[i][a]
-    if (q > best) {  // strict: the FIRST maximal ground truth, as torch.max(dim=0) returns
-      best = q;
-      arg = i;
-    }
-    if (q > 0.f) atomicMax(&gt_max[sidx[i]], __float_as_uint(q));  // zero needs no write: the buffer starts at +0.0
+  int arg = 0;  // INPUT index of the best ground truth; 0 when the class has none
+  for (;;) {  // the class's ground truths in chunks of TA_MAX_GT, in input order; best / arg carried across
+    if (live)
+      for (int i = 0; i < m; i++) {
+        const float q = v3d::iou_prepped_lds(sp[i], ba, pts, dist);  // box_iou_rotated(gt, anchors)[i][a]
+        if (q > best) {  // strict: the FIRST maximal ground truth, as torch.max(dim=0) returns
+          best = q;
+          arg = sidx[i];
+        }
+        if (q > 0.f) atomicMax(&gt_max[sidx[i]], __float_as_uint(q));  // zero needs no write: the buffer starts at +0.0
+      }
+    if (m < TA_MAX_GT) break;  // block-uniform
+    m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count, next);
   }
-  best_iou[(size_t)c * p.A + a] = best;
-  best_gt[(size_t)c * p.A + a] = m ? sidx[arg] : 0;
+  if (!live) return;
+  best_iou[(size_t)c * p.A + a] = best;  // -1: no ground truth of this class
+  best_gt[(size_t)c * p.A + a] = arg;
 }
 
 __device__ __forceinline__ float ta_remainder(float x, float m) {  // torch.remainder: result takes the sign of m
@@ -97,22 +109,32 @@ __global__ __launch_bounds__(V3D_BLOCK) void ta_label_kernel(const float* __rest
   __shared__ v3d::P2 clip_pts[V3D_BLOCK / V3D_WAVE][24 * 64];  // the clipper's work arrays: LDS, not scratch (rotated_iou.h)
   __shared__ float clip_dist[V3D_BLOCK / V3D_WAVE][24 * 64];
   const int c = blockIdx.y;
-  const int m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count);
   const int a = blockIdx.x * V3D_BLOCK + threadIdx.x;
-  if (a >= p.A) return;
+  const bool live = a < p.A;  // the other threads only stage
   v3d::P2* pts = clip_pts[threadIdx.x >> 6] + (threadIdx.x & 63);
   float* dist = clip_dist[threadIdx.x >> 6] + (threadIdx.x & 63);
-  const size_t ia = (size_t)c * p.A + a;
+  const size_t ia = (size_t)c * p.A + (live ? a : 0);
   const float* an = anchors + 7 * ia;
-  int label = 0;  // no ground truth of this class: the lowest band (matcher.py:69-79)
-  if (m) {
-    const float best = best_iou[ia];
-    label = best < p.lo[c] ? 0 : (best < p.hi[c] ? -1 : 1);
-    if (p.allow_low_quality) {
-      const v3d::BoxPrep ba = ta_prep7(an);
-      for (int i = 0; i < m; i++)
-        if (__float_as_uint(v3d::iou_prepped_lds(sp[i], ba, pts, dist)) == gt_max[sidx[i]]) label = 1;  // ties included (matcher.py:98-130)
+  int next = 0;
+  int m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count, next);
+  const int any = m;  // the class has ground truth
+  bool hit = false;   // attains some ground truth's maximum
+  if (p.allow_low_quality) {
+    v3d::BoxPrep ba = {};
+    if (live) ba = ta_prep7(an);
+    for (;;) {  // the same chunks as ta_match_kernel
+      if (live)
+        for (int i = 0; i < m; i++)
+          if (__float_as_uint(v3d::iou_prepped_lds(sp[i], ba, pts, dist)) == gt_max[sidx[i]]) hit = true;  // ties included (matcher.py:98-130)
+      if (m < TA_MAX_GT) break;  // block-uniform
+      m = ta_stage(gt, gt_class, p.n_gt, c, sp, sidx, &s_count, next);
     }
+  }
+  if (!live) return;
+  int label = 0;  // no ground truth of this class: the lowest band (matcher.py:69-79)
+  if (any) {
+    const float best = best_iou[ia];
+    label = hit ? 1 : best < p.lo[c] ? 0 : (best < p.hi[c] ? -1 : 1);
   }
   const int g = best_gt[ia];
   if (matches) matches[ia] = g;
