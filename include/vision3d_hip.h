@@ -115,7 +115,8 @@ int v3d_refine_nms(const float* deltas, const float* proposals, const float* con
  * Replaces nn.BatchNorm1d(eps, momentum) + nn.ReLU on SparseConvTensor.features (detector/sparse_cnn.py:15-30) in
  * training: forward = chunk statistics (two-pass per chunk) + Chan merge in double + fused normalise/affine/ReLU;
  * backward = chunk sums + merge + fused input gradient.  save_mean / save_invstd (C) feed the backward; var_unbiased (C)
- * is what the running_var update uses.  Deterministic. */
+ * is what the running_var update uses.  Deterministic.  n = 1 is served (torch refuses it): the variance is 0, so
+ * y = relu(beta), var_unbiased = 0 (no n - 1 division), and the backward gives dx = 0. */
 size_t v3d_sparse_bn_workspace(int n, int C);
 int v3d_sparse_bn_relu_fwd(const float* x, int n, int C, const float* gamma, const float* beta, float eps, int relu, float* y,
                            float* save_mean, float* save_invstd, float* var_unbiased, float* running_mean /*nullable pair:*/,
@@ -920,7 +921,9 @@ int v3d_dense_train_bn_finalize(const float* stats, int tiles, long long count, 
 int v3d_dense_train_bn_relu_apply(const void* x, long long M, const float* mean, const float* invstd, const float* gamma,
                                   const float* beta, int relu, void* y, v3d_stream_t stream);
 size_t v3d_dense_train_bn_bwd_workspace(void);
-/* x = the layer's raw convolution output, dy = gradient w.r.t. the post-ReLU output -> dx (may alias dy), dgamma, dbeta */
+/* x = the layer's raw convolution output, dy = gradient w.r.t. the post-ReLU output -> dx (may alias dy), dgamma, dbeta.
+ * The ReLU mask is the forward's: the fp32 expression v3d_dense_train_bn_relu_apply stores, recomputed from x -- it equals
+ * (y > 0) of that call's output on every element. */
 int v3d_dense_train_bn_relu_bwd(const void* x, const void* dy, long long M, const float* mean, const float* invstd,
                                 const float* gamma, const float* beta, int relu, void* dx, float* dgamma, float* dbeta,
                                 void* workspace, size_t workspace_bytes, v3d_stream_t stream);

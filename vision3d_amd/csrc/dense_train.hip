@@ -708,6 +708,14 @@ extern "C" int v3d_dense_train_bn_finalize(const float* partial, int tiles, long
   return V3D_OK;
 }
 
+// The folded affine of a channel: y = relu(fmaf(x, sc, sh)).  The forward stores THIS expression, and both backward kernels decide
+// the ReLU mask with it (not with fmaf(x_hat, gamma, beta), which rounds differently where y is within an ulp of 0: the gradient
+// would pass where the stored output is 0, or stop where it is positive -- tests/test_gpu_bn_edges.py, the tie kind).
+__device__ __forceinline__ void dt_bn_fold(float mean, float invstd, float gamma, float beta, float& sc, float& sh) {
+  sc = invstd * gamma;
+  sh = beta - mean * sc;
+}
+
 // y = relu((x - mean) * invstd * gamma + beta), bf16 NHWC -> bf16 NHWC.  thread = 8 channels of one pixel (16-byte load / store).
 __global__ __launch_bounds__(256) void dt_bn_relu_apply_kernel(const dt_bf16* __restrict__ x, const dt_bf16* __restrict__ x_lo, long long M,
                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -718,8 +726,7 @@ __global__ __launch_bounds__(256) void dt_bn_relu_apply_kernel(const dt_bf16* __
 #pragma unroll
   for (int e = 0; e < 8; e++) {
     const int c = c8 * 8 + e;
-    sc[e] = invstd[c] * gamma[c];
-    sh[e] = beta[c] - mean[c] * sc[e];
+    dt_bn_fold(mean[c], invstd[c], gamma[c], beta[c], sc[e], sh[e]);
   }
   for (long long m = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); m < M; m += (long long)gridDim.x * 16) {
     float v[8];
@@ -776,11 +783,12 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_reduce_kernel(const dt_bf16* __
                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                int relu, float* __restrict__ partial /*[blocks][2][128]*/) {
   const int c8 = threadIdx.x & 15, rg = threadIdx.x >> 4;
-  float mu[8], is[8], ga[8], be[8], s1[8], s2[8];
+  float mu[8], is[8], sc[8], sh[8], s1[8], s2[8];
 #pragma unroll
   for (int e = 0; e < 8; e++) {
     const int c = c8 * 8 + e;
-    mu[e] = mean[c]; is[e] = invstd[c]; ga[e] = gamma[c]; be[e] = beta[c];
+    mu[e] = mean[c]; is[e] = invstd[c];
+    dt_bn_fold(mu[e], is[e], gamma[c], beta[c], sc[e], sh[e]);
     s1[e] = s2[e] = 0.f;
   }
   for (long long m = (long long)blockIdx.x * 16 + rg; m < M; m += (long long)gridDim.x * 16) {
@@ -790,7 +798,7 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_reduce_kernel(const dt_bf16* __
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       const float xh = (xv[e] - mu[e]) * is[e];
-      const float g = (!relu || fmaf(xh, ga[e], be[e]) > 0.f) ? gv[e] : 0.f;
+      const float g = (!relu || fmaf(xv[e], sc[e], sh[e]) > 0.f) ? gv[e] : 0.f;  // the forward's y > 0
       s1[e] += g;
       s2[e] = fmaf(g, xh, s2[e]);
     }
@@ -816,12 +824,13 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_apply_kernel(const dt_bf16* __r
                                                               const float* __restrict__ dbeta, const float* __restrict__ dgamma, int relu,
                                                               dt_bf16* dx, dt_bf16* dx_lo) {
   const int c8 = threadIdx.x & 15;
-  float mu[8], is[8], ga[8], be[8], k0[8], k1[8];
+  float mu[8], is[8], ga[8], sc[8], sh[8], k0[8], k1[8];
   const float inv_m = 1.f / (float)M;
 #pragma unroll
   for (int e = 0; e < 8; e++) {
     const int c = c8 * 8 + e;
-    mu[e] = mean[c]; is[e] = invstd[c]; ga[e] = gamma[c]; be[e] = beta[c];
+    mu[e] = mean[c]; is[e] = invstd[c]; ga[e] = gamma[c];
+    dt_bn_fold(mu[e], is[e], ga[e], beta[c], sc[e], sh[e]);
     k0[e] = dbeta[c] * inv_m;
     k1[e] = dgamma[c] * inv_m;
   }
@@ -832,7 +841,7 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_apply_kernel(const dt_bf16* __r
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       const float xh = (xv[e] - mu[e]) * is[e];
-      const float g = (!relu || fmaf(xh, ga[e], be[e]) > 0.f) ? gv[e] : 0.f;
+      const float g = (!relu || fmaf(xv[e], sc[e], sh[e]) > 0.f) ? gv[e] : 0.f;  // the forward's y > 0
       o[e] = ga[e] * is[e] * (g - k0[e] - xh * k1[e]);
     }
     dt_store8(dx, dx_lo, m * DT_C + c8 * 8, o);
@@ -842,7 +851,8 @@ __global__ __launch_bounds__(256) void dt_bn_bwd_apply_kernel(const dt_bf16* __r
 extern "C" size_t v3d_dense_train_bn_bwd_workspace(void) { return (size_t)DT_RED_BLOCKS * 2 * DT_C * sizeof(float); }
 
 // x: the layer's raw convolution output (bf16 NHWC), dy: gradient w.r.t. the post-ReLU output -> dx (gradient w.r.t. x, bf16 NHWC;
-// may alias dy), dgamma, dbeta (fp32).
+// may alias dy), dgamma, dbeta (fp32).  The ReLU mask is the forward's: fmaf(x, sc, sh) > 0 with dt_bn_fold's sc / sh, the value
+// v3d_dense_train_bn_relu_apply rounded and stored -- so it equals (y > 0) of that output on every element.
 // (x_lo / dy_lo / dx_lo: the lo planes of split storage, all three or none)
 static int dt_bn_relu_bwd(const void* x, const void* x_lo, const void* dy, const void* dy_lo, long long M, const float* mean,
                           const float* invstd, const float* gamma, const float* beta, int relu, void* dx, void* dx_lo, float* dgamma,

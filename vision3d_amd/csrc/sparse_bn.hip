@@ -20,6 +20,8 @@ __host__ __device__ static inline int sbn_chunks(int n) {
   int g = (n + SBN_MIN_ROWS - 1) / SBN_MIN_ROWS;
   return g < 1 ? 1 : (g > SBN_MAX_CHUNKS ? SBN_MAX_CHUNKS : g);
 }
+// Above 131 072 rows G stays 512 and ceil(n / G) rows per chunk leave trailing chunks EMPTY (cnt = 0: count 0, mean 0, M2 0);
+// pinned by tests/test_gpu_bn_edges.py, the cap cases n = 131 073 and 140 000.
 
 // The row count is either a host value (n_dev == nullptr) or lives in device memory (the plan's training path: no host
 // read anywhere).  Every kernel derives the SAME chunking from it -- G = sbn_chunks(n), rows_per_chunk = ceil(n / G) -- so
