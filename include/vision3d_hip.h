@@ -333,6 +333,9 @@ int v3d_sparse_conv_fwd_packed(const float* in, const void* weight_image, const 
                                int32_t* range_flag, const void* in_split, void* out_split, v3d_stream_t stream);
 int v3d_sparse_rows_split(const float* rows, const int32_t* n_rows, int cap, int C, int prec, const float* act_entry,
                           void* out_split, v3d_stream_t stream);
+/* 1 where the MFMA kernels (v3d_sparse_conv_fwd_packed, and algo 0 / 3 of v3d_sparse_conv_fwd) exist for Cin -> Cout, 0 where only
+ * the scalar kernel (algo 1) runs the layer.  The data gradient asks it for the SWAPPED pair (Cout -> Cin) before it picks a kernel. */
+int v3d_sparse_conv_packed_supported(int Cin, int Cout);
 /* ---- T3 over SPATIALLY ORDERED rows (csrc/brick.hip; same interface the reference reaches through spconv.SubMConv3d,
  * detector/sparse_cnn.py:15-30).  When the rows of a stage are numbered in a spatial (brick / Morton) order, the 27 x 256
  * neighbours of 256 consecutive rows are ~1.2-1.7 x 256 distinct rows: v3d_sparse_brick_plan derives, once per submanifold

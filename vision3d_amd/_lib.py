@@ -58,6 +58,7 @@ _SIGNATURES = {
     "v3d_sparse_conv_pack_weights": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "v3d_sparse_conv_fwd_packed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_sparse_rows_split": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "v3d_sparse_conv_packed_supported": (_i, [_i, _i]),
     "v3d_sparse_brick_table_bytes": (_sz, [_i, _i, _vp, _vp, _vp, _vp]),
     "v3d_sparse_brick_plan": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "v3d_sparse_conv_fwd_brick": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1560,6 +1560,10 @@ bool v3d_i_sparse_conv_packed_supported(int Cin, int Cout) {
   return false;
 }
 
+// the same table for callers outside the library: launch_wave (algo 0 / 3 of v3d_sparse_conv_fwd) is instantiated for exactly these
+// pairs too, so "1" means both MFMA kernels exist and "0" means only the scalar kernel (algo 1) can run the layer
+extern "C" int v3d_sparse_conv_packed_supported(int Cin, int Cout) { return v3d_i_sparse_conv_packed_supported(Cin, Cout) ? 1 : 0; }
+
 int v3d_i_sparse_conv_fwd_packed(const float* in, const void* weight_image, const int32_t* nbr, const int32_t* n_out,
                                  int cap_out, int K, int Cin, int Cout, const float* scale, const float* shift, int relu,
                                  float* out, int rows_hint, hipStream_t st, const V3dDensifyOut* densify, int ring_tiles_min,

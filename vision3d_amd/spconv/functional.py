@@ -4,8 +4,12 @@ forward   out[o] = sum_k x[nbr[k][o]] @ W[k]                                  (c
 backward  dX[i]  = sum_k dY[nbrT[k][i]] @ W[k]^T   -- the SAME gather kernel on the transposed rulebook:
                      submanifold: nbrT[k] = nbr[K-1-k]  (o = i + off_k  <=>  i = o + off_{K-1-k})
                      strided:     nbrT built by v3d_rulebook_transpose
+                     kernel: the MFMA kernels where the library has them for the SWAPPED pair Cout -> Cin, else the scalar one
+                     (data_grad_algo)
           dW[k]  = sum_{pairs} x[i]^T dY[o]         -- exact-fp32 MFMA reduction, deterministic
 """
+import functools
+
 import torch
 
 from .. import _lib as L
@@ -37,6 +41,14 @@ def transpose_rulebook(rb, n_in, device):
     return Rulebook(nbr_t, cap_in, n_in, n_dev, None, None)
 
 
+@functools.lru_cache(maxsize=None)
+def data_grad_algo(cin, cout):
+    """Kernel route of the data gradient of a Cin -> Cout layer: the transposed layer is Cout -> Cin.  0 (packed bf16x3 kernel from
+    Cout >= 16 on, fp32 wave kernel below) where the library has MFMA kernels for that swapped pair -- asked of the table the C side
+    dispatches on --, 1 (the scalar kernel, any channel counts) where it has none: a layer whose forward runs has a backward that runs."""
+    return 0 if L.lib().v3d_sparse_conv_packed_supported(cout, cin) else 1
+
+
 class SparseConvFunction(torch.autograd.Function):
 
     @staticmethod
@@ -66,8 +78,7 @@ class SparseConvFunction(torch.autograd.Function):
             else:
                 rb_t = transpose_rulebook(rb, n_in, features.device)
                 w_t = w.transpose(1, 2).contiguous()
-            algo = 0 if cin % 16 == 0 else 1  # the transposed layer has Cout' = Cin: MFMA kernels need a multiple of 16
-            grad_f = sparse_conv_forward(g, w_t, rb_t, None, None, False, algo)
+            grad_f = sparse_conv_forward(g, w_t, rb_t, None, None, False, data_grad_algo(cin, cout))
         return grad_f, grad_w, None, None, None
 
 
