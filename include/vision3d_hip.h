@@ -977,6 +977,11 @@ int v3d_dense_train_forward_split(const void* bev_hi, const void* bev_lo, int B,
 int v3d_dense_train_backward_split(const void* bev_hi, const void* bev_lo, const float* dmaps, int B, int H, int W,
                                    const v3d_dense_train_layer* layers, int n_layers, const float* head_weight, int O, void* arena,
                                    float* dhead_weight, float* dhead_bias, void* dbev_hi, void* dbev_lo, v3d_stream_t stream);
+/* The split step's weight gradient on its own: dw (128, 128, k, k) fp32 = x_hi (*) dy_hi + x_hi (*) dy_lo + x_lo (*) dy_hi (the exact
+ * product of the two split tensors minus its lo * lo term), three passes of the kernel of v3d_dense_train_wgrad and ONE fixed-order
+ * reduction over their slab partials.  workspace: 3 * v3d_dense_train_wgrad_workspace(ksize) bytes, V3D_EWORKSPACE below that. */
+int v3d_dense_train_wgrad_split(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, int B, int H, int W, int ksize,
+                                float* dw, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 
 /* ---- KITTI 2-D bbox, BEV and 3-D average precision and average orientation similarity (AOS) (vision3d_amd/evaluation/kitti.py;
  * the protocol is written out in its docstring).  The upstream project has no evaluator.  All frames form one ragged batch: rows

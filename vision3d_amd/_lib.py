@@ -166,6 +166,7 @@ _SIGNATURES = {
     "v3d_dense_train_bn_relu_bwd": (_i, [_vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_dense_train_wgrad_workspace": (_sz, [_i]),
     "v3d_dense_train_wgrad": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "v3d_dense_train_wgrad_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "v3d_dense_train_head_workspace": (_sz, [_i]),
     "v3d_dense_train_head_fwd": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "v3d_dense_train_head_bwd": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1118,6 +1118,14 @@ extern "C" int v3d_dense_train_wgrad(const void* x, const void* dy, int B, int H
   return dt_wgrad(dt_t(x), dt_t(dy), B, H, W, ksize, dw, workspace, workspace_bytes, stream);
 }
 
+// the same on split planes (value = hi + lo): dw = x_hi (*) dy_hi + x_hi (*) dy_lo + x_lo (*) dy_hi, the weight gradient of the split step
+// on its own.  workspace: THREE v3d_dense_train_wgrad_workspace (one set of slab partials per term).
+extern "C" int v3d_dense_train_wgrad_split(const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, int B, int H, int W,
+                                           int ksize, float* dw, void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
+  if (!x_hi || !x_lo || !dy_hi || !dy_lo || !dw || !workspace || B < 1 || H < 1 || W < 1 || (ksize != 1 && ksize != 3)) return V3D_EINVAL;
+  return dt_wgrad(dt_t(x_hi, x_lo), dt_t(dy_hi, dy_lo), B, H, W, ksize, dw, workspace, workspace_bytes, stream);
+}
+
 // ------------------------------------------------------------------------------------------------ 1x1 head (<= 64 outputs, bias)
 // maps[b][o][pix] = sum_c feat[m][c] * W[o][c] + bias[o]   (fp32 NCHW out: what ProposalLayer.reshape_* and the loss take)
 #define DT_HEAD_MAX 64

@@ -42,7 +42,13 @@ def why_unsupported(rpn, head, bev, precision="bf16"):
     RPN conv 128 -> 128, 3x3 (pad 1 / ZeroPad2d + pad 0) or 1x1, stride 1, bias-free, fp32 weights, each followed by a
     BatchNorm2d (affine, in TRAINING mode with a numeric momentum: the kernels always normalise with batch statistics and update
     the running statistics by `momentum`; fp32 running statistics on the input's device) + ReLU; head = two biased fp32 1x1
-    convs with 8 * n <= 64 fused outputs."""
+    convs with 8 * n <= 64 fused outputs.
+
+    Maps narrower than four columns are refused as "input is not a ... map" (W >= 4).  The gate came with the first version of
+    this path, whose weight gradient re-laid its operands as padded channel planes; no kernel of today's needs it -- the raw bf16
+    calls (convolution, data gradient, weight gradient, head) equal float64 at W = 1 and 3 (tests/test_gpu_dense_train_edges.py, shapes
+    1x1x1 and 1x3x3), and the C ABI accepts W >= 1.  It stays because no BEV map is that narrow and the whole step, through this
+    module and in both arithmetics, has only ever been run from W = 4 on."""
     if precision == "bf16x3":
         if not (bev.is_cuda and bev.dtype == torch.float32 and bev.dim() == 4 and bev.shape[1] == 128 and bev.shape[3] >= 4):
             return "input is not an fp32 CUDA map with 128 channels"
