@@ -262,6 +262,36 @@ int v3d_voxelize(const float* points, int n_points, int C, const int32_t* frame_
                  int32_t* coords, int32_t* occupancy, float* mean, int32_t* n_voxels, void* workspace,
                  size_t workspace_bytes, v3d_stream_t stream);
 
+/* ---- T1d: dynamic voxelization -- no per-voxel point cap (MVF, arXiv 1910.06528).
+ * Replaces nothing in the reference (which has only the hard form above); the interface is that of mmdet3d's DynamicScatter /
+ * OpenPCDet's DynamicVFE with mean reduction: every in-range point counts, there is no (M, max_pts, C) slot tensor.
+ * Inputs as v3d_voxelize.  Outputs sized for min(n_points, B*max_voxels) rows: coords (.,4) i32 = (b,z,y,x), occupancy (.) i32,
+ * mean (.,C) f32; point_voxel (n_points) i32 [may be NULL]; n_out[2] (device i32) = {n_voxels, status}.
+ * Cells, order: a point belongs to a cell by the statements of the hard voxelizer (IEEE fp32 floorf((q - lo) / vs) and its bounds
+ *   test; a NaN coordinate drops the point); rows are frame-major in first-touch order, max_voxels per frame by the same
+ *   "continue" rule: coords, the row order and n_voxels are bit for bit those of v3d_voxelize on the same input.
+ * occupancy[v] = the TRUE number of points in the cell.  point_voxel[i] = the row of point i, -1 when it is out of bounds or its
+ *   voxel was cut by max_voxels.
+ * Mean, independent of any order by construction (S = 24):
+ *   q_ic      = rint(double(v_ic) * 2^S)                          exact product, round half to even, int64
+ *   mean[v,c] = float(double(sum_i q_ic) / (double(k) * 2^S))     the int64 sum is exact; int64 -> double, the double division and
+ *                                                                 double -> float each round to nearest even
+ *   At most 2^-25 + ulp_fp32(mean) / 2 from the true mean of the fp32 inputs.
+ * Range: |v| < 2^16 in every channel and n_points <= 2^22 (no sum can leave int64); V3D_EUNSUPPORTED before any launch beyond
+ *   that, also when the largest |bounds_host| is >= 2^16.  A kept point whose channel value is not finite or not below 2^16 in
+ *   magnitude contributes nothing to that sum: the voxel's mean in that channel is NaN and bit 0 of status is set.
+ * No host read anywhere. */
+size_t v3d_voxelize_dynamic_workspace(int n_points);
+int v3d_voxelize_dynamic(const float* points, int n_points, int C, const int32_t* frame_offsets_host, int B,
+                         const float* voxel_size_host, const float* bounds_host, int max_voxels, int32_t* coords,
+                         int32_t* occupancy, float* mean, int32_t* point_voxel, int32_t* n_out, void* workspace,
+                         size_t workspace_bytes, v3d_stream_t stream);
+/* How the int64 sums are formed (same results bit for bit; profiles/dynamic_voxelize.txt): 0 = a thread per point adds into its
+ * voxel's accumulators with 64-bit integer atomics, 1 = a voxel's first point walks the voxel's point list, 2 (default) = the
+ * walk for voxels of at most 32 points and the atomics for larger ones.  Sets the choice for the calls that follow in this
+ * process (measurements, tests) and returns the previous one; any other value only reads it. */
+int v3d_voxelize_dynamic_variant(int variant);
+
 /* ---- T3: sparse-convolution rulebooks (spconv ops.get_indice_pairs, reached through
  * spconv.SubMConv3d / SparseConv3d at detector/sparse_cnn.py:15-30,153-175).
  * coords (cap,4) i32 (b,z,y,x); *n (device i32) active rows.  The rulebook is an output-stationary
@@ -504,7 +534,7 @@ typedef struct {
 typedef struct {
   float voxel_size[3];                     /* x, y, z */
   float bounds[6];                         /* x0,y0,z0,x1,y1,z1 */
-  int32_t max_pts, max_voxels;             /* per voxel / per frame */
+  int32_t max_pts, max_voxels;             /* per voxel / per frame; max_pts = 0: dynamic voxelization (v3d_voxelize_dynamic) */
   int32_t point_channels;                  /* C of the input points == Cin of layer 0 */
   int32_t grid_shape[3];                   /* D,H,W of the CNN input grid (sparse_cnn.py:40-45: z + 1) */
   int32_t max_batch, max_points;           /* capacities: frames per forward, total points per forward */
@@ -531,6 +561,8 @@ int v3d_backbone_layer_output(v3d_backbone* plan, int layer, float** features, i
  * and uses them as size hints for the following forwards (capacities are upper bounds).  Not capturable. */
 int v3d_backbone_tune(v3d_backbone* plan);
 int32_t* v3d_backbone_occupancy(v3d_backbone* plan);       /* (cap0) i32, voxel occupancies of the last forward */
+int32_t* v3d_backbone_voxel_status(v3d_backbone* plan);    /* (1) i32 device status word of the last forward's dynamic voxelization
+                                                              (v3d_voxelize_dynamic; stays 0 with max_pts > 0) */
 int32_t* v3d_backbone_overflow_flags(v3d_backbone* plan);  /* (n_layers+1) i32 device flags of the last forward: [l] > 0 = layer l
                                                               hit its active-site capacity (rows were dropped), [n_layers] > 0 = any */
 

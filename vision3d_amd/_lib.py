@@ -50,6 +50,9 @@ _SIGNATURES = {
     "v3d_database_extract": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, C.c_int64, _vp, _vp, _sz, _vp]),
     "v3d_voxelize_workspace": (_sz, [_i]),
     "v3d_voxelize": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_voxelize_dynamic_workspace": (_sz, [_i]),
+    "v3d_voxelize_dynamic": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_voxelize_dynamic_variant": (_i, [_i]),
     "v3d_rulebook_workspace": (_sz, [_i, _i, _i]),
     "v3d_rulebook_subm": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_rulebook_sparse": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -97,6 +100,7 @@ _SIGNATURES = {
     "v3d_backbone_set_layer": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_backbone_layer_output": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_backbone_occupancy": (_vp, [_vp]),
+    "v3d_backbone_voxel_status": (_vp, [_vp]),
     "v3d_backbone_overflow_flags": (_vp, [_vp]),
     "v3d_backbone_forward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_backbone_forward_reuse": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),

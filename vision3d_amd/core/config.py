@@ -109,6 +109,12 @@ def _defaults():
         # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
         # straight into the map the dense RPN reads (no sparse 3-D backbone; the dense plans are 128 wide, so Second takes CHANNELS=128)
         PILLAR=dict(ENABLED=False, CHANNELS=128),
+        # dynamic voxelization (csrc/voxelize.hip "DYNAMIC"; MVF / DynamicScatter, not in the reference), opt-in: a voxel takes EVERY point
+        # inside it instead of the first MAX_OCCUPANCY in input order -- same cells, same row order, `occupancy` = the true counts,
+        # `voxel_mean` an order-independent mean (integer sums of the values scaled by 2^24), a `point_voxel` map and no `features` slot
+        # tensor; values must stay below 2^16 in magnitude, at most 2^22 points per call; refused together with PILLAR (its encoder
+        # reads the point slots)
+        DYNAMIC_VOXELIZATION=dict(ENABLED=False),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
         CNN="SpMiddleFHD",
@@ -155,6 +161,27 @@ WAYMO_RANGE = dict(GRID_BOUNDS=[-75.2, -75.2, -2.0, 75.2, 75.2, 4.0], MAX_VOXELS
 # PointPillars' KITTI grid on the bounds above: 0.4 m pillars over the whole z extent, map stride 1 -- the same 200 x 176 map the RPN
 # sees behind the sparse backbone (0.05 m voxels, stride 8).
 PILLAR_KITTI = dict(VOXEL_SIZE=[0.4, 0.4, 4.0], STRIDES=[1], MAX_OCCUPANCY=32, MAX_VOXELS=12000, PILLAR=dict(ENABLED=True))
+
+
+DYNAMIC_VOXELIZATION_DEFAULTS = dict(ENABLED=False)
+
+
+def dynamic_voxel_config(cfg):
+    """-> the keys of cfg.DYNAMIC_VOXELIZATION over their defaults (a config written before the key existed means "disabled")."""
+    out = dict(DYNAMIC_VOXELIZATION_DEFAULTS)
+    out.update(cfg.get("DYNAMIC_VOXELIZATION") or {})
+    return out
+
+
+def dynamic_voxel_enabled(cfg):
+    return bool(dynamic_voxel_config(cfg)["ENABLED"])
+
+
+def refuse_dynamic_with_pillar(cfg):
+    """The pillar encoder reads the point slots of the hard voxelizer, which the dynamic form does not produce."""
+    if dynamic_voxel_enabled(cfg) and bool((cfg.get("PILLAR") or {}).get("ENABLED", False)):
+        raise ValueError("cfg.DYNAMIC_VOXELIZATION.ENABLED together with cfg.PILLAR.ENABLED: the pillar encoder reads the (M, P, C) point "
+                         "slots, which dynamic voxelization does not produce (a dynamic pillar encoder over point_voxel is a follow-up)")
 
 
 def second_car_cfg():

@@ -7,6 +7,10 @@
 `.cuda()` calls on them become no-ops.  Voxel order/content equals the sequential reference loop
 (first-touch order, first-come slots).  Extra key `voxel_mean` (M, C) carries the fused
 VoxelFeatureExtractor output for callers that want to skip `features`.
+
+cfg.DYNAMIC_VOXELIZATION (opt-in): every point of a voxel counts (csrc/voxelize.hip "DYNAMIC").  The item then has
+  points | coordinates | occupancy (the TRUE counts) | voxel_mean (order-independent) | point_voxel (sum Np,) i32 | batch_size
+and no `features` (the slot tensor does not exist in this mode); same voxels in the same order.
 """
 from collections import defaultdict
 
@@ -14,7 +18,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..spconv.utils import VoxelGenerator, voxelize_batch
+from ..spconv.utils import VoxelGenerator, voxelize_batch, voxelize_dynamic_batch
+from .config import dynamic_voxel_enabled, refuse_dynamic_with_pillar
 
 
 class Preprocessor(nn.Module):
@@ -22,6 +27,8 @@ class Preprocessor(nn.Module):
     def __init__(self, cfg, seed=None):
         super().__init__()
         self.cfg = cfg
+        refuse_dynamic_with_pillar(cfg)
+        self.dynamic = dynamic_voxel_enabled(cfg)  # cfg.DYNAMIC_VOXELIZATION (opt-in): see forward
         self.voxel_generator = self.build_voxel_generator(cfg)
         self._rng = np.random.default_rng(seed)  # reference pads with unseeded np.random (H12)
 
@@ -44,6 +51,19 @@ class Preprocessor(nn.Module):
         m = int(n_vox.item())
         return voxels[:m], coords[:m], occ[:m], mean[:m]
 
+    def generate_batch_voxels_dynamic(self, points):
+        """cfg.DYNAMIC_VOXELIZATION: every point of a voxel counts.  -> (coordinates, occupancy (true counts), mean, point_voxel (sum N_b,)
+        row of every point of the concatenated clouds, -1 = dropped).  The one host read brings the status word with the count."""
+        offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in points])]).astype(np.int64).tolist()
+        flat = torch.cat(points, dim=0) if len(points) > 1 else points[0]
+        coords, occ, mean, point_voxel, n_out = voxelize_dynamic_batch(flat, offsets, self.cfg.VOXEL_SIZE, self.cfg.GRID_BOUNDS,
+                                                                       self.cfg.MAX_VOXELS)
+        m, status = n_out.tolist()
+        if status & 1:
+            raise ValueError("dynamic voxelization: a point inside GRID_BOUNDS holds a channel value that is not finite or not below "
+                             "2^16 in magnitude (the precondition of the exact integer sums; that voxel's mean is NaN)")
+        return coords[:m], occ[:m], mean[:m], point_voxel
+
     def pad_for_batch(self, points):
         """Dense (B, N, C) minibatch; short frames are padded by resampling their own points."""
         n_max = max(p.shape[0] for p in points)
@@ -58,6 +78,11 @@ class Preprocessor(nn.Module):
 
     def forward(self, item):
         points = [self._to_device(p) for p in item["points"]]
+        if self.dynamic:  # no `features`: the slot tensor does not exist in this mode
+            coordinates, occupancy, mean, point_voxel = self.generate_batch_voxels_dynamic(points)
+            item.update(points=self.pad_for_batch(points), coordinates=coordinates, occupancy=occupancy, voxel_mean=mean,
+                        point_voxel=point_voxel, batch_size=len(points))
+            return item
         features, coordinates, occupancy, mean = self.generate_batch_voxels(points)
         item.update(points=self.pad_for_batch(points), features=features, coordinates=coordinates,
                     occupancy=occupancy, voxel_mean=mean, batch_size=len(points))

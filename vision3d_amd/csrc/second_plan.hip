@@ -63,6 +63,10 @@ struct v3d_backbone {
   size_t vox_ws_bytes = 0;
   int32_t* occupancy = nullptr;
   float* mean = nullptr;
+  // dynamic voxelization (cfg.max_pts == 0): the integer sums' scratch (outside the 0xFF region) and the device status word
+  void* vox_dyn = nullptr;
+  size_t vox_dyn_bytes = 0;
+  int32_t* vox_status = nullptr;
   // strided-rulebook scratch
   int* cand_slot[2] = {nullptr, nullptr};  // two: a strided layer's candidate pass may run while the previous layer's table is filled
   int32_t* overflow = nullptr;  // one flag per layer (<= 0 fine, 1 = capacity hit)
@@ -244,6 +248,11 @@ extern "C" int v3d_backbone_create(const v3d_backbone_config* cfg, const v3d_lay
       L.out = ar.take<float>((size_t)p->stages[L.stage_out].cap * L.d.cout);
       L.out_s = (&L != &p->layers.back() && L.d.cout % 8 == 0) ? (void*)ar.take<float>((size_t)p->stages[L.stage_out].cap * L.d.cout) : nullptr;
     }
+    p->vox_status = ar.take<int32_t>(1);  // (last: everything above lies where it lay before the dynamic form existed)
+    if (cfg->max_pts == 0) {
+      p->vox_dyn_bytes = v3d_i_voxelize_dynamic_extra(cfg->max_points);
+      p->vox_dyn = ar.take<char>(p->vox_dyn_bytes);
+    }
   };
   {
     V3dArena probe((void*)256, (size_t)1 << 60);
@@ -258,6 +267,7 @@ extern "C" int v3d_backbone_create(const v3d_backbone_config* cfg, const v3d_lay
   e = hipMemset(p->ff_begin, 0xFF, p->ff_bytes);
   if (e == hipSuccess) e = hipMemset(p->bev_hi, 0, (size_t)((char*)p->bev_lo - (char*)p->bev_hi) * 2);  // the planes are adjacent
   if (e == hipSuccess) e = hipMemset(p->bev_pix_n, 0, sizeof(int32_t));
+  if (e == hipSuccess) e = hipMemset(p->vox_status, 0, sizeof(int32_t));
   if (e == hipSuccess) e = hipMemset(p->frame_max, 0, (p->layers.size() + 1) * sizeof(unsigned));
   if (e == hipSuccess) {
     std::vector<const int32_t*> rows(p->layers.size() + 1);
@@ -461,9 +471,13 @@ extern "C" int v3d_backbone_forward(v3d_backbone* p, const float* points, int n_
   }
   // the voxelizer also fills stage 0's coordinate hash (what rb_hash_build would do in a launch of its own)
   const bool vox_hash = !p->layers.empty() && p->layers[0].d.subm && p->layers[0].builds_rulebook;
-  int rc = v3d_i_voxelize(points, n_points, c.point_channels, frame_offsets_host, B, c.voxel_size, c.bounds, c.max_pts,
-                          c.max_voxels, nullptr, s0.coords, p->occupancy, p->mean, s0.n_dev, p->vox_ws, p->vox_ws_bytes, 0,
-                          vox_hash ? &s0.hash : nullptr, s0.shape, st);
+  int rc = c.max_pts == 0
+               ? v3d_i_voxelize_dynamic(points, n_points, c.point_channels, frame_offsets_host, B, c.voxel_size, c.bounds, c.max_voxels,
+                                        s0.coords, p->occupancy, p->mean, nullptr, s0.n_dev, p->vox_status, p->vox_ws, p->vox_ws_bytes,
+                                        p->vox_dyn, p->vox_dyn_bytes, 0, vox_hash ? &s0.hash : nullptr, s0.shape, -1, st)
+               : v3d_i_voxelize(points, n_points, c.point_channels, frame_offsets_host, B, c.voxel_size, c.bounds, c.max_pts,
+                                c.max_voxels, nullptr, s0.coords, p->occupancy, p->mean, s0.n_dev, p->vox_ws, p->vox_ws_bytes, 0,
+                                vox_hash ? &s0.hash : nullptr, s0.shape, st);
   if (rc) return rc;
   return plan_run_layers(p, B, vox_hash, dense_out, dense_hi, dense_lo, st);
 }
@@ -802,6 +816,8 @@ extern "C" int v3d_backbone_tune_from_voxels(v3d_backbone* p, const int32_t* coo
 extern "C" uint32_t* v3d_backbone_bev_occupancy(v3d_backbone* p) { return p ? p->bev_occ : nullptr; }
 
 extern "C" int32_t* v3d_backbone_occupancy(v3d_backbone* p) { return p ? p->occupancy : nullptr; }
+// status word of the last forward's dynamic voxelization (v3d_voxelize_dynamic): zero at create, never written with max_pts > 0
+extern "C" int32_t* v3d_backbone_voxel_status(v3d_backbone* p) { return p ? p->vox_status : nullptr; }
 // flags[l] = layer l hit its active-site capacity; flags[n_layers] = any of them (one word for the caller's per-frame read)
 extern "C" int32_t* v3d_backbone_overflow_flags(v3d_backbone* p) { return p ? p->overflow : nullptr; }
 extern "C" int v3d_backbone_num_layers(const v3d_backbone* p) { return p ? (int)p->layers.size() : 0; }

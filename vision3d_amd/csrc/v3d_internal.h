@@ -27,6 +27,18 @@ int v3d_i_voxelize(const float* points, int n_points, int C, const int32_t* fram
                    size_t workspace_bytes, int clear_tables, const V3dRbHash* site_hash /*nullable: also insert every
                    emitted voxel into this (pre-cleared) coordinate hash*/,
                    const int32_t* site_shape /*(D, H, W) of the grid that hash is keyed on*/, hipStream_t st);
+// Dynamic voxelization (voxelize.hip): `workspace` is laid out as v3d_i_voxelize's (v3d_voxelize_workspace bytes; clear_tables as
+// there), `extra` (v3d_i_voxelize_dynamic_extra bytes, no initialisation needed) holds the integer sums.  *status is written.
+// variant: V3D_VOXDYN_ATOMIC / _WALK / _HYBRID, or < 0 for the library's current choice (v3d_voxelize_dynamic_variant).
+#define V3D_VOXDYN_ATOMIC 0
+#define V3D_VOXDYN_WALK 1
+#define V3D_VOXDYN_HYBRID 2
+size_t v3d_i_voxelize_dynamic_extra(int n_points);
+int v3d_i_voxelize_dynamic(const float* points, int n_points, int C, const int32_t* frame_offsets_host, int B,
+                           const float* voxel_size_host, const float* bounds_host, int max_voxels, int32_t* coords,
+                           int32_t* occupancy, float* mean, int32_t* point_voxel /*nullable*/, int32_t* n_voxels, int32_t* status,
+                           void* workspace, size_t workspace_bytes, void* extra, size_t extra_bytes, int clear_tables,
+                           const V3dRbHash* site_hash, const int32_t* site_shape, int variant, hipStream_t st);
 int v3d_i_hash_build(const int32_t* coords, const int32_t* n, int cap, const int32_t* shape, V3dRbHash h, int clear,
                      hipStream_t st);
 // The candidate pass of a strided rulebook handed to an EARLIER launch (rulebook.hip RbCandJob): the next strided layer's

@@ -51,6 +51,8 @@ class PV_RCNN(nn.Module):
         from .pillar import refuse_pillar
         refuse_pillar(cfg, "PV_RCNN (its keypoints read the sparse backbone's levels)")
         self.cfg = cfg
+        from ..core.config import dynamic_voxel_enabled
+        self.dynamic_voxels = dynamic_voxel_enabled(cfg)  # cfg.DYNAMIC_VOXELIZATION (opt-in): items without `features`, plans with max_pts = 0
         self.voxel_pool = bool(voxel_roi_pool.voxelpool_config(cfg)["ENABLED"])
         if self.voxel_pool and vector_pool.vectorpool_config(cfg)["ENABLED"]:
             raise ValueError("cfg.VECTORPOOL.ENABLED with cfg.VOXELPOOL.ENABLED: voxel RoI pooling builds no point nets to replace")

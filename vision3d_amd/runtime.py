@@ -104,7 +104,9 @@ class BackbonePlan(object):
         c = L.BackboneConfig()
         c.voxel_size[:] = [float(v) for v in cfg.VOXEL_SIZE]
         c.bounds[:] = [float(v) for v in cfg.GRID_BOUNDS]
-        c.max_pts, c.max_voxels, c.point_channels = cfg.MAX_OCCUPANCY, cfg.MAX_VOXELS, cfg.C_IN
+        from .core.config import dynamic_voxel_enabled
+        self.dynamic_voxels = dynamic_voxel_enabled(cfg)  # cfg.DYNAMIC_VOXELIZATION: max_pts = 0 is the plan's word for it
+        c.max_pts, c.max_voxels, c.point_channels = 0 if self.dynamic_voxels else cfg.MAX_OCCUPANCY, cfg.MAX_VOXELS, cfg.C_IN
         c.grid_shape[:] = self.grid_shape
         c.max_batch, c.max_points, c.n_layers, c.growth = self.max_batch, self.max_points, len(self.layers), float(growth)
         c.conv_algo = int(conv_algo)
@@ -365,6 +367,11 @@ class BackbonePlan(object):
         d, h, w = self.out_shape
         ptr = L.lib().v3d_backbone_bev_occupancy(self._handle)
         return _view(ptr, (int(batch_size) * h, (w + 31) // 32), torch.int32, self.device)
+
+    def voxel_status(self):
+        """(1,) int32 device view of the status word of the last forward's dynamic voxelization (bit 0: a kept point held a
+        non-finite or out-of-range channel value, that voxel's mean in that channel is NaN); stays 0 in the default mode."""
+        return _view(L.lib().v3d_backbone_voxel_status(self._handle), (1,), torch.int32, self.device)
 
     # ---- training: the sparse half of a train step, one native call each way (csrc/second_plan.hip, "Training plan")
     def train_parameters(self):

@@ -32,6 +32,33 @@ def voxelize_batch(points, frame_offsets, voxel_size, bounds, max_pts, max_voxel
     return voxels, coords, occupancy, mean, n_vox
 
 
+def voxelize_dynamic_batch(points, frame_offsets, voxel_size, bounds, max_voxels, want_point_map=True):
+    """Dynamic voxelization of B concatenated frames (csrc/voxelize.hip "DYNAMIC"): every in-range point counts, no slot tensor.
+
+    Inputs as voxelize_batch.  Returns device tensors (coords (M,4) int32 (b,z,y,x), occupancy (M,) int32 = the true counts,
+    mean (M,C) -- order-independent, see include/vision3d_hip.h --, point_voxel (N,) int32 row of every point (-1: dropped) | None,
+    n_out (2,) int32 = {n_voxels, status}) sized by the capacity min(N, B*max_voxels) -- no host sync here.  Same cells, row order
+    and count as voxelize_batch on the same input."""
+    L.require_gpu("voxelize_dynamic", points)
+    pts = L.as_f32("voxelize_dynamic", points)
+    n, c = pts.shape
+    b = len(frame_offsets) - 1
+    cap = max(1, min(n, b * int(max_voxels)))
+    dev = pts.device
+    coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+    occupancy = torch.empty((cap,), dtype=torch.int32, device=dev)
+    mean = torch.empty((cap, c), dtype=torch.float32, device=dev)
+    point_voxel = torch.empty((n,), dtype=torch.int32, device=dev) if want_point_map else None
+    n_out = torch.zeros((2,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    ws = L.workspace(lib.v3d_voxelize_dynamic_workspace(n), dev)
+    with torch.cuda.device(dev):
+        L.check(lib.v3d_voxelize_dynamic(L.ptr(pts), n, c, L.host_i32(frame_offsets), b, L.host_f32(voxel_size), L.host_f32(bounds),
+                                         int(max_voxels), L.ptr(coords), L.ptr(occupancy), L.ptr(mean), L.ptr(point_voxel), L.ptr(n_out),
+                                         L.ptr(ws), ws.numel(), L.stream_ptr()), "voxelize_dynamic")
+    return coords, occupancy, mean, point_voxel, n_out
+
+
 class VoxelGenerator(object):
     """Same constructor/`generate` contract as spconv.utils.VoxelGenerator: returns
     (voxels (M,max_num_points,C), coordinates (M,3) int32 zyx, num_points_per_voxel (M,) int32).
