@@ -898,6 +898,42 @@ int v3d_pillar_train_bwd(const float* features, const int32_t* occupancy, const 
                          const int32_t* winner, const float* d_rows, const double* moments, float* dW, float* d_gamma, float* d_beta,
                          void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 
+/* ---- Dynamic pillar feature encoder (DynamicPillarVFE of MVF, arXiv 1910.06528; opt-in, cfg.PILLAR.DYNAMIC; no upstream counterpart):
+ * the encoder above over the outputs of v3d_voxelize_dynamic -- every point of a pillar counts, there is no slot tensor and no cap.
+ * The definition is this repository's: csrc/pillar_device.h "The DYNAMIC encoder", restated by DynamicPillarFeatureNet.forward_torch
+ * (detector/pillar.py) in torch and by tests/pillar_dynamic_ref.py in float64.  points (n_points, C) f32 = the frames concatenated
+ * (x, y, z first); point_voxel (n_points) i32 = the row of every point, any value outside [0, M) = dropped; voxel_mean (M, C) f32,
+ * occupancy (M) i32 = the true counts (>= 1), coordinates (M, 4) i32 (b, z, y, x); geometry_host and W as above.
+ * Kept point i of pillar v: f = [point | xyz - voxel_mean[v, :3] | xyz - pillar centre]; y = W f (fmaf chain, k ascending);
+ * out[v][c] = max over the pillar's points of relu(fmaf(y, scale[c], shift[c])); no padded candidate.  winner (M, channels) i32 = the
+ * FLAT index of the point that reaches the maximum, the lowest among equals: the results do not depend on the order of the points.
+ * Limits: 3 <= C <= 8, channels 64 or 128, n_points and M <= 2^22 -- beyond them V3D_EUNSUPPORTED before any launch; M = 0 returns
+ * V3D_OK and launches nothing.  The caller's stream, no host read, no float atomics (an integer cursor per pillar builds the point
+ * lists): two runs agree bit for bit.  Inconsistent inputs (occupancy that does not match point_voxel, indices out of range) never
+ * make a kernel leave its buffers: surplus points of a pillar are ignored, a pillar without a listed point gives a zero row, winner -1.
+ * _encode (eval, three launches: offsets, point lists, encode): scale / shift = the folded BatchNorm; winner may be NULL.
+ * _train_fwd (five launches): batch statistics over the N_kept = sum(occupancy) kept points (no padded rows) from the double moments,
+ * then the same encode.  bn (4, channels) as above; moments (K + K (K + 1) / 2 + 1) f64, the LAST entry = N_kept -- known on the device
+ * only, read there by the statistics and by the backward.  One kept point is legal (variance 0).
+ * _train_bwd (two launches): as v3d_pillar_train_bwd with N = N_kept; a winner is followed only where point_voxel[winner] names the
+ * pillar.  Gradients reach W, gamma and beta, never the points.
+ * workspace: 8-byte aligned, v3d_pillar_dynamic_workspace bytes (any of the three calls). */
+size_t v3d_pillar_dynamic_workspace(int n_points, int M, int C, int channels);
+int v3d_pillar_dynamic_encode(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                              const int32_t* occupancy, const int32_t* coordinates, int M, int C, const float* geometry_host,
+                              const float* W, int channels, const float* scale, const float* shift, float* rows, int32_t* winner,
+                              void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+int v3d_pillar_dynamic_train_fwd(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                                 const int32_t* occupancy, const int32_t* coordinates, int M, int C, const float* geometry_host,
+                                 const float* W, int channels, const float* gamma, const float* beta, float eps, float* rows,
+                                 int32_t* winner, float* bn, double* moments, void* workspace, size_t workspace_bytes,
+                                 v3d_stream_t stream);
+int v3d_pillar_dynamic_train_bwd(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                                 const int32_t* coordinates, int M, int C, const float* geometry_host, const float* W, int channels,
+                                 const float* gamma, float eps, const float* rows, const int32_t* winner, const float* d_rows,
+                                 const double* moments, float* dW, float* d_gamma, float* d_beta, void* workspace,
+                                 size_t workspace_bytes, v3d_stream_t stream);
+
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.
  * Every layer must be conv + BatchNorm1d (training mode: batch statistics) [+ ReLU] with a power-of-two Cout in [4, 256].

@@ -107,13 +107,15 @@ def _defaults():
         # pillar feature encoder for SECOND (detector/pillar.py; the PFN layer of PointPillars, not in the reference), opt-in: with a voxel
         # as tall as the grid the voxelizer's slots are pillars; every point becomes [channels | xyz - pillar mean | xyz - pillar centre],
         # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
-        # straight into the map the dense RPN reads (no sparse 3-D backbone; the dense plans are 128 wide, so Second takes CHANNELS=128)
-        PILLAR=dict(ENABLED=False, CHANNELS=128),
+        # straight into the map the dense RPN reads (no sparse 3-D backbone; the dense plans are 128 wide, so Second takes CHANNELS=128).
+        # DYNAMIC (inert unless ENABLED; DynamicPillarFeatureNet, the DynamicPillarVFE of MVF): the Preprocessor voxelizes dynamically and
+        # ignores MAX_OCCUPANCY, EVERY point of a pillar enters the maximum and the BatchNorm statistics (no padded rows); same parameters
+        PILLAR=dict(ENABLED=False, CHANNELS=128, DYNAMIC=False),
         # dynamic voxelization (csrc/voxelize.hip "DYNAMIC"; MVF / DynamicScatter, not in the reference), opt-in: a voxel takes EVERY point
         # inside it instead of the first MAX_OCCUPANCY in input order -- same cells, same row order, `occupancy` = the true counts,
         # `voxel_mean` an order-independent mean (integer sums of the values scaled by 2^24), a `point_voxel` map and no `features` slot
-        # tensor; values must stay below 2^16 in magnitude, at most 2^22 points per call; refused together with PILLAR (its encoder
-        # reads the point slots)
+        # tensor; values must stay below 2^16 in magnitude, at most 2^22 points per call; refused together with PILLAR (its hard encoder
+        # reads the point slots; cfg.PILLAR.DYNAMIC is the way to dynamic pillars)
         DYNAMIC_VOXELIZATION=dict(ENABLED=False),
         MAX_VOXELS=20000, MAX_OCCUPANCY=5, VOXEL_SIZE=[0.05, 0.05, 0.1],
         GRID_BOUNDS=[0, -40, -3, 70.4, 40, 1],
@@ -181,7 +183,14 @@ def refuse_dynamic_with_pillar(cfg):
     """The pillar encoder reads the point slots of the hard voxelizer, which the dynamic form does not produce."""
     if dynamic_voxel_enabled(cfg) and bool((cfg.get("PILLAR") or {}).get("ENABLED", False)):
         raise ValueError("cfg.DYNAMIC_VOXELIZATION.ENABLED together with cfg.PILLAR.ENABLED: the pillar encoder reads the (M, P, C) point "
-                         "slots, which dynamic voxelization does not produce (a dynamic pillar encoder over point_voxel is a follow-up)")
+                         "slots, which dynamic voxelization does not produce; set cfg.PILLAR.DYNAMIC instead (with DYNAMIC_VOXELIZATION "
+                         "off): the dynamic pillar encoder voxelizes dynamically itself and reads point_voxel")
+
+
+def pillar_dynamic_enabled(cfg):
+    """cfg.PILLAR.ENABLED and cfg.PILLAR.DYNAMIC (a config written before the key existed means "hard pillars")."""
+    opt = cfg.get("PILLAR") or {}
+    return bool(opt.get("ENABLED", False)) and bool(opt.get("DYNAMIC", False))
 
 
 def second_car_cfg():
@@ -190,6 +199,10 @@ def second_car_cfg():
 
 def pillar_car_cfg():
     return second_car_cfg().merge_from_dict(copy.deepcopy(PILLAR_KITTI))
+
+
+def pillar_dynamic_car_cfg():
+    return pillar_car_cfg().merge_from_dict(dict(PILLAR=dict(DYNAMIC=True)))
 
 
 def waymo_range_cfg():

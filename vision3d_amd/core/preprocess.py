@@ -11,6 +11,9 @@ VoxelFeatureExtractor output for callers that want to skip `features`.
 cfg.DYNAMIC_VOXELIZATION (opt-in): every point of a voxel counts (csrc/voxelize.hip "DYNAMIC").  The item then has
   points | coordinates | occupancy (the TRUE counts) | voxel_mean (order-independent) | point_voxel (sum Np,) i32 | batch_size
 and no `features` (the slot tensor does not exist in this mode); same voxels in the same order.
+
+cfg.PILLAR.ENABLED with cfg.PILLAR.DYNAMIC (opt-in, the dynamic pillar encoder): the same dynamic item -- MAX_OCCUPANCY is ignored --
+plus `flat_points` (sum Np, C), the concatenation of the frames that `point_voxel` indexes (a key of this mode only).
 """
 from collections import defaultdict
 
@@ -19,7 +22,7 @@ import torch
 from torch import nn
 
 from ..spconv.utils import VoxelGenerator, voxelize_batch, voxelize_dynamic_batch
-from .config import dynamic_voxel_enabled, refuse_dynamic_with_pillar
+from .config import dynamic_voxel_enabled, pillar_dynamic_enabled, refuse_dynamic_with_pillar
 
 
 class Preprocessor(nn.Module):
@@ -28,7 +31,8 @@ class Preprocessor(nn.Module):
         super().__init__()
         self.cfg = cfg
         refuse_dynamic_with_pillar(cfg)
-        self.dynamic = dynamic_voxel_enabled(cfg)  # cfg.DYNAMIC_VOXELIZATION (opt-in): see forward
+        self.pillar_dynamic = pillar_dynamic_enabled(cfg)  # cfg.PILLAR.DYNAMIC (opt-in): dynamic pillars, the item keeps `flat_points`
+        self.dynamic = dynamic_voxel_enabled(cfg) or self.pillar_dynamic  # cfg.DYNAMIC_VOXELIZATION (opt-in): see forward
         self.voxel_generator = self.build_voxel_generator(cfg)
         self._rng = np.random.default_rng(seed)  # reference pads with unseeded np.random (H12)
 
@@ -53,7 +57,8 @@ class Preprocessor(nn.Module):
 
     def generate_batch_voxels_dynamic(self, points):
         """cfg.DYNAMIC_VOXELIZATION: every point of a voxel counts.  -> (coordinates, occupancy (true counts), mean, point_voxel (sum N_b,)
-        row of every point of the concatenated clouds, -1 = dropped).  The one host read brings the status word with the count."""
+        row of every point of the concatenated clouds, -1 = dropped, flat = those clouds).  The one host read brings the status word
+        with the count."""
         offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in points])]).astype(np.int64).tolist()
         flat = torch.cat(points, dim=0) if len(points) > 1 else points[0]
         coords, occ, mean, point_voxel, n_out = voxelize_dynamic_batch(flat, offsets, self.cfg.VOXEL_SIZE, self.cfg.GRID_BOUNDS,
@@ -62,7 +67,7 @@ class Preprocessor(nn.Module):
         if status & 1:
             raise ValueError("dynamic voxelization: a point inside GRID_BOUNDS holds a channel value that is not finite or not below "
                              "2^16 in magnitude (the precondition of the exact integer sums; that voxel's mean is NaN)")
-        return coords[:m], occ[:m], mean[:m], point_voxel
+        return coords[:m], occ[:m], mean[:m], point_voxel, flat
 
     def pad_for_batch(self, points):
         """Dense (B, N, C) minibatch; short frames are padded by resampling their own points."""
@@ -79,9 +84,11 @@ class Preprocessor(nn.Module):
     def forward(self, item):
         points = [self._to_device(p) for p in item["points"]]
         if self.dynamic:  # no `features`: the slot tensor does not exist in this mode
-            coordinates, occupancy, mean, point_voxel = self.generate_batch_voxels_dynamic(points)
+            coordinates, occupancy, mean, point_voxel, flat = self.generate_batch_voxels_dynamic(points)
             item.update(points=self.pad_for_batch(points), coordinates=coordinates, occupancy=occupancy, voxel_mean=mean,
                         point_voxel=point_voxel, batch_size=len(points))
+            if self.pillar_dynamic:
+                item["flat_points"] = flat
             return item
         features, coordinates, occupancy, mean = self.generate_batch_voxels(points)
         item.update(points=self.pad_for_batch(points), features=features, coordinates=coordinates,

@@ -12,6 +12,7 @@
 //                          reduction across lanes); the four waves' sums are added in wave order: one partial per workgroup.
 //   pillar_bwd_final_kernel  a workgroup per channel: partials in workgroup order, then the closed forms of pillar_device.h.
 // No atomics: every sum has one fixed order for a given M, so two runs agree bit for bit.  No host synchronisation.
+// The dynamic encoder (cfg.PILLAR.DYNAMIC: the pillars of the dynamic voxelizer, every point counts) follows at the end of the file.
 #include "pillar_device.h"
 #include "scan_device.h"
 #include "v3d_internal.h"
@@ -148,24 +149,29 @@ __global__ __launch_bounds__(V3D_BLOCK) void pillar_moments_kernel(const float* 
   }
 }
 
-// One workgroup.  bn (4, CH): mean, biased variance, scale, shift.
+// One workgroup.  bn (4, CH): mean, biased variance, scale, shift.  counted (the dynamic encoder): every partial, and `moments`, end
+// in one more double, the number of rows behind the sums, and that sum is N -- the host does not know it.
 __global__ __launch_bounds__(V3D_BLOCK) void pillar_stats_kernel(const double* __restrict__ partials, int groups, int K, int CH, double N,
-                                                                 const float* __restrict__ W, const float* __restrict__ gamma,
+                                                                 int counted, const float* __restrict__ W, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float eps, double* __restrict__ moments,
                                                                  float* __restrict__ bn) {
-  __shared__ double S[V3D_PILLAR_MAX_MOMENTS];
-  const int nm = v3d::pillar_moments(K);
-  for (int i = threadIdx.x; i < nm; i += V3D_BLOCK) {
+  __shared__ double S[V3D_PILLAR_MAX_MOMENTS + 1];
+  const int nm = v3d::pillar_moments(K), entries = nm + (counted ? 1 : 0);
+  for (int i = threadIdx.x; i < entries; i += V3D_BLOCK) {
     double t = 0.0;
-    for (int b = 0; b < groups; b++) t += partials[(size_t)b * nm + i];
+    for (int b = 0; b < groups; b++) t += partials[(size_t)b * entries + i];
     S[i] = t;
     moments[i] = t;
   }
   __syncthreads();
+  if (counted) N = S[nm];
   for (int c = threadIdx.x; c < CH; c += V3D_BLOCK) {
     double mean, var, scale, shift;
     v3d::pillar_bn_stats(K, S, N, W + (size_t)c * K, mean, var);
-    v3d::pillar_fold(mean, var, (double)gamma[c], (double)beta[c], (double)eps, scale, shift);
+    if (counted)
+      v3d::pillar_fold_counted(N, mean, var, (double)gamma[c], (double)beta[c], (double)eps, scale, shift);
+    else
+      v3d::pillar_fold(mean, var, (double)gamma[c], (double)beta[c], (double)eps, scale, shift);
     bn[c] = (float)mean;
     bn[CH + c] = (float)var;
     bn[2 * CH + c] = (float)scale;
@@ -237,13 +243,14 @@ __global__ __launch_bounds__(V3D_BLOCK) void pillar_bwd_kernel(const float* __re
   }
 }
 
-// A workgroup of 64 threads per channel.
+// A workgroup of 64 threads per channel.  counted: N is the double behind the moments (pillar_stats_kernel).
 __global__ __launch_bounds__(64) void pillar_bwd_final_kernel(const double* __restrict__ partials, int groups, int K, int CH, double N,
-                                                              const double* __restrict__ moments, const float* __restrict__ W,
+                                                              int counted, const double* __restrict__ moments, const float* __restrict__ W,
                                                               const float* __restrict__ gamma, float eps, float* __restrict__ dW,
                                                               float* __restrict__ d_gamma, float* __restrict__ d_beta) {
   __shared__ double Gs[V3D_PILLAR_MAX_K + 2];
   const int c = blockIdx.x, Q = K + 2;
+  if (counted) N = moments[v3d::pillar_moments(K)];
   if ((int)threadIdx.x < Q) {
     double t = 0.0;
     for (int b = 0; b < groups; b++) t += partials[((size_t)b * CH + c) * Q + threadIdx.x];
@@ -252,7 +259,10 @@ __global__ __launch_bounds__(64) void pillar_bwd_final_kernel(const double* __re
   __syncthreads();
   if (threadIdx.x == 0) {
     double dw[V3D_PILLAR_MAX_K], dg, db;
-    v3d::pillar_bwd_channel(K, moments, N, W + (size_t)c * K, (double)gamma[c], (double)eps, Gs[0], Gs[1], Gs + 2, dw, dg, db);
+    if (counted)
+      v3d::pillar_bwd_channel_counted(K, moments, N, W + (size_t)c * K, (double)gamma[c], (double)eps, Gs[0], Gs[1], Gs + 2, dw, dg, db);
+    else
+      v3d::pillar_bwd_channel(K, moments, N, W + (size_t)c * K, (double)gamma[c], (double)eps, Gs[0], Gs[1], Gs + 2, dw, dg, db);
     for (int k = 0; k < K; k++) dW[(size_t)c * K + k] = (float)dw[k];
     d_gamma[c] = (float)dg;
     d_beta[c] = (float)db;
@@ -336,7 +346,7 @@ extern "C" int v3d_pillar_train_fwd(const float* features, const int32_t* occupa
   PL_DISPATCH_C(C, { hipLaunchKernelGGL((pillar_moments_kernel<PC>), dim3(groups), dim3(V3D_BLOCK), 0, st, features, occupancy, coordinates, M, P, g, partials); });
   V3D_CHECK_LAUNCH();
   hipLaunchKernelGGL(pillar_stats_kernel, dim3(1), dim3(V3D_BLOCK), 0, st, (const double*)partials, groups, C + 6, channels,
-                     (double)M * (double)P, W, gamma, beta, eps, moments, bn);
+                     (double)M * (double)P, 0, W, gamma, beta, eps, moments, bn);
   V3D_CHECK_LAUNCH();
   return pl_launch_encode(features, occupancy, coordinates, M, P, C, g, W, channels, bn + 2 * channels, bn + 3 * channels, rows, winner, st);
 }
@@ -364,7 +374,378 @@ extern "C" int v3d_pillar_train_bwd(const float* features, const int32_t* occupa
   });
   V3D_CHECK_LAUNCH();
   hipLaunchKernelGGL(pillar_bwd_final_kernel, dim3(channels), dim3(64), 0, st, (const double*)partials, groups, C + 6, channels,
-                     (double)M * (double)P, moments, W, gamma, eps, dW, d_gamma, d_beta);
+                     (double)M * (double)P, 0, moments, W, gamma, eps, dW, d_gamma, d_beta);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- dynamic encoder
+// The encoder over the dynamic voxelizer's point_voxel map (pillar_device.h "The DYNAMIC encoder"): every point of a pillar counts.
+//   pillar_dyn_offsets_kernel  one workgroup: offsets = exclusive scan of occupancy (scan_device.h), the cursors set to zero.
+//   pillar_dyn_list_kernel     a thread per point takes the next slot of its pillar with an integer atomic cursor: the point list.
+//                              The order inside a pillar may differ between runs; the winner rule does not depend on it.
+//   pillar_dyn_encode_kernel   one wave (a workgroup of its own) per pillar: the list is walked in chunks of 64 through the LDS slab,
+//                              a lane owns channels lane (+ 64) with their K weights in registers.
+//   pillar_dyn_moments_kernel  a thread per point, grid-stride in a capped grid: double moments and the kept count in registers, one
+//                              partial per workgroup; pillar_stats_kernel adds them in workgroup order and takes N from the count.
+//   pillar_dyn_bwd_kernel      a wave per pillar, a lane per channel: the winner POINT is read directly (it belongs to the pillar when
+//                              point_voxel says so); partials as pillar_bwd_kernel, then pillar_bwd_final_kernel with the counted N.
+// No float atomics; every float sum has one fixed order for a given (N, M): two runs agree bit for bit.
+//
+// GUARDS -- no input, however inconsistent, makes a kernel read or write outside its buffers:
+//   * a point_voxel outside [0, M) is skipped by every kernel that reads one (list, moments);
+//   * an occupancy is clamped to [0, N] and the running offset saturates at N, so 0 <= offsets[v] <= offsets[v + 1] <= N whatever
+//     the counts hold, and no partial sum leaves int (a thread's 8 items saturate at N <= 2^22, 256 threads: 2^30);
+//   * a point takes slot r of its pillar only when r < offsets[v + 1] - offsets[v]: a pillar with more points than its occupancy
+//     says loses the surplus instead of writing into its neighbour's range; list entries [offsets[v], offsets[v] + min(cursor[v],
+//     range)) are exactly the written ones -- the encode kernel reads no others, so an unfilled entry is never read;
+//   * a list entry outside [0, N) reads as "no point"; a winner is followed only when 0 <= winner < N and point_voxel[winner] is
+//     the pillar that names it.
+#define PD_SCAN_ITEMS 8
+#define PD_MAX_ENCODE_GROUPS 4096  // one-wave workgroups
+#define PD_MAX_N (1 << 22)         // the dynamic voxelizer's limit
+
+namespace {
+
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_dyn_offsets_kernel(const int32_t* __restrict__ occ, int M, int N, int32_t* __restrict__ offsets,
+                                                                       int32_t* __restrict__ cursor) {
+  __shared__ int lds[PL_WAVES];
+  int carry = 0;
+  for (int c0 = 0; c0 < M; c0 += V3D_BLOCK * PD_SCAN_ITEMS) {
+    const int first = c0 + threadIdx.x * PD_SCAN_ITEMS;
+    int n[PD_SCAN_ITEMS], mine = 0;
+#pragma unroll
+    for (int q = 0; q < PD_SCAN_ITEMS; q++) {
+      n[q] = first + q < M ? min(max(occ[first + q], 0), N) : 0;
+      mine = min(mine + n[q], N);
+    }
+    int total;
+    const int incl = v3d_block_scan_incl<PL_WAVES>(mine, total, lds);
+    int at = min(carry + (incl - mine), N);
+#pragma unroll
+    for (int q = 0; q < PD_SCAN_ITEMS; q++) {
+      if (first + q < M) {
+        offsets[first + q] = at;
+        cursor[first + q] = 0;
+      }
+      at = min(at + n[q], N);
+    }
+    carry = min(carry + total, N);
+    __syncthreads();  // the next round's scan writes `lds` again
+  }
+  if (threadIdx.x == 0) offsets[M] = carry;
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_dyn_list_kernel(const int32_t* __restrict__ point_voxel, int N, int M,
+                                                                    const int32_t* __restrict__ offsets, int32_t* __restrict__ cursor,
+                                                                    int32_t* __restrict__ list) {
+  const int i = blockIdx.x * V3D_BLOCK + threadIdx.x;
+  if (i >= N) return;
+  const int v = point_voxel[i];
+  if (v < 0 || v >= M) return;
+  const int start = offsets[v], room = offsets[v + 1] - start;  // 0 <= start, start + room <= N (pillar_dyn_offsets_kernel)
+  const int r = atomicAdd(cursor + v, 1);                       // at most N increments: no overflow
+  if (r < room) list[start + r] = i;
+}
+
+template <int C, int NCH>
+__global__ __launch_bounds__(64) void pillar_dyn_encode_kernel(const float* __restrict__ points, int N, const float* __restrict__ mean,
+                                                               const int32_t* __restrict__ coords, int M, const int32_t* __restrict__ offsets,
+                                                               const int32_t* __restrict__ cursor, const int32_t* __restrict__ list,
+                                                               PillarGeom g, const float* __restrict__ W, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, float* __restrict__ rows,
+                                                               int32_t* __restrict__ winner) {
+  constexpr int K = C + 6, CH = 64 * NCH;
+  __shared__ float4 slab4[64 * PL_ROW / 4];
+  __shared__ int index[64];
+  float* slab = reinterpret_cast<float*>(slab4);
+  const int lane = threadIdx.x;
+  float w[NCH][K], sc[NCH], sh[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    const int c = lane + 64 * j;
+#pragma unroll
+    for (int k = 0; k < K; k++) w[j][k] = W[c * K + k];
+    sc[j] = scale[c];
+    sh[j] = shift[c];
+  }
+  for (int m = blockIdx.x; m < M; m += gridDim.x) {
+    const int start = min(max(offsets[m], 0), N), room = min(max(offsets[m + 1], start), N) - start;
+    const int count = min(max(cursor[m], 0), room);  // the written entries of the pillar's range
+    float mu[3], centre[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      mu[k] = mean[(size_t)m * C + k];
+      centre[k] = v3d::pillar_centre(coords[(size_t)m * 4 + 3 - k], g.v[k], g.o[k]);
+    }
+    float best[NCH];
+    int win[NCH];
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      best[j] = -1.f;
+      win[j] = -1;
+    }
+    for (int base = 0; base < count; base += 64) {  // (workgroup = wave: every trip count is workgroup-uniform)
+      const int n = min(64, count - base);
+      int i = -1;
+      if (lane < n) {
+        i = list[start + base + lane];
+        if (i < 0 || i >= N) i = -1;
+      }
+      if (i >= 0) {
+        float pt[C], f[K];
+#pragma unroll
+        for (int k = 0; k < C; k++) pt[k] = points[(size_t)i * C + k];
+        v3d::pillar_feature_row<C>(pt, mu, centre, f);
+#pragma unroll
+        for (int k = 0; k < K; k++) slab[lane * PL_ROW + k] = f[k];
+      }
+      index[lane] = i;
+      __syncthreads();
+      for (int p = 0; p < n; p++) {
+        const int ip = index[p];
+        if (ip < 0) continue;
+        float f[K];
+        pl_read_row<K>(slab, p, f);
+        v3d::pillar_offer_point<K, NCH>(f, ip, w, sc, sh, best, win);
+      }
+      __syncthreads();  // the next chunk overwrites the slab
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      rows[(size_t)m * CH + lane + 64 * j] = win[j] >= 0 ? best[j] : 0.f;  // (no candidate: an empty or all-NaN pillar)
+      if (winner) winner[(size_t)m * CH + lane + 64 * j] = win[j];
+    }
+  }
+}
+
+// partials (groups, NM + 1) double: the moments, then the number of kept points.
+template <int C>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_dyn_moments_kernel(const float* __restrict__ points, const int32_t* __restrict__ point_voxel,
+                                                                       int N, const float* __restrict__ mean, const int32_t* __restrict__ coords,
+                                                                       int M, PillarGeom g, double* __restrict__ partials) {
+  constexpr int K = C + 6, NM = K + K * (K + 1) / 2;
+  __shared__ double red[PL_WAVES];
+  double S[NM], kept = 0.0;
+#pragma unroll
+  for (int i = 0; i < NM; i++) S[i] = 0.0;
+  for (int i = blockIdx.x * V3D_BLOCK + threadIdx.x; i < N; i += gridDim.x * V3D_BLOCK) {
+    const int v = point_voxel[i];
+    if (v < 0 || v >= M) continue;
+    float pt[C], mu[3], centre[3], f[K];
+#pragma unroll
+    for (int k = 0; k < C; k++) pt[k] = points[(size_t)i * C + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      mu[k] = mean[(size_t)v * C + k];
+      centre[k] = v3d::pillar_centre(coords[(size_t)v * 4 + 3 - k], g.v[k], g.o[k]);
+    }
+    v3d::pillar_feature_row<C>(pt, mu, centre, f);
+    v3d::pillar_moments_add<K>(f, S);
+    kept += 1.0;
+  }
+#pragma unroll
+  for (int i = 0; i < NM; i++) {
+    const double t = v3d_block_sum<PL_WAVES>(S[i], red);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * (NM + 1) + i] = t;
+  }
+  const double t = v3d_block_sum<PL_WAVES>(kept, red);
+  if (threadIdx.x == 0) partials[(size_t)blockIdx.x * (NM + 1) + NM] = t;
+}
+
+// partials (groups, CH, K + 2) double as pillar_bwd_kernel's.
+template <int C, int NCH>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_dyn_bwd_kernel(const float* __restrict__ points, const int32_t* __restrict__ point_voxel,
+                                                                   int N, const float* __restrict__ mean, const int32_t* __restrict__ coords,
+                                                                   int M, PillarGeom g, const float* __restrict__ W, const float* __restrict__ rows,
+                                                                   const int32_t* __restrict__ winner, const float* __restrict__ d_rows,
+                                                                   double* __restrict__ partials) {
+  constexpr int K = C + 6, CH = 64 * NCH, Q = K + 2;
+  __shared__ double red[PL_WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float w[NCH][K];
+  double G[NCH][Q];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+#pragma unroll
+    for (int k = 0; k < K; k++) w[j][k] = W[(lane + 64 * j) * K + k];
+#pragma unroll
+    for (int q = 0; q < Q; q++) G[j][q] = 0.0;
+  }
+  for (int m = blockIdx.x * PL_WAVES + wave; m < M; m += gridDim.x * PL_WAVES) {
+    float mu[3], centre[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      mu[k] = mean[(size_t)m * C + k];
+      centre[k] = v3d::pillar_centre(coords[(size_t)m * 4 + 3 - k], g.v[k], g.o[k]);
+    }
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      const size_t at = (size_t)m * CH + lane + 64 * j;
+      const int win = winner[at];
+      if (!(rows[at] > 0.f) || win < 0 || win >= N || point_voxel[win] != m) continue;  // (a winner outside the pillar: no gradient)
+      float pt[C], f[K];
+#pragma unroll
+      for (int k = 0; k < C; k++) pt[k] = points[(size_t)win * C + k];
+      v3d::pillar_feature_row<C>(pt, mu, centre, f);
+      const double gd = (double)d_rows[at], y = (double)v3d::pillar_dot<K>(w[j], f);
+      G[j][0] += gd;
+      G[j][1] += gd * y;
+#pragma unroll
+      for (int k = 0; k < K; k++) G[j][2 + k] += gd * (double)f[k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      __syncthreads();
+      red[wave][lane] = G[j][q];
+      __syncthreads();
+      if (wave == 0) {
+        double t = red[0][lane];
+#pragma unroll
+        for (int v = 1; v < PL_WAVES; v++) t += red[v][lane];
+        partials[((size_t)blockIdx.x * CH + lane + 64 * j) * Q + q] = t;
+      }
+    }
+  }
+}
+
+bool pd_supported(int n_points, int M, int C, int CH) {
+  return n_points <= PD_MAX_N && M <= PD_MAX_N && C >= V3D_PILLAR_MIN_C && C <= V3D_PILLAR_MAX_C && (CH == 64 || CH == 128);
+}
+
+int pd_moment_groups(int n_points) { return std::min(v3d_ceil_div(std::max(n_points, 1), V3D_BLOCK), PL_MAX_GROUPS); }
+
+// The workspace: doubles first (the partials of the moments, later of the backward), then offsets (M + 1), cursor (M), list (N).
+struct PdWorkspace {
+  double* partials;
+  int32_t *offsets, *cursor, *list;
+  bool ok;
+};
+
+size_t pd_partials_doubles(int n_points, int M, int C, int CH) {
+  const size_t fwd = (size_t)pd_moment_groups(n_points) * (v3d::pillar_moments(C + 6) + 1);
+  const size_t bwd = (size_t)pl_groups(std::max(M, 1), PL_MAX_GROUPS) * CH * (C + 8);
+  return std::max(fwd, bwd);
+}
+
+PdWorkspace pd_carve(void* workspace, size_t bytes, int n_points, int M, int C, int CH) {
+  V3dArena a(workspace, bytes);
+  PdWorkspace w;
+  w.partials = a.take<double>(pd_partials_doubles(n_points, M, C, CH));
+  w.offsets = a.take<int32_t>((size_t)M + 1);
+  w.cursor = a.take<int32_t>((size_t)M);
+  w.list = a.take<int32_t>((size_t)std::max(n_points, 1));
+  w.ok = a.ok() && w.partials && w.offsets && w.cursor && w.list;
+  return w;
+}
+
+// offsets -> list -> encode: the three launches of the eval forward, the last three of the training forward.
+int pd_launch_encode(const float* points, const int32_t* point_voxel, int N, const float* mean, const int32_t* occ, const int32_t* coords, int M,
+                     int C, const PillarGeom& g, const float* W, int CH, const float* scale, const float* shift, float* rows, int32_t* winner,
+                     const PdWorkspace& ws, hipStream_t st) {
+  hipLaunchKernelGGL(pillar_dyn_offsets_kernel, dim3(1), dim3(V3D_BLOCK), 0, st, occ, M, N, ws.offsets, ws.cursor);
+  V3D_CHECK_LAUNCH();
+  if (N > 0) {
+    hipLaunchKernelGGL(pillar_dyn_list_kernel, dim3(v3d_ceil_div(N, V3D_BLOCK)), dim3(V3D_BLOCK), 0, st, point_voxel, N, M,
+                       (const int32_t*)ws.offsets, ws.cursor, ws.list);
+    V3D_CHECK_LAUNCH();
+  }
+  const dim3 grid(std::min(M, PD_MAX_ENCODE_GROUPS)), block(64);
+  PL_DISPATCH_C(C, {
+    if (CH == 64)
+      hipLaunchKernelGGL((pillar_dyn_encode_kernel<PC, 1>), grid, block, 0, st, points, N, mean, coords, M, (const int32_t*)ws.offsets,
+                         (const int32_t*)ws.cursor, (const int32_t*)ws.list, g, W, scale, shift, rows, winner);
+    else
+      hipLaunchKernelGGL((pillar_dyn_encode_kernel<PC, 2>), grid, block, 0, st, points, N, mean, coords, M, (const int32_t*)ws.offsets,
+                         (const int32_t*)ws.cursor, (const int32_t*)ws.list, g, W, scale, shift, rows, winner);
+  });
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+}  // namespace
+
+extern "C" size_t v3d_pillar_dynamic_workspace(int n_points, int M, int C, int channels) {
+  if (n_points < 0 || M <= 0 || !pd_supported(n_points, M, C, channels)) return 256;
+  return v3d_align(pd_partials_doubles(n_points, M, C, channels) * sizeof(double)) + v3d_align(((size_t)M + 1) * 4) + v3d_align((size_t)M * 4) +
+         v3d_align((size_t)std::max(n_points, 1) * 4);
+}
+
+extern "C" int v3d_pillar_dynamic_encode(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                                         const int32_t* occupancy, const int32_t* coordinates, int M, int C, const float* geometry_host,
+                                         const float* W, int channels, const float* scale, const float* shift, float* rows, int32_t* winner,
+                                         void* workspace, size_t workspace_bytes, v3d_stream_t stream) {
+  if (M < 0 || n_points < 0 || !geometry_host) return V3D_EINVAL;
+  if (!pd_supported(n_points, M, C, channels)) return V3D_EUNSUPPORTED;
+  if (M == 0) return V3D_OK;
+  if ((n_points > 0 && (!points || !point_voxel)) || !voxel_mean || !occupancy || !coordinates || !W || !scale || !shift || !rows || !workspace)
+    return V3D_EINVAL;
+  if ((uintptr_t)workspace & 7) return V3D_EWORKSPACE;
+  const PdWorkspace ws = pd_carve(workspace, workspace_bytes, n_points, M, C, channels);
+  if (!ws.ok) return V3D_EWORKSPACE;
+  return pd_launch_encode(points, point_voxel, n_points, voxel_mean, occupancy, coordinates, M, C, pl_geom(geometry_host), W, channels, scale,
+                          shift, rows, winner, ws, (hipStream_t)stream);
+}
+
+extern "C" int v3d_pillar_dynamic_train_fwd(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                                            const int32_t* occupancy, const int32_t* coordinates, int M, int C, const float* geometry_host,
+                                            const float* W, int channels, const float* gamma, const float* beta, float eps, float* rows,
+                                            int32_t* winner, float* bn, double* moments, void* workspace, size_t workspace_bytes,
+                                            v3d_stream_t stream) {
+  if (M < 0 || n_points < 0 || !geometry_host) return V3D_EINVAL;
+  if (!pd_supported(n_points, M, C, channels)) return V3D_EUNSUPPORTED;
+  if (M == 0) return V3D_OK;
+  if ((n_points > 0 && (!points || !point_voxel)) || !voxel_mean || !occupancy || !coordinates || !W || !gamma || !beta || !rows || !winner ||
+      !bn || !moments || !workspace)
+    return V3D_EINVAL;
+  if (((uintptr_t)workspace & 7) || ((uintptr_t)moments & 7)) return V3D_EWORKSPACE;
+  const PdWorkspace ws = pd_carve(workspace, workspace_bytes, n_points, M, C, channels);
+  if (!ws.ok) return V3D_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const PillarGeom g = pl_geom(geometry_host);
+  const int groups = pd_moment_groups(n_points);
+  PL_DISPATCH_C(C, {
+    hipLaunchKernelGGL((pillar_dyn_moments_kernel<PC>), dim3(groups), dim3(V3D_BLOCK), 0, st, points, point_voxel, n_points, voxel_mean, coordinates,
+                       M, g, ws.partials);
+  });
+  V3D_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pillar_stats_kernel, dim3(1), dim3(V3D_BLOCK), 0, st, (const double*)ws.partials, groups, C + 6, channels, 0.0, 1, W, gamma,
+                     beta, eps, moments, bn);
+  V3D_CHECK_LAUNCH();
+  return pd_launch_encode(points, point_voxel, n_points, voxel_mean, occupancy, coordinates, M, C, g, W, channels, bn + 2 * channels,
+                          bn + 3 * channels, rows, winner, ws, st);
+}
+
+extern "C" int v3d_pillar_dynamic_train_bwd(const float* points, const int32_t* point_voxel, int n_points, const float* voxel_mean,
+                                            const int32_t* coordinates, int M, int C, const float* geometry_host, const float* W, int channels,
+                                            const float* gamma, float eps, const float* rows, const int32_t* winner, const float* d_rows,
+                                            const double* moments, float* dW, float* d_gamma, float* d_beta, void* workspace,
+                                            size_t workspace_bytes, v3d_stream_t stream) {
+  if (M <= 0 || n_points < 0 || !geometry_host) return V3D_EINVAL;
+  if (!pd_supported(n_points, M, C, channels)) return V3D_EUNSUPPORTED;
+  if ((n_points > 0 && (!points || !point_voxel)) || !voxel_mean || !coordinates || !W || !gamma || !rows || !winner || !d_rows || !moments ||
+      !dW || !d_gamma || !d_beta || !workspace)
+    return V3D_EINVAL;
+  const int groups = pl_groups(M, PL_MAX_GROUPS);
+  if (workspace_bytes < (size_t)groups * channels * (C + 8) * sizeof(double) || ((uintptr_t)workspace & 7) || ((uintptr_t)moments & 7))
+    return V3D_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const PillarGeom g = pl_geom(geometry_host);
+  double* partials = (double*)workspace;
+  PL_DISPATCH_C(C, {
+    if (channels == 64)
+      hipLaunchKernelGGL((pillar_dyn_bwd_kernel<PC, 1>), dim3(groups), dim3(V3D_BLOCK), 0, st, points, point_voxel, n_points, voxel_mean,
+                         coordinates, M, g, W, rows, winner, d_rows, partials);
+    else
+      hipLaunchKernelGGL((pillar_dyn_bwd_kernel<PC, 2>), dim3(groups), dim3(V3D_BLOCK), 0, st, points, point_voxel, n_points, voxel_mean,
+                         coordinates, M, g, W, rows, winner, d_rows, partials);
+  });
+  V3D_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pillar_bwd_final_kernel, dim3(channels), dim3(64), 0, st, (const double*)partials, groups, C + 6, channels, 0.0, 1, moments,
+                     W, gamma, eps, dW, d_gamma, d_beta);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

@@ -22,6 +22,18 @@
 //   d_beta = G0;  d_gamma = s (Gy - mean_y G0)
 //   dW[k]  = gamma s (Gf[k] - d_beta / N * S1[k] - d_gamma / N * s (sum_i S2[k][i] w[i] - mean_y S1[k]))
 // -- the "all rows" sums of the BatchNorm gradient are closed forms in the same moments.
+//
+// The DYNAMIC encoder (DynamicPillarVFE of MVF, arXiv 1910.06528; opt-in, cfg.PILLAR.DYNAMIC) -- every point of a pillar counts.  The
+// pillars are those of the dynamic voxelizer: points (N, C) flat, point_voxel (N) the row of every point (outside [0, M): dropped),
+// voxel_mean (M, C), occupancy (M) the true counts (>= 1), coordinates (M, 4).  Per kept point i of pillar v:
+//   f = [point | xyz - voxel_mean[v, :3] | xyz - centre(v)],  y = pillar_dot(W_c, f),  a = pillar_activation(y, scale, shift)
+//   rows[v][c] = max of a over the pillar's points; there is no padded candidate (every pillar has a point)
+// winner[v][c] = the FLAT index of the point that reaches the maximum, the lowest among equals (pillar_offer_lowest): the result does
+// not depend on the order in which a pillar's points are visited.  Training: the moments run over the kept points only, N = N_kept =
+// their number (= sum of occupancy), known on the device alone -- it travels as one more double behind the moments; pillar_bn_stats,
+// pillar_fold_counted and pillar_bwd_channel_counted take it as their N.  One kept point is legal: variance 0, rows = relu(beta)
+// exactly, gradient to beta alone (stated by the two _counted forms).  tests/host/pillar_dynamic_host_shim.cpp compiles this text with g++, detector/pillar.py
+// (DynamicPillarFeatureNet.forward_torch) states it in torch, tests/pillar_dynamic_ref.py in float64.
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -96,6 +108,23 @@ V3D_HD void pillar_offer(float a, int index, float& best, int& win) {
   }
 }
 
+// The winner rule of the DYNAMIC encoder (below): candidates carry the flat index of their point and arrive in any order; a candidate
+// replaces the best when strictly greater, or equal with a lower index -- the lowest index that reaches the maximum wins whatever the
+// order.  Start from best = -1, win = -1 (the first real candidate is strictly greater); a NaN activation never wins.
+V3D_HD void pillar_offer_lowest(float a, int index, float& best, int& win) {
+  if (a > best || (a == best && index < win)) {
+    best = a;
+    win = index;
+  }
+}
+
+// One point of the dynamic encoder (flat index i) offered to the NCH channels a lane owns.
+template <int K, int NCH>
+V3D_HD void pillar_offer_point(const float* f, int i, const float (*w)[K], const float* scale, const float* shift, float* best, int* win) {
+#pragma unroll
+  for (int j = 0; j < NCH; j++) pillar_offer_lowest(pillar_activation(pillar_dot<K>(w[j], f), scale[j], shift[j]), i, best[j], win[j]);
+}
+
 // One real row offered to the NCH channels a lane owns (w[j]: the K weights of its j-th channel).
 template <int K, int NCH>
 V3D_HD void pillar_offer_row(const float* f, int p, const float (*w)[K], const float* scale, const float* shift, float* best, int* win) {
@@ -137,6 +166,19 @@ V3D_HD void pillar_fold(double mean, double var, double gamma, double beta, doub
   shift = beta - mean * scale;
 }
 
+// The fold of the dynamic encoder's training forward, where N is counted on the device and may be 1.  With ONE row the batch mean of
+// every channel is that row's y and the variance is 0 by construction, so (y - mean) is zero whatever y: the normalised value is
+// beta exactly.  The general fold would compute that zero as fp32 y minus a double mean times 1 / sqrt(eps) -- about 30 times the
+// rounding of y -- so the one-row batch states its result instead: scale = 0, shift = beta, a = relu(beta).
+V3D_HD void pillar_fold_counted(double N, double mean, double var, double gamma, double beta, double eps, double& scale, double& shift) {
+  if (N == 1.0) {
+    scale = 0.0;
+    shift = beta;
+  } else {
+    pillar_fold(mean, var, gamma, beta, eps, scale, shift);
+  }
+}
+
 // The backward of one channel from its winner sums (header comment); dW: K doubles.
 V3D_HD void pillar_bwd_channel(int K, const double* S, double N, const float* w, double gamma, double eps, double G0, double Gy,
                                const double* Gf, double* dW, double& d_gamma, double& d_beta) {
@@ -151,6 +193,19 @@ V3D_HD void pillar_bwd_channel(int K, const double* S, double N, const float* w,
     for (int i = 0; i < K; i++) s2w += S[pillar_s2(K, k, i)] * (double)w[i];
     const double xf = s * (s2w - mean * S[k]);  // sum over all rows of xhat * f[k]
     dW[k] = gamma * s * (Gf[k] - b_n * S[k] - g_n * xf);
+  }
+}
+
+// ... of the dynamic encoder (N counted on the device).  One row: the output is relu(beta) whatever W and gamma (pillar_fold_counted),
+// so the gradient reaches beta alone -- stated, not left to the cancellation of the closed forms.
+V3D_HD void pillar_bwd_channel_counted(int K, const double* S, double N, const float* w, double gamma, double eps, double G0, double Gy,
+                                       const double* Gf, double* dW, double& d_gamma, double& d_beta) {
+  if (N == 1.0) {
+    for (int k = 0; k < K; k++) dW[k] = 0.0;
+    d_gamma = 0.0;
+    d_beta = G0;
+  } else {
+    pillar_bwd_channel(K, S, N, w, gamma, eps, G0, Gy, Gf, dW, d_gamma, d_beta);
   }
 }
 

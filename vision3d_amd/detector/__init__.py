@@ -16,6 +16,7 @@ _EXPORTS = {
     "CenterHead": "center_head",
     "CenterLoss": "center_head",
     "PillarFeatureNet": "pillar",
+    "DynamicPillarFeatureNet": "pillar",
 }
 __all__ = sorted(_EXPORTS)
 

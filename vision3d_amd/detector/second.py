@@ -159,15 +159,16 @@ class Second(nn.Module):
 
     def __init__(self, cfg):
         super().__init__()
-        from .pillar import PillarFeatureNet, pillar_enabled
-        from ..core.config import dynamic_voxel_enabled, refuse_dynamic_with_pillar
+        from .pillar import DynamicPillarFeatureNet, PillarFeatureNet, pillar_enabled
+        from ..core.config import dynamic_voxel_enabled, pillar_dynamic_enabled, refuse_dynamic_with_pillar
         refuse_dynamic_with_pillar(cfg)
         # cfg.DYNAMIC_VOXELIZATION (opt-in): the Preprocessor's items carry voxel_mean over ALL points of a voxel and no `features`; the
         # backbone plans behind the raw-point entry points voxelize the same way (runtime.BackbonePlan)
         self.dynamic_voxels = dynamic_voxel_enabled(cfg)
         self.pillar = pillar_enabled(cfg)  # cfg.PILLAR (opt-in): the pillar encoder writes the BEV map itself, no sparse backbone
         if self.pillar:
-            self.vfe = PillarFeatureNet(cfg)
+            # cfg.PILLAR.DYNAMIC (opt-in): the same parameters over the dynamic voxelizer's item, every point of a pillar counts
+            self.vfe = DynamicPillarFeatureNet(cfg) if pillar_dynamic_enabled(cfg) else PillarFeatureNet(cfg)
             if self.vfe.channels != 128:
                 raise ValueError(f"cfg.PILLAR.CHANNELS = {self.vfe.channels}: Second takes 128 (the native dense RPN plans, inference and "
                                  "training, are 128 channels wide); PillarFeatureNet alone also runs 64")
