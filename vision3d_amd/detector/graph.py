@@ -57,6 +57,7 @@ class GraphedSecond(object):
         # must not invalidate this capture
         with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.outputs = self._body()
+        self.captured = (self.plan._param_stamp(), self.dense._param_stamp())  # what the graph baked in (packed images, scale entries)
 
     def _body(self):
         # (the slot's plan keeps its own BEV planes: a frame clears the pixels the previous one wrote, no 18 MB fill)
@@ -82,12 +83,13 @@ class GraphedSecond(object):
                 self.static_points[a + n:b].fill_(PAD_COORDINATE)
 
     def weights_changed(self):
-        """One integer comparison per launch (Second.notify_weights_changed); the tensors are looked at only when it moved."""
+        """One integer comparison per launch (Second.notify_weights_changed); the tensors are looked at only when it moved, and then
+        against THIS graph's capture: the plans are shared (eager calls, a pipeline's other slots), their "since the last upload" is not it."""
         epoch = self.model.__dict__.get("_weights_epoch", 0)
         if epoch == self.__dict__.get("_seen_epoch"):
             return False
         self._seen_epoch = epoch
-        return self.plan.weights_changed() or self.dense.weights_changed()
+        return (self.plan._param_stamp(), self.dense._param_stamp()) != self.captured
 
     def launch(self):
         """Enqueue the frame sitting in the static buffer.  Captures on first use -- and AGAIN when a parameter of the model changed

@@ -6,6 +6,8 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ..stamp import cached
+
 
 class VoxelFeatureExtractor(nn.Module):
     """(M, K, C) zero-padded point slots + (M,) occupancy -> (M, C) mean over the occupied slots.
@@ -69,12 +71,10 @@ class BEVFeatureGatherer(nn.Module):
         b, c, height, width = feature_map.shape
         xyz = keypoint_xyz.contiguous()
         k = xyz.shape[1]
-        consts = self.__dict__.setdefault("_host_consts", {})
-        key = (str(feature_map.device),)
-        if key not in consts:  # the module's own fp32 arithmetic, once, on the host: pixel = base_pixel_size * STRIDES[-1]
-            pixel = (self.base_pixel_size.detach().cpu().float() * self.cfg.STRIDES[-1]).tolist()
-            consts[key] = (self.pixel_offset.detach().cpu().float().tolist(), pixel)
-        (off_x, off_y), (pix_x, pix_y) = consts[key]
+        offset, base = self._buffers["pixel_offset"], self._buffers["base_pixel_size"]
+        # the module's own fp32 arithmetic on the host, once per state of the two buffers: pixel = base_pixel_size * STRIDES[-1]
+        (off_x, off_y), (pix_x, pix_y) = cached(self, "_host_consts", (offset, base), lambda: (
+            offset.detach().cpu().float().tolist(), (base.detach().cpu().float() * self.cfg.STRIDES[-1]).tolist()), str(feature_map.device))
         if out_pm is None:
             out_pm = torch.empty((b, k, c), dtype=torch.float32, device=feature_map.device)
         if out_pm.shape[:2] != (b, k) or out_pm.shape[2] < c or out_pm.stride(2) != 1 or out_pm.stride(0) != k * out_pm.stride(1):
@@ -150,12 +150,12 @@ class MLP(nn.Sequential):
         """[(W^T (K, Nout padded to 16), bias padded or None, relu, Nout)] per Linear, cached until a parameter changes.  `first_rows`:
         a permutation of the FIRST layer's input features (the caller holds them in another order: RoiGridPool's point-major rows)."""
         mods = list(self)
-        lins = [m for m in mods if isinstance(m, nn.Linear)]
-        stamp = tuple((t.data_ptr(), t._version) for l in lins for t in (l.weight, l.bias) if t is not None)
-        cache = self.__dict__.setdefault("_pack_cache", {})
         key = None if first_rows is None else (first_rows.data_ptr(), first_rows.numel())
-        if key in cache and cache[key][0] == stamp:
-            return cache[key][1]
+        return cached(self, "_pack_cache", (t for m in mods if isinstance(m, nn.Linear) for t in (m.weight, m.bias)),
+                      lambda: self._pack(mods, first_rows), key)
+
+    @staticmethod
+    def _pack(mods, first_rows):
         packed, k_pad = [], None
         with torch.no_grad():
             for i, m in enumerate(mods):
@@ -176,7 +176,6 @@ class MLP(nn.Sequential):
                 relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
                 packed.append((full.contiguous(), bias, relu, nout))
                 k_pad = npad
-        cache[key] = (stamp, packed)
         return packed
 
     def native_forward(self, x, first_rows=None):

@@ -23,6 +23,7 @@ from torch import nn
 
 from .. import _lib as L
 from .. import spconv
+from ..stamp import cached
 
 PILLAR_DEFAULTS = dict(ENABLED=False, CHANNELS=128)
 MAX_P, MIN_C, MAX_C, WIDTHS = 64, 3, 8, (64, 128)  # the native limits (csrc/pillar_device.h)
@@ -192,14 +193,12 @@ class PillarFeatureNet(nn.Module):
     # ---- eval-mode BatchNorm folded to scale / shift, cached until a tensor changes (as RPN._folded)
     def _folded(self):
         n = self.norm
-        stamp = tuple((t.data_ptr(), t._version) for t in (n.running_mean, n.running_var, n.weight, n.bias))
-        cache = self.__dict__.get("_fold_cache")
-        if cache is None or cache[0] != stamp:
+
+        def build():
             with torch.no_grad():
                 scale = torch.rsqrt(n.running_var + n.eps) * n.weight
-                cache = (stamp, (scale.contiguous(), (n.bias - n.running_mean * scale).contiguous()))
-            self.__dict__["_fold_cache"] = cache
-        return cache[1]
+                return scale.contiguous(), (n.bias - n.running_mean * scale).contiguous()
+        return cached(self, "_fold_cache", (n.running_mean, n.running_var, n.weight, n.bias), build)
 
     def forward(self, item):
         self._check(item)

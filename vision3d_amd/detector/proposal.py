@@ -20,6 +20,7 @@ from .. import _lib as L
 from ..core.box_encode import decode
 from ..core.proposal_targets import direction_config
 from ..ops import batched_nms_rotated, batched_nms_rotated_padded, sigmoid_focal_loss
+from ..stamp import cached
 from .fused_loss import scale_gradient, take_gradient
 
 
@@ -362,16 +363,13 @@ class ProposalLayer(nn.Module):
         directly; this entry is for callers that hold an fp32 feature map: PV_RCNN.proposal, `model.head(features)`.)"""
         from ..runtime import conv2d_split, pack_conv_weight, to_split_nhwc
         convs = fused_convs(self)
-        tensors = tuple(t for c in convs for t in (c.weight, c.bias))
-        stamp = tuple((t.data_ptr(), t._version) for t in tensors)
-        cache = self.__dict__.get("_native_head")
-        if cache is None or cache[0] != stamp:
+
+        def build():
             with torch.no_grad():
                 w = torch.cat([c.weight for c in convs], 0)
                 bias = torch.cat([c.bias for c in convs], 0).float().contiguous()
-                cache = (stamp, pack_conv_weight(w, None, "fp32"), bias, w.shape[1], w.shape[0])
-            self.__dict__["_native_head"] = cache
-        _, img, bias, cin, cout = cache
+                return pack_conv_weight(w, None, "fp32"), bias, w.shape[1], w.shape[0]
+        img, bias, cin, cout = cached(self, "_native_head", (t for c in convs for t in (c.weight, c.bias)), build)
         hi, lo = to_split_nhwc(feature_map.float(), "fp32")
         return conv2d_split(hi, lo, img, bias, False, cin, cout, 1, out_split=False, out_nchw=True, pr=(hi.v3d_entry, None, None))[1]
 

@@ -14,6 +14,7 @@ from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
 from .. import spconv
+from ..stamp import cached
 from .layers import VoxelFeatureExtractor
 from .proposal import ProposalLayer
 from .sparse_cnn import SpMiddleFHD
@@ -105,19 +106,16 @@ class RPN(nn.Module):
         """Eval-mode BatchNorm folded into each conv's weight/bias, cached until a tensor changes."""
         convs = [m for m in list(self.down_block) + list(self.up_block) if isinstance(m, nn.Conv2d)]
         bns = [m for m in list(self.down_block) + list(self.up_block) if isinstance(m, _BatchNorm)]
-        stamp = tuple((t.data_ptr(), t._version) for c, b in zip(convs, bns)
-                      for t in (c.weight, b.running_mean, b.running_var, b.weight, b.bias))
-        cache = self.__dict__.get("_fold_cache")
-        if cache is None or cache[0] != stamp:
+        tensors = (t for c, b in zip(convs, bns) for t in (c.weight, b.running_mean, b.running_var, b.weight, b.bias))
+
+        def build():
             folded = []
             with torch.no_grad():
                 for c, b in zip(convs, bns):
                     inv = torch.rsqrt(b.running_var + b.eps) * b.weight
-                    folded.append(((c.weight * inv.view(-1, 1, 1, 1)).contiguous(), (b.bias - b.running_mean * inv).contiguous(),
-                                   c.padding))
-            cache = (stamp, folded)
-            self.__dict__["_fold_cache"] = cache
-        return cache[1]
+                    folded.append(((c.weight * inv.view(-1, 1, 1, 1)).contiguous(), (b.bias - b.running_mean * inv).contiguous(), c.padding))
+            return folded
+        return cached(self, "_fold_cache", tensors, build)
 
     def native_forward(self, x):
         """fp32 (B, C, H, W) cuda -> fp32 (B, C_up, H, W): the seven conv + folded-BN + ReLU layers on csrc/dense_conv.hip

@@ -20,6 +20,7 @@ from torch import nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
 from .. import spconv
+from ..stamp import cached
 
 BN_EPS, BN_MOMENTUM = 1e-3, 0.01
 
@@ -137,10 +138,10 @@ class SparseCNNBase(nn.Module):
         if ind.is_cuda and ind.dtype == torch.int32 and ind.dim() == 2 and ind.shape[1] == 4 and ind.is_contiguous() and ind.data_ptr() % 16 == 0:
             # the statements below in one launch (csrc/pointops.hip v3d_voxel_centers): same values
             from .. import _lib as L
-            consts = self.__dict__.setdefault("_global_consts", {})
-            if stride not in consts:  # base_voxel_size * stride rounded in fp32 like the tensor product, once, on the host
-                consts[stride] = ((self.base_voxel_size.detach().cpu().float() * stride).tolist(), self.voxel_offset.detach().cpu().float().tolist())
-            (sx, sy, sz), (ox, oy, oz) = consts[stride]
+            base, offset = self._buffers["base_voxel_size"], self._buffers["voxel_offset"]
+            # base_voxel_size * stride rounded in fp32 like the tensor product, on the host, once per state of the two buffers
+            (sx, sy, sz), (ox, oy, oz) = cached(self, "_global_consts", (base, offset), lambda: (
+                (base.detach().cpu().float() * stride).tolist(), offset.detach().cpu().float().tolist()), key=stride)
             xyz = torch.empty((ind.shape[0], 3), dtype=torch.float32, device=ind.device)
             with L.device_guard(ind.device):
                 L.check(L.lib().v3d_voxel_centers(L.ptr(ind), ind.shape[0], sx, sy, sz, ox, oy, oz, L.ptr(xyz), L.stream_ptr()), "voxel_centers")

@@ -24,6 +24,7 @@ take `query_torch`, the search in torch chunked over the queries."""
 import torch
 from torch import nn
 
+from ..stamp import cached
 from .layers import MLP
 
 VECTORPOOL_DEFAULTS = dict(
@@ -291,12 +292,10 @@ class VectorPoolAggregationMSG(nn.Module):
     def _folded(self):
         """The parameters as the kernels take them, eval BatchNorms folded in, cached until a parameter or running statistic changes:
         per group (w_local (nv, Cr + 9, CL), shift (nv * CL), [(W (K, Nout padded to 16), bias, Nout)]), then the MSG_POST layers."""
-        tensors = [t for mod in self.modules() for t in list(mod._parameters.values()) + list(mod._buffers.values()) if t is not None]
-        stamp = tuple((t.data_ptr(), t._version) for t in tensors)
-        cache = self.__dict__.get("_fold_cache")
-        if cache is not None and cache[0] == stamp:
-            return cache[1]
+        tensors = (t for mod in self.modules() for t in list(mod._parameters.values()) + list(mod._buffers.values()))
+        return cached(self, "_fold_cache", tensors, self._fold_all)
 
+    def _fold_all(self):
         def layers(mlp, k_in):
             lins = [mod for mod in mlp if isinstance(mod, nn.Linear)]
             bns = [mod for mod in mlp if isinstance(mod, nn.BatchNorm1d)]
@@ -320,9 +319,7 @@ class VectorPoolAggregationMSG(nn.Module):
                 w_local = (g.local_weight.float() * scale.view(g.nv, 1, g.local)).contiguous()
                 groups.append((w_local, shift, layers(g.post, g.nv * g.local)))
             cat_width = -(-sum(g.out_width() for g in self.groups) // 4) * 4
-            folded = (groups, layers(self.msg_post, cat_width), cat_width)
-        self.__dict__["_fold_cache"] = (stamp, folded)
-        return folded
+            return groups, layers(self.msg_post, cat_width), cat_width
 
     def forward_native(self, xyz, features_pm, new_xyz):
         """`native_ok` inputs -> (B, C_out, M), a view of point-major rows.  Only enqueues: no host read."""

@@ -25,6 +25,7 @@ from collections import namedtuple
 import torch
 from torch import nn
 
+from ..stamp import cached
 from .layers import MLP
 from .roi_grid_pool import gridpoints
 
@@ -257,11 +258,11 @@ class VoxelRoiPool(nn.Module):
         """Level k's MLP with eval BatchNorm folded in, as the kernels take it: (W1[3:]^T (C, K1), W1[0:3]^T (3, K1), b1 (K1),
         W2^T (K1, Nout), b2 (Nout)), cached until a parameter or running statistic changes."""
         mlp = self.mlps[k]
-        tensors = [t for m in mlp for t in list(m._parameters.values()) + list(m._buffers.values()) if t is not None]
-        stamp = tuple((t.data_ptr(), t._version) for t in tensors)
-        cache = self.__dict__.setdefault("_fold_cache", {})
-        if k in cache and cache[k][0] == stamp:
-            return cache[k][1]
+        tensors = (t for m in mlp for t in list(m._parameters.values()) + list(m._buffers.values()))
+        return cached(self, "_fold_cache", tensors, lambda: self._fold(mlp), k)
+
+    @staticmethod
+    def _fold(mlp):
         lins = [m for m in mlp if isinstance(m, nn.Linear)]
         bns = [m for m in mlp if isinstance(m, nn.BatchNorm1d)]
         folded = []
@@ -270,9 +271,7 @@ class VoxelRoiPool(nn.Module):
                 scale = bn.weight.float() * torch.rsqrt(bn.running_var.float() + bn.eps)
                 folded.append(((lin.weight.float() * scale[:, None]).t().contiguous(), (bn.bias.float() - bn.running_mean.float() * scale).contiguous()))
         (w1, b1), (w2, b2) = folded
-        out = (w1[3:].contiguous(), w1[0:3].contiguous(), b1, w2, b2)
-        cache[k] = (stamp, out)
-        return out
+        return w1[3:].contiguous(), w1[0:3].contiguous(), b1, w2, b2
 
     def forward_native(self, boxes, levels):
         """`native_ok` inputs: per level query + first-layer products + pooling into the level's column block of ONE (R, C_total) matrix,

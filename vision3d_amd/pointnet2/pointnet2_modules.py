@@ -5,6 +5,7 @@ use_xyz (upstream behaviour -- the reason the reference deep-copies its config l
 import torch
 from torch import nn
 
+from ..stamp import cached
 from . import pointnet2_utils as PU
 
 
@@ -99,10 +100,11 @@ class PointnetSAModuleMSG(nn.Module):
                         [(b, n) for b in bns for n in ("weight", "bias", "running_mean", "running_var")])
         _, convs, bns, names = lists[k]
         # (a Parameter may be REPLACED on its module -- .cuda(), load_state_dict(assign=True): read it through the module's dicts)
-        stamp = tuple((t.data_ptr(), t._version) for t in (m._parameters.get(n, None) if n in m._parameters else m._buffers[n] for m, n in names))
-        cache = self.__dict__.setdefault("_pack_cache", {})
-        if k in cache and cache[k][0] == stamp:
-            return cache[k][1]
+        tensors = (m._parameters[n] if n in m._parameters else m._buffers[n] for m, n in names)
+        return cached(self, "_pack_cache", tensors, lambda: self._pack(convs, bns), k)
+
+    @staticmethod
+    def _pack(convs, bns):
         packed, k_prev_pad = [], None
         with torch.no_grad():
             for li, conv in enumerate(convs):
@@ -127,7 +129,6 @@ class PointnetSAModuleMSG(nn.Module):
                 bpad[:conv.out_channels] = bias
                 packed.append((full.contiguous(), bpad.contiguous()))
                 k_prev_pad = nout_pad
-        cache[k] = (stamp, packed)
         return packed
 
     def max_radius(self):

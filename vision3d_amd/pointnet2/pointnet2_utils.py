@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from .. import _lib as L
+from ..stamp import stamp_of
 
 
 def furthest_point_sample(xyz, npoint):
@@ -132,11 +133,10 @@ class BallQueryGrid:
 
     def __init__(self, xyz, radius_max, workspace):
         self.workspace, self.radius_max = workspace, float(radius_max)
-        self.shape, self.stamp = tuple(xyz.shape), (xyz.data_ptr(), xyz._version)
+        self.stamp = stamp_of((xyz,), tuple(xyz.shape))
 
     def matches(self, xyz, radius):
-        return (tuple(xyz.shape) == self.shape and (xyz.data_ptr(), xyz._version) == self.stamp
-                and abs(float(radius)) <= self.radius_max)
+        return stamp_of((xyz,), tuple(xyz.shape)) == self.stamp and abs(float(radius)) <= self.radius_max
 
 
 def ball_query_grids(databases):

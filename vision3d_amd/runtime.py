@@ -14,6 +14,7 @@ from torch import nn
 from . import _lib as L
 from .spconv.conv import _SparseConvBase
 from .spconv.modules import fold_batchnorm
+from .stamp import stamp_of
 
 
 class RangeOverflow(RuntimeError):
@@ -179,11 +180,8 @@ class BackbonePlan(object):
                 self.calibration_generation = self.__dict__.get("calibration_generation", 0) + 1
 
     def _param_stamp(self):
-        st = []
-        for conv, bn, _ in self.layers:
-            ts = [conv.weight, conv.bias] + ([bn.running_mean, bn.running_var, bn.weight, bn.bias] if bn is not None else [])
-            st.append(tuple((t.data_ptr(), t._version) for t in ts if t is not None))
-        return tuple(st)
+        return stamp_of(t for conv, bn, _ in self.layers for t in
+                        (conv.weight, conv.bias) + ((bn.running_mean, bn.running_var, bn.weight, bn.bias) if bn is not None else ()))
 
     def sync_weights(self):
         """Upload folded parameters if any module tensor changed since the last upload."""
@@ -442,7 +440,7 @@ class BackbonePlan(object):
                                                        0 if bf16_nhwc else L.ptr(out), L.ptr(out) if bf16_nhwc else 0,
                                                        L.stream_ptr()), "backbone_train_forward")
             # the kernels updated the running statistics through raw pointers: bump the tensors' version counters so that every
-            # cache keyed on (data_ptr, _version) -- folded BatchNorm of the inference plans -- sees the change even when no
+            # cache keyed on the tensors' stamps (stamp.py) -- folded BatchNorm of the inference plans -- sees the change even when no
             # optimizer step follows (statistics-only passes, skipped steps)
             stats = [t for _, bn, _ in self.layers if bn.track_running_stats and bn.running_mean is not None
                      for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
@@ -766,7 +764,7 @@ class DenseHeadPlan(object):
         if self.head is not None:
             from .detector.proposal import fused_convs
             tensors += [t for c in fused_convs(self.head) for t in (c.weight, c.bias)]
-        return tuple((t.data_ptr(), t._version) for t in tensors) + (self.precision,)
+        return stamp_of(tensors, self.precision)
 
     def weights_changed(self):
         """True when a module tensor changed since the last upload: the packed images (new tensors) are then stale -- a captured

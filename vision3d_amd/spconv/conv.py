@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from .. import _lib as L
+from ..stamp import cached
 from .tensor import Rulebook, SparseConvTensor
 
 
@@ -155,14 +156,12 @@ class _SparseConvBase(nn.Module):
     def _packed_weight(self, precision="bf16x3"):
         """Split/packed weight image, cached ON THE MODULE and refreshed when the parameter (or the arithmetic) changes."""
         w = self.weight
-        stamp = (w.data_ptr(), w._version, str(w.device), precision)
-        cache = self.__dict__.get("_pack_cache")
-        if cache is None or cache[0] != stamp:
+
+        def build():
             k = self.kernel_size[0] * self.kernel_size[1] * self.kernel_size[2]
             flat = w.detach().to(torch.float32).reshape(k, self.in_channels, self.out_channels).contiguous()
-            cache = (stamp, pack_sparse_weight(flat, k, self.in_channels, self.out_channels, precision))
-            self.__dict__["_pack_cache"] = cache
-        return cache[1]
+            return pack_sparse_weight(flat, k, self.in_channels, self.out_channels, precision)
+        return cached(self, "_pack_cache", (w,), build, extra=(str(w.device), precision))
 
     def rulebook(self, x):
         rb = x.indice_dict.get(("prebuilt", id(self)))  # training pre-pass (modules.prebuild_rulebooks)

@@ -4,9 +4,12 @@ the SparseConvTensor, plain nn.Modules are applied to `.features` (detector/spar
 In eval mode the pattern [sparse conv, BatchNorm1d, ReLU] is executed as ONE kernel launch: the
 batch-norm is folded to a per-channel scale/shift in the conv epilogue together with the ReLU.
 """
+import os
+
 import torch
 from torch import nn
 
+from ..stamp import cached
 from .conv import _SparseConvBase
 from .tensor import SparseConvTensor
 
@@ -21,13 +24,8 @@ def fold_batchnorm(bn):
     return scale.contiguous(), shift.contiguous()
 
 
-import os
-
 # training-mode BatchNorm1d + ReLU on sparse features: csrc/sparse_bn.hip ("fused") or the torch modules ("torch")
 FUSED_TRAINING_BN = os.environ.get("V3D_SPARSE_BN", "fused") == "fused"
-
-
-import os
 
 
 def prebuild_rulebooks(root, x):
@@ -60,16 +58,9 @@ def prebuild_rulebooks(root, x):
 class SparseSequential(nn.Sequential):
 
     def _folded(self, bn):
-        """Folded (scale, shift) of an eval-mode BatchNorm, cached until one of its tensors changes
-        (tensor._version is bumped by every in-place update, load_state_dict included)."""
-        cache = self.__dict__.setdefault("_fold_cache", {})
+        """Folded (scale, shift) of an eval-mode BatchNorm, cached until one of its tensors changes (stamp.py)."""
         tensors = (bn.running_mean, bn.running_var, bn.weight, bn.bias)
-        stamp = tuple((t.data_ptr(), t._version) for t in tensors if t is not None) + (bn.eps,)
-        hit = cache.get(id(bn))
-        if hit is None or hit[0] != stamp:
-            hit = (stamp,) + fold_batchnorm(bn)
-            cache[id(bn)] = hit
-        return hit[1], hit[2]
+        return cached(self, "_fold_cache", tensors, lambda: fold_batchnorm(bn), id(bn), (bn.eps,))
 
     def forward(self, x):
         mods = list(self._modules.values())
