@@ -101,6 +101,23 @@ int v3d_proposals_dir_flag(const float* head_maps, const float* anchors, int B, 
                            void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset);
 int v3d_proposals_dir_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                            float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset);
+/* The same two calls for a head with an IoU-aware confidence logit (cfg.IOU_HEAD of vision3d_amd/detector/proposal.py; the rectified
+ * score of CIA-SSD / SECOND-IoU, which upstream's ProposalLayer does not have): head_maps (B, n_cls*n_yaw*(9 + with_dir), H, W) =
+ * [cls | reg | (dir) | iou], the IoU logit of anchor (c, yaw) in channel n_cls*n_yaw*(8 + with_dir) + c*n_yaw + yaw.  They replace the
+ * score of proposal.py:61-80 (the sigmoid class score) BEHIND the top-k selection, which still runs on the class score, by
+ *   s' = s * q^iou_power,  q = 1 / (1 + exp(-z)) of the candidate's IoU logit z (NaN counts as -inf), iou_power in 0 .. 8 as that many
+ *   successive fp32 multiplications from the left; sentinel rows (s < 0) keep their score;
+ * sort, NMS order, score cut and returned scores use s', ties fall to the position in the class-score order.  iou_power = 0 reads no
+ * IoU logit.  with_dir != 0: the direction rule of v3d_proposals_dir_* applies as well (else dir_offset is ignored).  _iou_flag replaces
+ * v3d_proposals_flag / v3d_proposals_dir_flag, _iou_topk replaces v3d_proposals_topk / v3d_proposals_dir_topk and returns the candidates
+ * of a group in the order of s'.  Launches and workspace are theirs. */
+int v3d_proposals_iou_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                           const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                           int64_t* out_class_idx, float* out_scores, int32_t* n_out /*[2]*/, const int32_t* aux_flag,
+                           void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset, int with_dir, int iou_power);
+int v3d_proposals_iou_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                           float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset,
+                           int with_dir, int iou_power);
 /* Stage-2 tail on candidates in that layout: refined = core/box_encode.py:13-21 decode of `deltas` against `proposals` (written to
  * `refined` (N, 7) when not NULL), score = sigmoid(conf), coordinate-offset batched rotated NMS per (frame, class) group
  * (ops/iou_nms.py:90-134), per-class score cut; outputs as v3d_proposals (padded to N rows, decreasing score, *n_out valid).
@@ -711,6 +728,25 @@ int v3d_proposal_dir_loss_fwd_bwd(const float* maps, const int8_t* g_cls, const 
                                   float* losses, float* dmaps, void* workspace, size_t workspace_bytes, v3d_stream_t stream);
 int v3d_proposal_dir_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
                                 const float* g_dir, const float* one, v3d_stream_t stream);
+
+/* The same loss for a head with an IoU-aware confidence logit (cfg.IOU_HEAD; replaces ProposalLoss.forward of
+ * vision3d_amd/detector/proposal.py with IOU_HEAD enabled -- upstream's detector/proposal.py:100-141 has no such term): maps
+ * (B, n_cls * n_yaw * (9 + with_dir), H, W) = [cls | reg | (dir) | iou], with_dir = (g_dir != NULL); anchors (n_cls, n_yaw, H, W, 7).
+ * cls_loss, reg_loss and dir_loss are bit for bit those of v3d_proposal_loss_fwd_bwd / v3d_proposal_dir_loss_fwd_bwd on the same channels.
+ * iou_loss = sum over M_reg of max(z, 0) - z t + log1p(exp(-|z|)) / max(#M_reg, 1), z the IoU logit and t = clamp(IoU3D(P, G), 0, 1) a
+ * constant: the rotated 3-D IoU of v3d_iou3d_loss_fwd_bwd between the boxes decoded from the predicted residuals and from g_reg, both
+ * RELATIVE to the anchor's centre (xyz = d * (diag, diag, a_h), wlh = exp(d) * a_wlh, yaw = d + a_yaw); gradient (sigmoid(z) - t) /
+ * normalizer in the IoU channels at M_reg, exactly 0 elsewhere, none in the box channels.  losses[5] = cls_loss, reg_loss, dir_loss (0
+ * without the group), iou_loss, normalizer; dmaps = all gradients in their channel groups; iou_target (nullable; B * n_cls * n_yaw * H * W)
+ * = t at M_reg, 0 elsewhere.  _scale multiplies the four (three: g_dir NULL) groups with their upstream gradients (device scalars; one:
+ * a device 1.0f).  fp32, no float atomics, bit-repeatable, no host read. */
+size_t v3d_proposal_iou_loss_workspace(void);
+int v3d_proposal_iou_loss_fwd_bwd(const float* maps, const float* anchors, const int8_t* g_cls, const uint8_t* m_cls, const float* g_reg,
+                                  const uint8_t* m_reg, const int8_t* g_dir /*NULL: no direction group*/, int sin_yaw, int B, int n_cls,
+                                  int n_yaw, int H, int W, float alpha, float gamma, float* losses, float* dmaps, float* iou_target,
+                                  void* workspace, size_t workspace_bytes, v3d_stream_t stream);
+int v3d_proposal_iou_loss_scale(float* dmaps, int B, int n_cls, int n_yaw, int H, int W, const float* g_cls, const float* g_reg,
+                                const float* g_dir /*NULL: no direction group*/, const float* g_iou, const float* one, v3d_stream_t stream);
 
 /* ---- RefinementLoss (PV-RCNN stage 2; this repository's definition, tests/refine_targets_ref.py) and its gradient in ONE launch.
  * rows = B * n RoIs.  R_reg: 7 residuals per row, row stride ld_reg floats; R_cls: one confidence logit per row, stride ld_cls

@@ -32,6 +32,8 @@ _SIGNATURES = {
     "v3d_proposals_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "v3d_proposals_dir_flag": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _f]),
     "v3d_proposals_dir_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _f]),
+    "v3d_proposals_iou_flag": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _f, _i, _i]),
+    "v3d_proposals_iou_topk": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _f, _i, _i]),
     "v3d_refine_nms_workspace": (_sz, [_i, _i, _i]),
     "v3d_refine_nms": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_sparse_bn_workspace": (_sz, [_i, _i]),
@@ -131,6 +133,9 @@ _SIGNATURES = {
     "v3d_proposal_dir_loss_workspace": (_sz, []),
     "v3d_proposal_dir_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "v3d_proposal_dir_loss_scale": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "v3d_proposal_iou_loss_workspace": (_sz, []),
+    "v3d_proposal_iou_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "v3d_proposal_iou_loss_scale": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_refine_targets": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _f, _f, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_fwd_bwd": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_refine_loss_scale": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -104,6 +104,12 @@ def _defaults():
         # > 0].  SIN_YAW: the yaw column of the box loss takes sin(P_yaw - G_yaw) as its smooth-L1 argument (no cliff between residuals 0
         # and pi).  The default OFFSET puts the bin edges on the diagonals, away from the axis-aligned headings and both anchor yaws
         DIRECTION=dict(ENABLED=False, OFFSET=0.7853981634, SIN_YAW=True, LOSS_WEIGHT=0.2),
+        # IoU-aware confidence for the anchor head (detector/proposal.py; the rectified score of CIA-SSD / SE-SSD / SECOND-IoU, not in the
+        # reference), opt-in: one more logit per anchor predicts the rotated 3-D IoU of the anchor's decoded box with its object -- target
+        # (positives only, a constant) = clamp(IoU3D(decode(P_reg), decode(G_reg)), 0, 1), loss = soft-target BCE-with-logits over the
+        # positives / max(#positives, 1) times LOSS_WEIGHT; inference picks the TOPK of a (frame, class) by class score as before, then
+        # ranks, suppresses and cuts by score * sigmoid(logit)^POWER (POWER an integer in 0 .. 8; 0: train the head, leave the scores alone)
+        IOU_HEAD=dict(ENABLED=False, LOSS_WEIGHT=1.0, POWER=4),
         # pillar feature encoder for SECOND (detector/pillar.py; the PFN layer of PointPillars, not in the reference), opt-in: with a voxel
         # as tall as the grid the voxelizer's slots are pillars; every point becomes [channels | xyz - pillar mean | xyz - pillar centre],
         # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
@@ -177,6 +183,16 @@ def dynamic_voxel_config(cfg):
 
 def dynamic_voxel_enabled(cfg):
     return bool(dynamic_voxel_config(cfg)["ENABLED"])
+
+
+IOU_HEAD_DEFAULTS = dict(ENABLED=False, LOSS_WEIGHT=1.0, POWER=4)
+
+
+def iou_head_config(cfg):
+    """-> the keys of cfg.IOU_HEAD over their defaults (a config written before the key existed means "disabled")."""
+    out = dict(IOU_HEAD_DEFAULTS)
+    out.update(cfg.get("IOU_HEAD") or {})
+    return out
 
 
 def refuse_dynamic_with_pillar(cfg):

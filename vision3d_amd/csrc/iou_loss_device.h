@@ -17,7 +17,8 @@
 // Area: rectangle a is clipped by the four half-planes of b (Sutherland-Hodgman); every output edge carries the label of the
 // rectangle edge it lies on (0-3: edge of a, 4-7: edge of b), eight 4-bit labels in one register.  A convex polygon gains at most
 // one vertex per half-plane: <= 8 vertices, and every store is bounded by 8 whatever the inputs (a NaN distance compares as
-// "outside": such a vertex is dropped).  The area is the shoelace sum.
+// "outside": such a vertex is dropped).  The vertices outside a half-plane are held to one run (il_one_run), which keeps that count
+// where edges coincide and rounding decides the signs.  The area is the shoelace sum.
 // Gradient: dA / dp = sum over the polygon's edges of length * (n . velocity of the edge's midpoint under p), p a parameter of the
 // box that OWNS the edge, n the owner edge's outward normal: (1, 0) / (0, 1) for the centre, half the length for the size the
 // edge bounds, length * (m x n) for the yaw (m = midpoint - owner's centre).  The velocity is affine along an edge, so the
@@ -36,6 +37,22 @@ namespace v3d {
 
 V3D_HD bool il_finite(float x) { return fabsf(x) <= 3.4028235e38f; }  // false for NaN and +-Inf
 
+// A convex polygon has ONE run of vertices outside a half-plane.  Where edges coincide (identical boxes, a shared face) the distances
+// of the vertices on the boundary are rounding noise of either sign, and their signs can spell several runs -- in, out, in, out --
+// each of which would add a vertex, past the eight a polygon may hold (dropped vertices: an IoU of 0.33 for two identical boxes).
+// out: bit i = vertex i lies outside; seed: the vertex farthest outside (and every vertex whose distance is NaN).  -> the bits of the
+// runs that hold a seed; the vertices of the other runs count as inside.  One run: `out` itself, so no decision of a pair in general
+// position changes.
+V3D_HD uint32_t il_one_run(uint32_t out, uint32_t seed, int n) {
+  const uint32_t full = (1u << n) - 1u;
+  uint32_t reach = seed & out;
+  for (int k = 1; k < V3D_IOU_LOSS_POLY; k++) {
+    const uint32_t up = ((reach << 1) | (reach >> (n - 1))) & full, down = ((reach >> 1) | (reach << (n - 1))) & full;
+    reach |= out & (up | down);
+  }
+  return reach;
+}
+
 // Clip polygon `in` (n vertices, labels lab_in: label i = the edge from vertex i to vertex i + 1) by the half-plane
 // n . (p - c) <= h whose boundary carries label `own`; -> the vertex count, at most 8.
 template <class A>
@@ -44,13 +61,32 @@ V3D_HD int il_clip(A in, int n, uint32_t lab_in, A out, uint32_t& lab_out, float
   uint32_t lo = 0u;
   if (n > V3D_IOU_LOSS_POLY) n = V3D_IOU_LOSS_POLY;
   if (n > 0) {
+    uint32_t outside = 0u, seed = 0u;  // a vertex is inside where d <= 0 (NaN: outside)
+    float d_far = 0.f;
+    int far = -1;
+    for (int i = 0; i < n; i++) {
+      const P2 p = in[i];
+      const float d = (nx * (p.x - cx) + ny * (p.y - cy)) - h;
+      if (!(d <= 0.f)) {
+        outside |= 1u << i;
+        if (d != d) {
+          seed |= 1u << i;
+        } else if (far < 0 || d > d_far) {
+          far = i;
+          d_far = d;
+        }
+      }
+    }
+    if (far >= 0) seed |= 1u << far;
+    outside = il_one_run(outside, seed, n);
     P2 cur = in[0];
     float dc = (nx * (cur.x - cx) + ny * (cur.y - cy)) - h;
     for (int i = 0; i < n; i++) {
-      const P2 nxt = in[i + 1 < n ? i + 1 : 0];
+      const int i_n = i + 1 < n ? i + 1 : 0;
+      const P2 nxt = in[i_n];
       const float dn = (nx * (nxt.x - cx) + ny * (nxt.y - cy)) - h;
       const uint32_t lab = (lab_in >> (4 * i)) & 7u;
-      const bool ic = dc <= 0.f, in_n = dn <= 0.f;  // NaN: outside
+      const bool ic = ((outside >> i) & 1u) == 0u, in_n = ((outside >> i_n) & 1u) == 0u;
       if (ic && m < V3D_IOU_LOSS_POLY) {
         out[m] = cur;
         lo |= lab << (4 * m);

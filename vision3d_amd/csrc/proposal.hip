@@ -40,6 +40,9 @@ struct PropGeom {
   float thresh[PROP_MAX_CLS];
   int dir_base;      // first direction channel (n_cls*n_yaw*8: v3d_proposals_dir_*), -1 = the head has none
   float dir_offset;  // cfg.DIRECTION.OFFSET
+  int iou_base;      // first IoU-confidence channel (n_cls*n_yaw*(8 + with_dir): v3d_proposals_iou_*), -1 = the head has none
+  int iou_power;     // cfg.IOU_HEAD.POWER in 0 .. 8; 0 = the channel is never read
+  int iou_order;     // != 0 (v3d_proposals_iou_topk with a power): the decoded candidates are stored in the order of s' inside a group
 };
 
 // Yaw of a head with a direction classifier (cfg.DIRECTION): raw = anchor yaw + residual is right modulo pi (the sine loss leaves the
@@ -53,6 +56,15 @@ __device__ __forceinline__ float prop_dir_yaw(float raw, float offset, float dir
 }
 
 __device__ __forceinline__ float prop_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }  // torch: 1 / (1 + exp(-x))
+// The rectified score of a head with an IoU-aware confidence logit (cfg.IOU_HEAD): s' = s * q^power, q = prop_sigmoid(z), the power as
+// `power` successive fp32 multiplications from the left (((s q) q) ...): no powf.  A NaN logit counts as -inf (q = 0), the rule of
+// the class logit.  Sentinel candidates (s < 0) are not the caller's to pass.
+__device__ __forceinline__ float prop_rectify(float s, float z, int power) {
+  const float q = prop_sigmoid(z != z ? -INFINITY : z);
+  for (int k = 0; k < power; k++) s = s * q;
+  return s;
+}
+
 __device__ __forceinline__ unsigned prop_logit_key(float x) {                               // order-preserving
   const unsigned u = __float_as_uint(x);
   return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
@@ -295,7 +307,7 @@ __global__ __launch_bounds__(SEL_THREADS) void prop_topk_merge_kernel(const floa
 // from arrays in candidate order instead of the head maps / anchor grid, the score is the sigmoid of a confidence logit.
 template <bool REFINE>
 __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ maps, const float* __restrict__ anchors,
-                                                      const PropGeom& g, const int* cand_anchor, const float* cand_score,
+                                                      const PropGeom& g, const int* cand_anchor, float* cand_score,
                                                       float* __restrict__ boxes /*(N,7)*/, long long* __restrict__ batch_idx,
                                                       long long* __restrict__ class_idx, int* __restrict__ order,
                                                       v3d::BoxPrep* __restrict__ prep, const float* __restrict__ ref_deltas = nullptr,
@@ -310,6 +322,20 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
   float hi = -INFINITY, lo = INFINITY;
   float o[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int grp = 0;
+  if constexpr (!REFINE) {
+    // cfg.IOU_HEAD: a real candidate's class score becomes s' = s * sigmoid(IoU logit)^power, stored back: the sort below and the
+    // score cut of the last launch read cand_score.  Kernel arguments: the branch is uniform.  (Rows [0, N) of cand_score /
+    // cand_anchor were written before this body runs, by an earlier launch or in front of a barrier of this workgroup; thread t
+    // alone reads and writes row t.)
+    if (g.iou_base >= 0 && g.iou_power > 0 && t < N) {
+      const float s = cand_score[t];
+      if (s >= 0.f) {
+        const int gr = t / g.topk, b = gr / g.n_cls, c = gr % g.n_cls;
+        const int a = min(max(cand_anchor[t], 0), g.n_yaw * g.HW - 1), yaw_i = a / g.HW, pix = a % g.HW;
+        cand_score[t] = prop_rectify(s, maps[((size_t)b * g.ctot + g.iou_base + (size_t)c * g.n_yaw + yaw_i) * g.HW + pix], g.iou_power);
+      }
+    }
+  }
   if (t < N) {
     grp = t / g.topk;
     const int b = grp / g.n_cls, c = grp % g.n_cls;
@@ -344,10 +370,12 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
         o[6] = prop_dir_yaw(o[6], g.dir_offset, maps[((size_t)b * g.ctot + g.dir_base + (size_t)c * g.n_yaw + yaw_i) * g.HW + pix]);
       }
     }
+    if (REFINE || !g.iou_order) {
 #pragma unroll
-    for (int q = 0; q < 7; q++) boxes[(size_t)t * 7 + q] = o[q];
-    batch_idx[t] = b;
-    class_idx[t] = c;
+      for (int q = 0; q < 7; q++) boxes[(size_t)t * 7 + q] = o[q];
+      batch_idx[t] = b;
+      class_idx[t] = c;
+    }
     hi = fmaxf(o[0], o[1]) + fmaxf(o[3], o[4]) / 2.f;
     lo = fminf(o[0], o[1]) - fminf(o[3], o[4]) / 2.f;
   }
@@ -368,8 +396,8 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
   sbev[t][4] = o[6];
   // key = (~orderable(score) << 32) | index, ascending == the order v3d_nms_rotated sorts in; padding sorts last
   unsigned long long key = ~0ull;
+  float sc = 0.f;
   if (t < N) {
-    float sc;
     if constexpr (REFINE) {
       sc = prop_sigmoid(ref_conf[t]);
       ref_score[t] = sc;
@@ -382,6 +410,24 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
   }
   keys[t] = key;
   __syncthreads();
+  if constexpr (!REFINE) {
+    // v3d_proposals_iou_topk: the candidates leave in the order of s' inside their group (ties: the position in the class-score
+    // order, which the key carries) -- candidate t goes to the row of its rank among its group's keys.  Every cand_score[t] was
+    // read in front of the barrier above.  (order / prep below still speak of the rows before the move: that entry stops behind
+    // this kernel and reads neither.)
+    if (g.iou_order) {
+      if (t < N) {
+        int r = 0;
+        for (int j = grp * g.topk; j < (grp + 1) * g.topk; j++) r += keys[j] < key ? 1 : 0;
+        const size_t dst = (size_t)grp * g.topk + r;
+#pragma unroll
+        for (int q = 0; q < 7; q++) boxes[dst * 7 + q] = o[q];
+        batch_idx[dst] = grp / g.n_cls;
+        class_idx[dst] = grp % g.n_cls;
+        cand_score[dst] = sc;
+      }
+    }
+  }
   int npad = 1;
   while (npad < N) npad <<= 1;
   if (npad <= PROP_RANK_SORT_MAX) {
@@ -426,7 +472,7 @@ __device__ __forceinline__ void prop_decode_sort_body(const float* __restrict__ 
 __global__ __launch_bounds__(PROP_THREADS) void prop_decode_sort_kernel(const float* __restrict__ maps,
                                                                         const float* __restrict__ anchors, PropGeom g,
                                                                         const int* __restrict__ cand_anchor,
-                                                                        const float* __restrict__ cand_score,
+                                                                        float* __restrict__ cand_score,
                                                                         float* __restrict__ boxes, long long* __restrict__ batch_idx,
                                                                         long long* __restrict__ class_idx, int* __restrict__ order,
                                                                         v3d::BoxPrep* __restrict__ prep) {
@@ -563,7 +609,7 @@ extern "C" int v3d_proposals(const float* head_maps, const float* anchors, int B
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores, bool dir = false, float dir_offset = 0.f);
+                    float* topk_boxes, float* topk_scores, bool dir = false, float dir_offset = 0.f, bool iou = false, int iou_power = 0);
 
 extern "C" int v3d_proposals_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W,
                                   int topk, const float* score_thresh_host, float iou_threshold, float* out_boxes,
@@ -601,20 +647,48 @@ extern "C" int v3d_proposals_dir_topk(const float* head_maps, const float* ancho
                   workspace_bytes, stream, boxes, scores, true, dir_offset);
 }
 
+// The two entry points for a head with an IoU-aware confidence logit (cfg.IOU_HEAD): head_maps (B, n_cls*n_yaw*(9 + with_dir), H, W) =
+// [cls | reg | (dir) | iou], the IoU logit of anchor (c, yaw) in channel n_cls*n_yaw*(8 + with_dir) + c*n_yaw + yaw.  The TOPK candidates
+// of a group are chosen by class score exactly as before (levels 1 and 2 are untouched); a real candidate then takes s' = s * q^iou_power,
+// q = sigmoid(IoU logit) (prop_rectify), and the sort, the NMS order, the score cut and the returned scores use s'.  with_dir = 0:
+// dir_offset is ignored.  iou_power = 0: the channel is not read and every output has the bits of the entry without it.  Same launches.
+extern "C" int v3d_proposals_iou_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                                      const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                                      int64_t* out_class_idx, float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace,
+                                      size_t workspace_bytes, v3d_stream_t stream, float dir_offset, int with_dir, int iou_power) {
+  if (!score_thresh_host || !out_boxes || !out_batch_idx || !out_class_idx || !out_scores || !n_out) return V3D_EINVAL;
+  return prop_run(head_maps, anchors, B, n_cls, n_yaw, H, W, topk, score_thresh_host, iou_threshold, out_boxes, out_batch_idx, out_class_idx,
+                  out_scores, n_out, aux_flag, workspace, workspace_bytes, stream, nullptr, nullptr, with_dir != 0, dir_offset, true, iou_power);
+}
+
+// ... and the decoded candidates before NMS: in the order of s' inside a group (ties: position in the class-score order), scores = s'.
+extern "C" int v3d_proposals_iou_topk(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                                      float* boxes, float* scores, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
+                                      float dir_offset, int with_dir, int iou_power) {
+  if (!boxes || !scores) return V3D_EINVAL;
+  return prop_run(head_maps, anchors, B, n_cls, n_yaw, H, W, topk, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
+                  workspace_bytes, stream, boxes, scores, with_dir != 0, dir_offset, true, iou_power);
+}
+
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores, bool dir, float dir_offset) {
+                    float* topk_boxes, float* topk_scores, bool dir, float dir_offset, bool iou, int iou_power) {
   hipStream_t st = (hipStream_t)stream;
   if (!head_maps || !anchors || !workspace) return V3D_EINVAL;
   if (B < 1 || n_cls < 1 || n_cls > PROP_MAX_CLS || n_yaw < 1 || H < 1 || W < 1 || topk < 1 || topk > PROP_MAX_TOPK)
     return V3D_EINVAL;
   if ((long long)B * n_cls * topk > PROP_THREADS) return V3D_EUNSUPPORTED;  // candidates of ALL groups are sorted by one block
-  if ((long long)n_yaw * H * W < topk) return V3D_EINVAL;  // torch.topk raises as well
+  // torch.topk raises as well.  (The cfg.IOU_HEAD entries take such a map: both selection levels pad a short range with (score -1,
+  // anchor -1) sentinels, which keep their score, decode the clamped anchor 0, sort last and fall at the score cut.)
+  if ((long long)n_yaw * H * W < topk && !iou) return V3D_EINVAL;
   if (workspace_bytes < v3d_proposals_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
   PropGeom g;
-  g.B = B; g.n_cls = n_cls; g.n_yaw = n_yaw; g.HW = H * W; g.topk = topk; g.ctot = n_cls * n_yaw * (dir ? 9 : 8);
+  if (iou && (iou_power < 0 || iou_power > 8)) return V3D_EINVAL;
+  g.B = B; g.n_cls = n_cls; g.n_yaw = n_yaw; g.HW = H * W; g.topk = topk; g.ctot = n_cls * n_yaw * ((dir ? 9 : 8) + (iou ? 1 : 0));
   g.dir_base = dir ? n_cls * n_yaw * 8 : -1; g.dir_offset = dir_offset;
+  g.iou_base = iou ? n_cls * n_yaw * (dir ? 9 : 8) : -1; g.iou_power = iou ? iou_power : 0;
+  g.iou_order = iou && iou_power > 0 && topk_boxes ? 1 : 0;
   for (int c = 0; c < PROP_MAX_CLS; c++) g.thresh[c] = (c < n_cls && score_thresh_host) ? score_thresh_host[c] : 0.f;
   const size_t N = (size_t)B * n_cls * topk;
   char* p = (char*)workspace;
@@ -692,6 +766,7 @@ extern "C" int v3d_refine_nms(const float* deltas, const float* proposals, const
   if (workspace_bytes < v3d_refine_nms_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
   PropGeom g;
   g.B = B; g.n_cls = n_cls; g.n_yaw = 1; g.HW = 1; g.topk = topk; g.ctot = 0; g.dir_base = -1; g.dir_offset = 0.f;
+  g.iou_base = -1; g.iou_power = 0; g.iou_order = 0;
   for (int c = 0; c < PROP_MAX_CLS; c++) g.thresh[c] = c < n_cls ? score_thresh_host[c] : 0.f;
   const size_t N = (size_t)B * n_cls * topk;
   char* p = (char*)workspace;

@@ -94,7 +94,8 @@ def why_unsupported(rpn, head, bev, precision="bf16"):
                 or off_device(conv.bias)):
             return "head parameters are not fp32 tensors on the input's device"
     width = sum(conv.out_channels for conv in fused_convs(head))
-    if width not in (8, 16, 24, 32, 48, 64):  # (18 and 54, a head with a direction classifier, among them: it trains through torch)
+    # (18 and 54, a head with a direction classifier, and 18 / 20 / 54 / 60, one with an IoU confidence, among them: they train through torch)
+    if width not in (8, 16, 24, 32, 48, 64):
         return f"fused head width {width} is not one of 8, 16, 24, 32, 48, 64"
     if precision == "bf16x3" and width > 16:
         return "fused head wider than 16 channels (the split path's head kernel)"

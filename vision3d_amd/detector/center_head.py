@@ -87,6 +87,8 @@ class CenterHead(nn.Module):
                              "not take the centre head yet")
         from .proposal import refuse_direction
         refuse_direction(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED regresses sin / cos of the yaw itself)")
+        from .proposal import refuse_iou_head
+        refuse_iou_head(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED has no anchors to rate)")
         self.cfg = cfg
         self.opt = centerhead_config(cfg)
         if len(self.opt["CODE_WEIGHTS"]) != 8:

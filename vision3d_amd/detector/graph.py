@@ -68,7 +68,7 @@ class GraphedSecond(object):
         self.native = head.native_supported(len(self.frame_sizes), self.anchors.numel() // (7 * self.model.cfg.NUM_CLASSES))
         if self.native:
             return head.native_proposals(maps, self.anchors, self.plan.overflow_any(), host_out=self.host_out)
-        return head.proposals_padded(*head.maps_from_fused(maps), self.anchors, head.dir_from_fused(maps))
+        return head.proposals_padded(*head.maps_from_fused(maps), self.anchors, *head.extra_from_fused(maps))
 
     def load(self, clouds):
         if len(clouds) != len(self.frame_sizes):

@@ -48,6 +48,7 @@ class PV_RCNN(nn.Module):
         from .center_head import refuse_centerhead
         refuse_centerhead(cfg, "PV_RCNN")
         proposal.refuse_direction(cfg, "PV_RCNN (stage 2 refines the yaw it is given)")
+        proposal.refuse_iou_head(cfg, "PV_RCNN (stage 2 regresses its own IoU-guided confidence)")
         from .pillar import refuse_pillar
         refuse_pillar(cfg, "PV_RCNN (its keypoints read the sparse backbone's levels)")
         self.cfg = cfg

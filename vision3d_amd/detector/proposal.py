@@ -9,6 +9,12 @@ cfg.DIRECTION (opt-in, not in the reference): the direction classifier and sine 
 residual is right only modulo pi; one more 1x1 head, conv_dir, gives a logit per anchor that says which half turn (fused map
 [cls | reg | dir], forward returns a third map, the decode applies `direction_yaw`), ProposalLoss gains dir_loss and, with SIN_YAW,
 takes sin(P_yaw - G_yaw) as the yaw column's smooth-L1 argument.  Definition: DESIGN.md section 7, tests/direction_ref.py.
+
+cfg.IOU_HEAD (opt-in, not in the reference): an IoU-aware confidence, the rectified score of CIA-SSD / SE-SSD / SECOND-IoU.  One more
+1x1 head, conv_iou, gives a logit per anchor (fused map [cls | reg | (dir) | iou], forward returns one more map behind the direction
+map) trained towards the rotated 3-D IoU of the anchor's decoded box with its object (ProposalLoss.iou_targets, iou_loss); inference
+selects the TOPK of a (frame, class) by class score as before and then ranks, suppresses and cuts by `rectified_scores`.
+Definition: DESIGN.md section 7, tests/iou_head_ref.py.
 """
 import math
 
@@ -18,6 +24,7 @@ from torch import nn
 
 from .. import _lib as L
 from ..core.box_encode import decode
+from ..core.config import iou_head_config
 from ..core.proposal_targets import direction_config
 from ..ops import batched_nms_rotated, batched_nms_rotated_padded, sigmoid_focal_loss
 from ..stamp import cached
@@ -35,13 +42,58 @@ def refuse_direction(cfg, what):
                          "does)")
 
 
+def iou_head_enabled(cfg):
+    return bool(iou_head_config(cfg)["ENABLED"])
+
+
+def refuse_iou_head(cfg, what):
+    """The models that have no use for the IoU-aware confidence say so instead of building a head that ignores the key."""
+    if iou_head_enabled(cfg):
+        raise ValueError(f"cfg.IOU_HEAD.ENABLED: {what} does not take the IoU-aware confidence head (Second with the anchor head does)")
+
+
+def checked_iou_head(cfg):
+    """cfg.IOU_HEAD over its defaults, refused where an enabled head could not mean what it says."""
+    opt = iou_head_config(cfg)
+    if opt["ENABLED"]:
+        power = opt["POWER"]
+        if isinstance(power, bool) or not isinstance(power, int) or not 0 <= power <= 8:
+            raise ValueError(f"cfg.IOU_HEAD.POWER must be an integer in 0 .. 8 (0: the scores stay as they are), got {power!r}")
+        if cfg.BOX_DOF != 7:
+            raise ValueError("cfg.IOU_HEAD.ENABLED: the IoU target is defined for 7-DOF boxes (cfg.BOX_DOF)")
+    return opt
+
+
 def fused_convs(head):
-    """The 1x1 convolutions of a head in the channel order of its fused map: [conv_cls | conv_reg], and [conv_cls | conv_reg | conv_dir]
-    for a ProposalLayer with a direction classifier.  The one statement of that order for runtime.DenseHeadPlan,
-    ProposalLayer.native_head and dense_train.DenseTrainPlan."""
+    """The 1x1 convolutions of a head in the channel order of its fused map: [conv_cls | conv_reg], then conv_dir for a ProposalLayer
+    with a direction classifier, then conv_iou for one with an IoU-aware confidence: [cls | reg | (dir) | (iou)].  The one statement of
+    that order for runtime.DenseHeadPlan, ProposalLayer.native_head and dense_train.DenseTrainPlan."""
     convs = [head.conv_cls, head.conv_reg]
-    conv_dir = getattr(head, "conv_dir", None)
-    return convs + [conv_dir] if conv_dir is not None else convs
+    for name in ("conv_dir", "conv_iou"):
+        conv = getattr(head, name, None)
+        if conv is not None:
+            convs.append(conv)
+    return convs
+
+
+def rectified_scores(scores, iou_logit, power):
+    """The score rule of cfg.IOU_HEAD: s' = s * q^POWER, q = sigmoid(IoU logit) with NaN counted as -inf (q = 0), the power as POWER
+    successive multiplications from the left; a sentinel (s < 0) keeps its score.  In the dtype of `scores`."""
+    z = iou_logit.to(scores.dtype)
+    q = torch.sigmoid(torch.where(torch.isnan(z), torch.full_like(z, -math.inf), z))
+    out = scores
+    for _ in range(int(power)):
+        out = out * q
+    return torch.where(scores >= 0, out, scores)
+
+
+def relative_boxes(deltas, anchors):
+    """core/box_encode.py:decode WITHOUT the anchor's centre (the IoU is translation invariant; csrc/iou_head_device.h):
+    (d_xyz * (diag, diag, a_h), exp(d_wlh) * a_wlh, d_yaw + a_yaw)."""
+    diag = torch.sqrt(anchors[..., 3] * anchors[..., 3] + anchors[..., 4] * anchors[..., 4])
+    return torch.stack((deltas[..., 0] * diag, deltas[..., 1] * diag, deltas[..., 2] * anchors[..., 5],
+                        torch.exp(deltas[..., 3]) * anchors[..., 3], torch.exp(deltas[..., 4]) * anchors[..., 4],
+                        torch.exp(deltas[..., 5]) * anchors[..., 5], deltas[..., 6] + anchors[..., 6]), -1)
 
 
 def direction_yaw(raw, dir_logit, offset):
@@ -88,6 +140,7 @@ class ProposalLayer(nn.Module):
         self.conv_reg = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor * cfg.BOX_DOF, 1)
         self.TOPK, self.DOF = cfg.PROPOSAL.TOPK, cfg.BOX_DOF
         self.direction = direction_config(cfg)
+        self.iou_head = checked_iou_head(cfg)
         self._init_weights()
         if self.direction["ENABLED"]:
             # cfg.DIRECTION (opt-in): one more logit per anchor, the half turn the wrapped yaw residual cannot carry.  Built behind the
@@ -97,6 +150,12 @@ class ProposalLayer(nn.Module):
             self.conv_dir = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor, 1)
             nn.init.constant_(self.conv_dir.bias, 0)
             nn.init.normal_(self.conv_dir.weight, std=0.01)
+        if self.iou_head["ENABLED"]:
+            # cfg.IOU_HEAD (opt-in): one more logit per anchor, the predicted IoU of its decoded box.  Built behind every other head,
+            # so that their initial values under a seed do not depend on it
+            self.conv_iou = nn.Conv2d(cfg.PROPOSAL.C_IN, n_anchor, 1)
+            nn.init.constant_(self.conv_iou.bias, 0)
+            nn.init.normal_(self.conv_iou.weight, std=0.01)
 
     def _init_weights(self):
         # focal-prior bias exactly as the reference writes it: +1.005 (proposal.py:27)
@@ -134,6 +193,26 @@ class ProposalLayer(nn.Module):
             raise RuntimeError("cfg.DIRECTION.ENABLED: the decode needs the direction map (dir_from_fused) beside the class and box maps")
         return dir_map
 
+    def _split_extra(self, extra):
+        """(dir_map, iou_map) from what follows (cls_map, reg_map) in the outputs of `forward`."""
+        extra = list(extra)
+        dir_map = extra.pop(0) if self.direction["ENABLED"] and extra else None
+        iou_map = extra.pop(0) if self.iou_head["ENABLED"] and extra else None
+        return dir_map, iou_map
+
+    def _rectify(self, scores, anchor_idx, iou_map):
+        """cfg.IOU_HEAD behind the top-k by class score: (scores, anchor_idx) (B, n_cls, TOPK) -> the same candidates with s' =
+        rectified_scores in place of the score, in a stable descending order of s' (ties: the position in the class-score order).
+        A head without the key, and POWER = 0, change nothing and read nothing."""
+        if not self.iou_head["ENABLED"] or self.iou_head["POWER"] == 0:
+            return scores, anchor_idx
+        if iou_map is None:
+            raise RuntimeError("cfg.IOU_HEAD.ENABLED: the proposal stage needs the IoU map (iou_from_fused) beside the class and box maps")
+        B, n_cls = scores.shape[:2]
+        rect = rectified_scores(scores, iou_map.reshape(B, n_cls, -1).gather(2, anchor_idx), self.iou_head["POWER"])
+        rect, order = torch.sort(rect, dim=-1, descending=True, stable=True)
+        return rect, anchor_idx.gather(2, order)
+
     def _decode(self, reg_map, anchors, anchor_idx, dir_map=None):
         B, n_cls = reg_map.shape[:2]
         gidx = anchor_idx[..., None].expand(-1, -1, -1, self.DOF)
@@ -148,11 +227,12 @@ class ProposalLayer(nn.Module):
 
     def inference(self, feature_map, anchors):
         """-> (boxes (K,7), batch_idx (K,), class_idx (K,), scores (K,)), by decreasing score."""
-        maps = self(feature_map)  # (cls_map, reg_map[, dir_map])
-        return self.inference_from_maps(maps[0], maps[1], anchors, *maps[2:])
+        maps = self(feature_map)  # (cls_map, reg_map[, dir_map][, iou_map])
+        return self.inference_from_maps(maps[0], maps[1], anchors, *self._split_extra(maps[2:]))
 
     def maps_from_fused(self, maps):
-        """(B, n_anchor*(1+DOF)[+ n_anchor], H, W) = [cls | reg (| dir)] channels of the fused 1x1 head -> (cls_map, reg_map)."""
+        """(B, n_anchor*(1+DOF)[+ n_anchor][+ n_anchor], H, W) = [cls | reg (| dir) (| iou)] channels of the fused 1x1 head ->
+        (cls_map, reg_map)."""
         n_anchor = self.cfg.NUM_CLASSES * self.cfg.NUM_YAW
         return (self.reshape_cls(maps[:, :n_anchor].contiguous()),
                 self.reshape_reg(maps[:, n_anchor:n_anchor * (1 + self.DOF)].contiguous()))
@@ -161,16 +241,29 @@ class ProposalLayer(nn.Module):
         """The direction logits of a fused [cls | reg | dir] map in the shape of cls_map; None for a head without the classifier."""
         if not self.direction["ENABLED"]:
             return None
-        return self.reshape_cls(maps[:, self.cfg.NUM_CLASSES * self.cfg.NUM_YAW * (1 + self.DOF):].contiguous())
+        n_anchor = self.cfg.NUM_CLASSES * self.cfg.NUM_YAW
+        return self.reshape_cls(maps[:, n_anchor * (1 + self.DOF):n_anchor * (2 + self.DOF)].contiguous())
 
-    def proposals_padded(self, cls_map, reg_map, anchors, dir_map=None):
+    def iou_from_fused(self, maps):
+        """The IoU logits of a fused [cls | reg | (dir) | iou] map in the shape of cls_map; None for a head without cfg.IOU_HEAD."""
+        if not self.iou_head["ENABLED"]:
+            return None
+        n_anchor = self.cfg.NUM_CLASSES * self.cfg.NUM_YAW
+        base = n_anchor * (1 + self.DOF + bool(self.direction["ENABLED"]))
+        return self.reshape_cls(maps[:, base:base + n_anchor].contiguous())
+
+    def extra_from_fused(self, maps):
+        """(dir_map, iou_map) of a fused map: what the torch statements take behind (cls_map, reg_map, anchors)."""
+        return self.dir_from_fused(maps), self.iou_from_fused(maps)
+
+    def proposals_padded(self, cls_map, reg_map, anchors, dir_map=None, iou_map=None):
         """Everything up to (and including) NMS with NO host synchronisation: returns the B*n_cls*TOPK
         candidates (boxes, batch_idx, class_idx, scores) plus (keep padded, n_keep) on the device.  This is
         the part that can live inside a captured HIP graph; `finalize` does the variable-length selection.
         For a NaN logit this statement behaves differently from `native_proposals`: torch.topk sorts NaN first, the kernel last."""
         score_map = cls_map.sigmoid()
         B, n_cls = score_map.shape[:2]
-        scores, anchor_idx = score_map.reshape(B, n_cls, -1).topk(self.TOPK, -1)
+        scores, anchor_idx = self._rectify(*score_map.reshape(B, n_cls, -1).topk(self.TOPK, -1), iou_map)
         boxes = self._decode(reg_map, anchors, anchor_idx, dir_map).reshape(-1, self.DOF)
         scores = scores.reshape(-1)
         batch_idx, class_idx, group_idx = self._generate_group_idx(B, n_cls, scores.device)
@@ -204,7 +297,8 @@ class ProposalLayer(nn.Module):
         B, ctot, H, W = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
         with_dir = bool(self.direction["ENABLED"])  # [cls | reg | dir] maps: v3d_proposals_dir_flag applies the direction decode rule
-        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
+        with_iou = bool(self.iou_head["ENABLED"])   # [cls | reg | (dir) | iou] maps: v3d_proposals_iou_flag rectifies the scores
+        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir + with_iou) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
             raise RuntimeError("proposals: head map / anchor grid shapes disagree")
         N = B * n_cls * self.TOPK
         dev = maps.device
@@ -222,6 +316,8 @@ class ProposalLayer(nn.Module):
         ws = L.workspace(lib.v3d_proposals_workspace(B, n_cls, self.TOPK), dev)
         thresh = L.host_f32([a["score_thresh"] for a in cfg.ANCHORS[:n_cls]])
         entry, extra = (lib.v3d_proposals_dir_flag, (float(self.direction["OFFSET"]),)) if with_dir else (lib.v3d_proposals_flag, ())
+        if with_iou:
+            entry, extra = lib.v3d_proposals_iou_flag, (float(self.direction["OFFSET"]), int(with_dir), int(self.iou_head["POWER"]))
         with L.device_guard(dev):
             L.check(entry(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, thresh, 0.01, L.ptr(boxes),
                           L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(overflow_flag),
@@ -236,8 +332,8 @@ class ProposalLayer(nn.Module):
         maps, anc = L.as_f32("proposals_topk", head_maps), L.as_f32("proposals_topk", anchors)
         B, ctot, H, W = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
-        with_dir = bool(self.direction["ENABLED"])
-        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
+        with_dir, with_iou = bool(self.direction["ENABLED"]), bool(self.iou_head["ENABLED"])
+        if ctot != n_cls * n_yaw * (1 + self.DOF + with_dir + with_iou) or self.DOF != 7 or anc.numel() != n_cls * n_yaw * H * W * 7:
             raise RuntimeError("proposals_topk: head map / anchor grid shapes disagree")
         N = B * n_cls * self.TOPK
         boxes = torch.empty((B, n_cls * self.TOPK, 7), dtype=torch.float32, device=maps.device)
@@ -245,6 +341,8 @@ class ProposalLayer(nn.Module):
         lib = L.lib()
         ws = L.workspace(lib.v3d_proposals_workspace(B, n_cls, self.TOPK), maps.device)
         entry, extra = (lib.v3d_proposals_dir_topk, (float(self.direction["OFFSET"]),)) if with_dir else (lib.v3d_proposals_topk, ())
+        if with_iou:  # (the candidates of a group then come in the order of the rectified score, which is what `scores` holds)
+            entry, extra = lib.v3d_proposals_iou_topk, (float(self.direction["OFFSET"]), int(with_dir), int(self.iou_head["POWER"]))
         with L.device_guard(maps.device):
             L.check(entry(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, L.ptr(boxes), L.ptr(scores), L.ptr(ws),
                           ws.numel(), L.stream_ptr(), *extra), "proposals_topk")
@@ -311,7 +409,7 @@ class ProposalLayer(nn.Module):
     def inference_native(self, head_maps, anchors, overflow_flag=None):
         if not self.native_supported(head_maps.shape[0], anchors.numel() // (7 * self.cfg.NUM_CLASSES)):  # too large: op-by-op
             cls_map, reg_map = self.maps_from_fused(head_maps)
-            out = self.inference_from_maps(cls_map, reg_map, anchors, self.dir_from_fused(head_maps))
+            out = self.inference_from_maps(cls_map, reg_map, anchors, *self.extra_from_fused(head_maps))
             if overflow_flag is not None:
                 _raise_on_flag(int(overflow_flag.item()))
             return out
@@ -323,10 +421,10 @@ class ProposalLayer(nn.Module):
         mask = self._above_score_thresh(scores, class_idx)
         return [x[mask] for x in (boxes, batch_idx, class_idx, scores)]
 
-    def inference_from_maps(self, cls_map, reg_map, anchors, dir_map=None):
+    def inference_from_maps(self, cls_map, reg_map, anchors, dir_map=None, iou_map=None):
         score_map = cls_map.sigmoid_()
         B, n_cls = score_map.shape[:2]
-        scores, anchor_idx = score_map.view(B, n_cls, -1).topk(self.TOPK, -1)
+        scores, anchor_idx = self._rectify(*score_map.view(B, n_cls, -1).topk(self.TOPK, -1), iou_map)
         boxes = self._decode(reg_map, anchors, anchor_idx, dir_map)
         return self._multiclass_batch_nms(boxes, scores)
 
@@ -339,20 +437,26 @@ class ProposalLayer(nn.Module):
         return reg_map.view(B, self.cfg.NUM_CLASSES, self.cfg.BOX_DOF, -1, ny, nx).permute(0, 1, 3, 4, 5, 2)
 
     def forward(self, feature_map):
-        """-> (cls_map, reg_map), and (cls_map, reg_map, dir_map) for a head with a direction classifier."""
+        """-> (cls_map, reg_map), then dir_map for a head with a direction classifier, then iou_map for one with cfg.IOU_HEAD."""
         if not self.training and not torch.is_grad_enabled() and feature_map.is_cuda:
             maps = self.native_head(feature_map)  # inference on the GPU: csrc/dense_conv.hip, not MIOpen
-            return self.maps_from_fused(maps) + ((self.dir_from_fused(maps),) if self.direction["ENABLED"] else ())
+            return self.maps_from_fused(maps) + tuple(m for m in self.extra_from_fused(maps) if m is not None)
         out = self.reshape_cls(self.conv_cls(feature_map)), self.reshape_reg(self.conv_reg(feature_map))
-        return out + ((self.reshape_cls(self.conv_dir(feature_map)),) if self.direction["ENABLED"] else ())
+        if self.direction["ENABLED"]:
+            out += (self.reshape_cls(self.conv_dir(feature_map)),)
+        if self.iou_head["ENABLED"]:
+            out += (self.reshape_cls(self.conv_iou(feature_map)),)
+        return out
 
-    def fuse(self, cls_map, reg_map, dir_map=None):
-        """The module outputs back in the fused layout [cls | reg (| dir)] (B, n_anchor * 8 (9), H, W), fp32 and contiguous: what
-        maps_from_fused / dir_from_fused split and the native loss reads."""
+    def fuse(self, cls_map, reg_map, *extra):
+        """The module outputs back in the fused layout [cls | reg (| dir) (| iou)] (B, n_anchor * (8 + groups), H, W), fp32 and
+        contiguous: what maps_from_fused / dir_from_fused / iou_from_fused split and the native loss reads.  extra: the maps `forward`
+        returns behind the first two, in its order."""
         B, _, _, H, W = cls_map.shape
         parts = [cls_map.reshape(B, -1, H, W), reg_map.permute(0, 1, 5, 2, 3, 4).reshape(B, -1, H, W)]
-        if dir_map is not None:
-            parts.append(dir_map.reshape(B, -1, H, W))
+        for m in extra:
+            if m is not None:
+                parts.append(m.reshape(B, -1, H, W))
         return torch.cat([p.float() for p in parts], 1)
 
     def native_head(self, feature_map):
@@ -431,16 +535,56 @@ class FusedProposalDirLossFunction(torch.autograd.Function):
         return (dmaps,) + (None,) * 10
 
 
+class FusedProposalIoULossFunction(torch.autograd.Function):
+    """The same for a head with an IoU-aware confidence logit (cfg.IOU_HEAD; v3d_proposal_iou_loss_fwd_bwd): (maps [cls | reg | (dir) |
+    iou], anchors, G_cls, M_cls, G_reg, M_reg, G_dir int8 or None) -> (cls_loss, reg_loss, dir_loss (0 without the group), iou_loss,
+    iou_target or None).  The IoU target is computed inside the pass from the box channels and is a constant: no gradient reaches
+    them through it.  backward scales the four (three) channel groups with their upstream gradients."""
+
+    @staticmethod
+    def forward(ctx, maps, anchors, g_cls, m_cls, g_reg, m_reg, g_dir, sin_yaw, n_cls, n_yaw, alpha, gamma, want_target=False):
+        from .. import _lib as L
+        b, _, h, w = maps.shape
+        losses = torch.empty(5, dtype=torch.float32, device=maps.device)
+        dmaps = torch.empty_like(maps)
+        target = torch.empty((b, n_cls, n_yaw, h, w), dtype=torch.float32, device=maps.device) if want_target else None
+        lib = L.lib()
+        ws = L.workspace(lib.v3d_proposal_iou_loss_workspace(), maps.device)
+        with L.device_guard(maps.device):
+            L.check(lib.v3d_proposal_iou_loss_fwd_bwd(L.ptr(maps), L.ptr(anchors), L.ptr(g_cls), L.ptr(m_cls), L.ptr(g_reg), L.ptr(m_reg),
+                                                      L.ptr(g_dir), int(bool(sin_yaw)), b, n_cls, n_yaw, h, w, float(alpha), float(gamma),
+                                                      L.ptr(losses), L.ptr(dmaps), L.ptr(target), L.ptr(ws), ws.numel(), L.stream_ptr()),
+                    "proposal_iou_loss_fwd_bwd")
+        ctx.grad, ctx.geom, ctx.with_dir = dmaps, (b, n_cls, n_yaw, h, w), g_dir is not None
+        if target is not None:
+            ctx.mark_non_differentiable(target)
+        return losses[0], losses[1], losses[2], losses[3], target
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cls_loss, g_reg_loss, g_dir_loss, g_iou_loss, _g_target=None):
+        from .. import _lib as L
+        dmaps = take_gradient(ctx, "proposal")
+        # (the last scalar is the 1.0f the two-way scale kernel multiplies the other groups with: csrc/proposal_loss.hip)
+        up = [g.to(torch.float32).contiguous() for g in (g_cls_loss, g_reg_loss, g_dir_loss, g_iou_loss, torch.ones_like(g_cls_loss))]
+        with L.device_guard(dmaps.device):
+            L.check(L.lib().v3d_proposal_iou_loss_scale(L.ptr(dmaps), *ctx.geom, L.ptr(up[0]), L.ptr(up[1]), L.ptr(up[2]) if ctx.with_dir else 0,
+                                                        L.ptr(up[3]), L.ptr(up[4]), L.stream_ptr()), "proposal_iou_loss_scale")
+        return (dmaps,) + (None,) * 12
+
+
 class ProposalLoss(nn.Module):
     """Focal classification + smooth-L1 box loss, both divided by max(#positives, 1)
     (proposal.py:100-141).  (P, G, M) = (predicted, ground truth, mask).  With cfg.DIRECTION.ENABLED: the yaw column's smooth-L1
     argument is sin(P_yaw - G_yaw) (SIN_YAW) and dir_loss = BCE-with-logits(P_dir, G_dir) over M_reg / max(#positives, 1) joins the
-    sum times LOSS_WEIGHT."""
+    sum times LOSS_WEIGHT.  With cfg.IOU_HEAD.ENABLED: iou_loss = soft-target BCE-with-logits(P_iou, iou_targets) over M_reg /
+    max(#positives, 1) joins the sum times its LOSS_WEIGHT; the target is detached."""
 
     def __init__(self, cfg):
         super().__init__()
         self.cfg = cfg
         self.direction = direction_config(cfg)
+        self.iou_head = checked_iou_head(cfg)
 
     @staticmethod
     def masked_sum(loss, mask):
@@ -460,6 +604,29 @@ class ProposalLoss(nn.Module):
         bce = x.clamp(min=0) - x * g + torch.log1p(torch.exp(-x.abs()))
         return self.masked_sum(bce, M_reg[..., 0])
 
+    def iou_targets(self, item, native=None):
+        """The IoU target of cfg.IOU_HEAD in the shape of P_cls: at the M_reg positives t = clamp(IoU3D(P, G), 0, 1) of the boxes decoded
+        from P_reg and G_reg relative to the anchor's centre (`relative_boxes`; the raw yaw, also with cfg.DIRECTION: IoU is
+        pi-periodic), 0 elsewhere; detached.  The IoU is ops.box_iou3d_aligned on fp32 GPU tensors (native=None: where it applies) and
+        its torch statement elsewhere, on the gathered positives."""
+        from ..ops.iou_loss import box_iou3d_aligned, box_iou3d_aligned_torch
+        P_reg, G_reg, M_reg = item["P_reg"].detach(), item["G_reg"], item["M_reg"]
+        mask = M_reg[..., 0].ne(0) if M_reg.dim() == P_reg.dim() else M_reg.ne(0)
+        anchors = item["anchors"].to(device=P_reg.device, dtype=P_reg.dtype).reshape((1,) + tuple(P_reg.shape[1:])).expand_as(P_reg)
+        p = relative_boxes(P_reg[mask], anchors[mask])
+        g = relative_boxes(G_reg.to(P_reg.dtype)[mask], anchors[mask])
+        if native is None:
+            native = p.is_cuda and p.dtype == torch.float32
+        iou = box_iou3d_aligned(p.contiguous(), g.contiguous()) if native else box_iou3d_aligned_torch(p, g)
+        target = torch.zeros(mask.shape, dtype=P_reg.dtype, device=P_reg.device)
+        target[mask] = iou.clamp(0, 1)
+        return target
+
+    def iou_loss(self, P_iou, target, M_reg):
+        z, t = P_iou, target.to(P_iou.dtype)
+        bce = z.clamp(min=0) - z * t + torch.log1p(torch.exp(-z.abs()))
+        return self.masked_sum(bce, M_reg[..., 0])
+
     def cls_loss(self, P_cls, G_cls, M_cls):
         # (float64 logits keep float64 targets: torch's BCE takes the dtype of its TARGET, so fp32 targets made the float64 statement fp32)
         target = G_cls.double() if P_cls.dtype == torch.float64 else G_cls.float()
@@ -472,29 +639,42 @@ class ProposalLoss(nn.Module):
         if isinstance(maps, tuple):
             # (maps, P_cls, P_reg) as Second.forward leaves them: the fused maps only speak for this item while its P_cls / P_reg
             # are still the views made from them -- outputs that were replaced or post-processed go through the torch expressions
-            maps, p_cls, p_reg, *p_dir = maps
-            if item.get("P_cls") is not p_cls or item.get("P_reg") is not p_reg or (p_dir and item.get("P_dir") is not p_dir[0]):
+            maps, p_cls, p_reg, *extra = maps
+            keys = [k for k, on in (("P_dir", self.direction["ENABLED"]), ("P_iou", self.iou_head["ENABLED"])) if on]
+            if item.get("P_cls") is not p_cls or item.get("P_reg") is not p_reg or len(extra) != len(keys) \
+                    or any(item.get(k) is not m for k, m in zip(keys, extra)):
                 return None
         cfg = self.cfg
-        with_dir = bool(self.direction["ENABLED"])
+        with_dir, with_iou = bool(self.direction["ENABLED"]), bool(self.iou_head["ENABLED"])
         if maps is None or not maps.is_cuda or maps.dtype != torch.float32 or not maps.is_contiguous() or cfg.BOX_DOF != 7:
             return None
         G_cls, M_cls, G_reg, M_reg = (item[k] for k in ("G_cls", "M_cls", "G_reg", "M_reg"))
         b, o, h, w = maps.shape
         n_cls, n_yaw = cfg.NUM_CLASSES, cfg.NUM_YAW
         shape = (b, n_cls, n_yaw, h, w)
-        if o != n_cls * n_yaw * (8 + with_dir) or tuple(G_cls.shape) != shape or tuple(M_cls.shape) != shape \
+        if o != n_cls * n_yaw * (8 + with_dir + with_iou) or tuple(G_cls.shape) != shape or tuple(M_cls.shape) != shape \
                 or tuple(G_reg.shape) != shape + (7,) or tuple(M_reg.shape) != shape + (1,) or G_reg.dtype != torch.float32:
             return None
         if any(t.device != maps.device for t in (G_cls, M_cls, G_reg, M_reg)):
             return None
         g_cls = G_cls if G_cls.dtype == torch.int8 else G_cls.to(torch.int8)
         as_u8 = lambda m: (m if m.dtype in (torch.bool, torch.uint8) else m.ne(0)).contiguous().view(torch.uint8)
+        g_dir = None
         if with_dir:
             G_dir = item["G_dir"]
             if tuple(G_dir.shape) != shape or G_dir.device != maps.device:
                 return None
-            g_dir = G_dir if G_dir.dtype == torch.int8 else G_dir.to(torch.int8)
+            g_dir = (G_dir if G_dir.dtype == torch.int8 else G_dir.to(torch.int8)).contiguous()
+        if with_iou:
+            anchors = item.get("anchors")
+            if not torch.is_tensor(anchors) or anchors.device != maps.device or anchors.dtype != torch.float32 \
+                    or anchors.numel() != n_cls * n_yaw * h * w * 7:
+                return None
+            cls_loss, reg_loss, dir_loss, iou_loss, _ = FusedProposalIoULossFunction.apply(
+                maps, anchors.contiguous(), g_cls.contiguous(), as_u8(M_cls), G_reg.contiguous(), as_u8(M_reg), g_dir,
+                bool(self.direction["SIN_YAW"]), n_cls, n_yaw, 0.25, 2.0)
+            return self._total(cls_loss, reg_loss, dir_loss if with_dir else None, iou_loss)
+        if with_dir:
             cls_loss, reg_loss, dir_loss = FusedProposalDirLossFunction.apply(
                 maps, g_cls.contiguous(), as_u8(M_cls), G_reg.contiguous(), as_u8(M_reg), g_dir.contiguous(), bool(self.direction["SIN_YAW"]),
                 n_cls, n_yaw, 0.25, 2.0)
@@ -503,9 +683,17 @@ class ProposalLoss(nn.Module):
                                                              n_cls, n_yaw, 0.25, 2.0)
         return dict(cls_loss=cls_loss, reg_loss=reg_loss, loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss)
 
-    def _total(self, cls_loss, reg_loss, dir_loss):
-        return dict(cls_loss=cls_loss, reg_loss=reg_loss, dir_loss=dir_loss,
-                    loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss + self.direction["LOSS_WEIGHT"] * dir_loss)
+    def _total(self, cls_loss, reg_loss, dir_loss, iou_loss=None):
+        out = dict(cls_loss=cls_loss, reg_loss=reg_loss)
+        loss = cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss
+        if dir_loss is not None:
+            out["dir_loss"] = dir_loss
+            loss = loss + self.direction["LOSS_WEIGHT"] * dir_loss
+        if iou_loss is not None:
+            out["iou_loss"] = iou_loss
+            loss = loss + self.iou_head["LOSS_WEIGHT"] * iou_loss
+        out["loss"] = loss
+        return out
 
     def forward(self, item):
         fused = self._fused(item)
@@ -515,6 +703,8 @@ class ProposalLoss(nn.Module):
         normalizer = M_reg.type_as(P_reg).sum().clamp_(min=1)
         cls_loss = self.cls_loss(P_cls, G_cls, M_cls) / normalizer
         reg_loss = self.reg_loss(P_reg, G_reg, M_reg) / normalizer
-        if self.direction["ENABLED"]:
-            return self._total(cls_loss, reg_loss, self.dir_loss(item["P_dir"], item["G_dir"], M_reg) / normalizer)
+        if self.direction["ENABLED"] or self.iou_head["ENABLED"]:
+            dir_loss = self.dir_loss(item["P_dir"], item["G_dir"], M_reg) / normalizer if self.direction["ENABLED"] else None
+            iou_loss = self.iou_loss(item["P_iou"], self.iou_targets(item), M_reg) / normalizer if self.iou_head["ENABLED"] else None
+            return self._total(cls_loss, reg_loss, dir_loss, iou_loss)
         return dict(cls_loss=cls_loss, reg_loss=reg_loss, loss=cls_loss + self.cfg.TRAIN.LAMBDA * reg_loss)

@@ -335,8 +335,10 @@ class Second(nn.Module):
         # the fused maps of an EARLIER training forward must never reach ProposalLoss through a re-used item dict
         item.pop("_head_maps", None)
         item.pop("P_dir", None)
+        item.pop("P_iou", None)
         with_dir = not self.center_head and self.head.direction["ENABLED"]  # cfg.DIRECTION: a third map, P_dir, beside P_cls / P_reg
-        direction = None
+        with_iou = not self.center_head and self.head.iou_head["ENABLED"]   # cfg.IOU_HEAD: one more map, P_iou, behind it
+        direction = iou = None
         if self._native_item(item):
             state = {}
 
@@ -346,26 +348,29 @@ class Second(nn.Module):
                 return maps
             maps = self._with_recalibration(run, lambda: state["plan"])
             scores, boxes = self.head.maps_from_fused(maps)
-            if with_dir:
-                direction = self.head.dir_from_fused(maps)
+            if with_dir or with_iou:
+                direction, iou = self.head.extra_from_fused(maps)
         elif (maps := self._train_head_maps(item)) is not None:
-            if with_dir and isinstance(maps, tuple) and maps[0].is_cuda:
-                # the dense half of a head with a direction classifier trains through the torch modules (dense_train.supported
-                # refuses its width): their three outputs, concatenated, are the fused map the native loss reads
+            if (with_dir or with_iou) and isinstance(maps, tuple) and maps[0].is_cuda:
+                # the dense half of a head with a direction classifier or an IoU confidence trains through the torch modules
+                # (dense_train.supported refuses its width): their outputs, concatenated, are the fused map the native loss reads
                 maps = self.head.fuse(*maps)
             scores, boxes = maps[:2] if isinstance(maps, tuple) else self.head.maps_from_fused(maps)
-            if with_dir:
-                direction = maps[2] if isinstance(maps, tuple) else self.head.dir_from_fused(maps)
+            if with_dir or with_iou:
+                direction, iou = self.head._split_extra(maps[2:]) if isinstance(maps, tuple) else self.head.extra_from_fused(maps)
             if not isinstance(maps, tuple):
                 # ProposalLoss takes its native pass on the fused maps (detector/proposal.py) -- only while P_cls / P_reg are
                 # still the views made here (it compares identities): post-processed outputs go through the torch expressions
-                item["_head_maps"] = (maps, scores, boxes) + ((direction,) if with_dir else ())
+                item["_head_maps"] = (maps, scores, boxes) + ((direction,) if with_dir else ()) + ((iou,) if with_iou else ())
         else:
             scores, boxes, *rest = self.head(self.feature_extract(item))
-            direction = rest[0] if with_dir else None
+            if with_dir or with_iou:
+                direction, iou = self.head._split_extra(rest)
         item.update(dict(P_cls=scores, P_reg=boxes))
         if with_dir:
             item["P_dir"] = direction
+        if with_iou:
+            item["P_iou"] = iou
         return item
 
     def inference(self, item):
@@ -500,4 +505,4 @@ class Second(nn.Module):
                              "is its op-by-op statement)")
         maps = self.fused_head_from_points(clouds)
         cls_map, reg_map = self.head.maps_from_fused(maps)
-        return self.head.inference_from_maps(cls_map, reg_map, anchors, self.head.dir_from_fused(maps))
+        return self.head.inference_from_maps(cls_map, reg_map, anchors, *self.head.extra_from_fused(maps))

@@ -83,7 +83,17 @@ def _clip(px, py, cnt, lab, nx, ny, cx, cy, h, own):
     nxt = torch.where(slot + 1 < cnt[:, None], slot + 1, torch.zeros_like(slot))
     d = (nx[:, None] * (px - cx[:, None]) + ny[:, None] * (py - cy[:, None])) - h[:, None]
     qx, qy, dn, = px.gather(1, nxt), py.gather(1, nxt), d.gather(1, nxt)
-    ic, inn = d <= 0, dn <= 0
+    # the vertices outside are held to ONE run (il_one_run): the runs that hold the vertex farthest outside, or a NaN distance
+    out = valid & ~(d <= 0)
+    nan = out & torch.isnan(d)
+    ranked = torch.where(out & ~nan, d, torch.full_like(d, -float("inf")))
+    seed = nan | ((slot == ranked.argmax(1, keepdim=True)) & (ranked.max(1, keepdim=True).values > -float("inf")))
+    prv = torch.where(slot >= 1, slot - 1, (cnt[:, None] - 1).clamp(min=0))
+    reach = seed & out
+    for _ in range(7):
+        reach = reach | (out & (reach.gather(1, nxt) | reach.gather(1, prv)))
+    ic = ~reach
+    inn = ic.gather(1, nxt)
     e1, e2 = valid & ic, valid & (ic != inn)
     t = d / (d - dn)
     ix, iy = px + t * (qx - px), py + t * (qy - py)
