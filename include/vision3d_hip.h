@@ -682,6 +682,16 @@ int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* weight
 int v3d_conv2d_1x1_head_fused(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1,
                               const void* w2_image, const float* b2, int relu2, int B, int H, int W, int Cmid, int Cout2,
                               float* y_nchw, const v3d_conv2d_prec* pr, v3d_stream_t stream);
+/* The same tail over the LIVE tiles only.  tile_state: the v3d_conv2d_bg_tiles(B, H, W) words the background-skipping 3x3 layer that
+ * wrote x_hi / x_lo keeps (5 x 16 tiles in (b, ty, tx) order; 0 = the tile holds that layer's empty-map response).  A 1x1 layer adds
+ * no reach: such a tile's head output is bg_maps (Cout2, H, W) fp32 -- v3d_conv2d_1x1_head_fused applied to that layer's empty-map
+ * planes of one image -- and is copied from there; the tile's input planes are not read (f16s: the range flag covers the computed
+ * tiles only).  Same bits as v3d_conv2d_1x1_head_fused on the same planes.  The launch takes at most max_workgroups CUs (0 = half
+ * of them) and loops when the live tiles need more.  A map of more than 4 096 tiles computes every pixel. */
+int v3d_conv2d_1x1_head_fused_tiles(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1,
+                                    const void* w2_image, const float* b2, int relu2, int B, int H, int W, int Cmid, int Cout2,
+                                    float* y_nchw, const v3d_conv2d_prec* pr, const uint32_t* tile_state, const float* bg_maps,
+                                    int max_workgroups, v3d_stream_t stream);
 /* fp32 (B, C, H, W) -> split planes (B, H, W, C) of `prec` (f16s: pieces of x * act_entry[0]; act_entry NULL for bf16x3) */
 int v3d_nchw_to_split_nhwc(const float* x, int B, int C, int H, int W, void* out_hi, void* out_lo, int prec,
                            const float* act_entry, v3d_stream_t stream);

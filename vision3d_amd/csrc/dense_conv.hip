@@ -29,6 +29,7 @@
 //              (16-byte stores) or fp32 NCHW for the consumer outside this file.
 #include "v3d_internal.h"
 #include "split_prec.h"
+#include "scan_device.h"
 
 typedef unsigned short bf16_t;  // storage type of a 16-bit piece at the C ABI (bf16 or f16 by the arithmetic)
 
@@ -1310,88 +1311,111 @@ __global__ __launch_bounds__(256) void conv1x1_bf16x3_small_cout_kernel(const bf
 // ReLU + the hi / lo split on the hardware converter exactly as the tile kernel's epilogue stores them, a transpose of the wave's
 // 16 x 128 tile through a private LDS slab into A fragments again, and the head's 12 MFMAs with its three term accumulators summed
 // (lh + hl) + hh + bias as in conv1x1_bf16x3_small_cout_kernel.  Bit-identical to the two launches it replaces
-// (tests/test_gpu_dense_conv.py); every pixel is computed (background included: same values as the skipping path, no tile state).
-// Persistent grid: <= one workgroup of FH_WAVES waves per CU, waves stride over the 16-pixel tiles.
+// (tests/test_gpu_dense_conv.py).  A pixel's result does not depend on the pixels that share its wave: the per-slot body
+// (fh_slot_body) is stated once and both forms of the kernel hand it 16 pixels of one row of the planes.
+//   every pixel (TILES = false): slot t = flat pixels 16 t .. 16 t + 15, background included, no tile state; grid <= one workgroup
+//     of FH_WAVES waves per CU, waves stride over the slots.
+//   live tiles only (TILES = true; v3d_conv2d_1x1_head_fused_tiles): a 1x1 layer adds no reach, so behind the last 3x3 layer a tile
+//     that layer left as background (its tile_state word reads 0: dl_tile2d) evaluates to a constant of the weights -- the head's
+//     empty-map response `bg` (Cout2, H, W).  Every workgroup reads the state words of that layer (D2_TH x D2_TW tiles in
+//     (b, ty, tx) order) and builds, with the workgroup scan, the same ascending list of live tiles in LDS (the dead ones descend
+//     from the list's far end).  Live tile e, row i is slot 5 e + i = pixels (b, y0 + i, x0 .. x0 + 15): rows beyond H are dropped,
+//     columns beyond W are computed on a clamped pixel and not stored; wave w of workgroup g takes slots g * 9 + w + k * 9 * grid.
+//     Dead tiles are plain copies bg -> y_nchw, dealt round-robin over the workgroups starting with those that hold no slot; their
+//     input planes are never read (f16s: maxima and the range flag cover the computed slots only, the rule of the skipping 3x3
+//     layers).  The grid is sized for the LIVE slots on at most `max_workgroups` CUs (default half the chip: 128 x 9 waves = 230 live
+//     KITTI tiles in one pass, more loop again): the other CUs stay with the other frames in flight.
+//     (grid of 64 / 128 / 192 workgroups at bs = 1, four frames in flight: `value` equal within the runs' scatter; one frame at a
+//     time a grid of 64 needs two passes and the launch lasts 6 us longer: profiles/head_live_tiles.txt.)
+// Order of requests: [the state words, alone in front,] the image, the head's weight column, the lane's biases and the scales; the
+// image's LDS stores; [the scan, whose barriers also publish the image: no barrier of its own;] the first slot's eight A-fragment
+// loads, [behind them the loads of the workgroup's first two dead tiles, stored as soon as they arrive,] then (every pixel) the
+// barrier, which the A fragments cross in flight -- they used to wait behind it.  A later slot's A fragments are requested as the
+// slot before it ends.  Every early load is unconditional on a clamped address: a load inside a divergent branch is waited for at the
+// branch's end.  One frame at a time the live-tiles launch lasts 12.3 us against the every-pixel form's 10.9 (one more dependent
+// round trip: state words -> list -> A fragments); what it buys is the half of the chip it leaves alone.
 // ------------------------------------------------------------------------------------------------
 #define FH_WAVES 9  // 256 workgroups x 9 waves = 2 304 >= the 2 200 sixteen-pixel tiles of the 200 x 176 KITTI map: one tile per wave, no second pass
+#define FH_THREADS (FH_WAVES * 64)
 #define FH_ROW 272                                  // bytes of one pixel row of a transpose slab (256 + 16: conflict-free 16-byte reads)
 #define FH_SLAB (2 * 16 * FH_ROW)                   // hi + lo planes of one wave's 16 x 128 tile
 #define FH_W1_BYTES (4 * 2 * 128 * 32 * 2)          // 4 k-steps x (hi, lo) x 128 couts x 32 cins, bf16
 #define FH_SMEM (FH_W1_BYTES + FH_WAVES * FH_SLAB)
+#define FH_W1_REGS ((FH_W1_BYTES / 16 + FH_THREADS - 1) / FH_THREADS)  // 16-byte pieces of the image per thread
+// the tile list beside the slabs: 4 096 tiles hold the Waymo-range map (376 x 376: 76 x 24 = 1 824 tiles) at batch 2 and the KITTI
+// map (440 tiles) at batch 9; a larger map takes the every-pixel form
+#define FH_LIST_MAX 4096
+#define FH_SMEM_TILES (FH_SMEM + FH_LIST_MAX * 4 + 16 * 4)  // + the scan's per-wave sums
+#define FH_CP_EARLY 2                                                           // dead tiles a workgroup copies in front of its slots
+#define FH_CP_REGS ((16 * D2_TH * D2_TW + FH_THREADS - 1) / FH_THREADS)        // elements of a (<= 16 channel) tile per thread
+static_assert(FH_SMEM_TILES <= 160 * 1024, "the head kernel's LDS request fits a CU");
+static_assert(FH_WAVES <= 16, "the scan's scratch holds 16 per-wave sums");
 struct FhScales {  // f16s (PREC 1): entries of the input planes and of the intermediate tensor, the two images' 1 / s_w, the flag
   const float *in_entry, *mid_entry, *w1_inv, *w2_inv;
   int* range_flag;
 };
-template <int PREC>
-__global__ __launch_bounds__(FH_WAVES * 64) void conv1x1_head_fused_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo,
-                                                                          const bf16_t* __restrict__ w1_img, const float* __restrict__ b1,
-                                                                          int relu1, const bf16_t* __restrict__ w2_img,
-                                                                          const float* __restrict__ b2, int relu2, int M, int HW,
-                                                                          int cout2, int cout2_pad, float* __restrict__ y_nchw,
-                                                                          const FhScales fs) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char fh_smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  {  // the 1x1 layer's packed image, as it lies in memory: [step][plane][n-tile][lane][8]
-    const u32x4* src = reinterpret_cast<const u32x4*>(w1_img);
-    u32x4* dst = reinterpret_cast<u32x4*>(fh_smem);
-    for (int i = tid; i < FH_W1_BYTES / 16; i += FH_WAVES * 64) dst[i] = src[i];
-  }
-  // the head's packed weight column (n-tile 0, hi and lo of the four k-steps) lives in registers for all of the wave's tiles
-  u32x4 h_bh[4], h_bl[4];
-  {
-    const size_t pe2 = (size_t)cout2_pad * 32;
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-      h_bh[s] = *reinterpret_cast<const u32x4*>(w2_img + (size_t)s * 2 * pe2 + (size_t)lane * 8);
-      h_bl[s] = *reinterpret_cast<const u32x4*>(w2_img + (size_t)s * 2 * pe2 + pe2 + (size_t)lane * 8);
-    }
-  }
-  __syncthreads();
-  DcScales sc1{1.f, 1.f, 3.0e38f}, sc2{1.f, 1.f, 3.0e38f};
-  if constexpr (PREC == 1) {
-    sc1.undo = fs.in_entry[1] * fs.w1_inv[0];
-    sc1.s_out = fs.mid_entry[0];
-    sc1.limit = fs.mid_entry[2];
-    sc2.undo = fs.mid_entry[1] * fs.w2_inv[0];
-  }
-  float vmax = 0.f;
-  const unsigned char* w1s = fh_smem;
-  unsigned char* slab = fh_smem + FH_W1_BYTES + wave * FH_SLAB;
+struct FhTiles {  // the live-tiles form: the feeding layer's state words, the head's empty-map response, the map's geometry
+  const uint32_t* state;
+  const float* bg;
+  int B, H, W;
+};
+struct FhSlot {  // 16 pixels of one row: flat index of the first, how many of them exist (0: nothing to compute)
+  int m0, n;
+};
+struct FhConsts {  // what every slot of a launch shares
+  float bv1[8], bv2;  // the lane's biases: couts nf * 16 + px_l of the 1x1 layer, cout px_l of the head (0 without a bias)
+  int relu1, relu2, HW, cout2;
+  float* y_nchw;
+  DcScales sc1, sc2;
+};
+__device__ __forceinline__ void fh_load_a(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo, const FhSlot sl, const int lane,
+                                          u32x4 (&ah)[4], u32x4 (&al)[4]) {
   const int px_l = lane & 15, kg = lane >> 4;
-  const int ntiles = (M + 15) / 16;
-  for (int t = blockIdx.x * FH_WAVES + wave; t < ntiles; t += gridDim.x * FH_WAVES) {
-    const int m0 = t * 16;
-    const int px = min(m0 + px_l, M - 1);  // rows beyond M are computed on a clamped pixel and not stored
-    u32x4 ah[4], al[4];
+  const int px = sl.m0 + min(px_l, sl.n - 1);  // pixels beyond the slot's end are computed on a clamped pixel and not stored
 #pragma unroll
-    for (int s = 0; s < 4; s++) {
-      ah[s] = *reinterpret_cast<const u32x4*>(x_hi + (size_t)px * 128 + s * 32 + kg * 8);
-      al[s] = *reinterpret_cast<const u32x4*>(x_lo + (size_t)px * 128 + s * 32 + kg * 8);
-    }
+  for (int s = 0; s < 4; s++) {
+    ah[s] = *reinterpret_cast<const u32x4*>(x_hi + (size_t)px * 128 + s * 32 + kg * 8);
+    al[s] = *reinterpret_cast<const u32x4*>(x_lo + (size_t)px * 128 + s * 32 + kg * 8);
+  }
+}
+// One slot: 96 MFMAs on the A fragments, bias + ReLU + split, the transpose through the wave's slab, the head's 12 MFMAs, the store.
+template <int PREC>
+__device__ __forceinline__ void fh_slot_body(const u32x4 (&ah)[4], const u32x4 (&al)[4], const FhSlot sl, const unsigned char* w1s,
+                                             unsigned char* slab, const u32x4 (&h_bh)[4], const u32x4 (&h_bl)[4], const FhConsts& c,
+                                             const int lane, float& vmax) {
+  const int px_l = lane & 15, kg = lane >> 4;
+  const int relu1 = c.relu1, relu2 = c.relu2, cout2 = c.cout2, HW = c.HW;
+  const DcScales sc1 = c.sc1, sc2 = c.sc2;
+  float* __restrict__ y_nchw = c.y_nchw;
+  {
     f32x4 acc[8];
 #pragma unroll
     for (int nf = 0; nf < 8; nf++) acc[nf] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 4; s++) {
-      u32x4 bh[8], bl[8];
-#pragma unroll
-      for (int nf = 0; nf < 8; nf++) {
-        bh[nf] = *reinterpret_cast<const u32x4*>(w1s + s * 16384 + (nf * 64 + lane) * 16);
-        bl[nf] = *reinterpret_cast<const u32x4*>(w1s + s * 16384 + 8192 + (nf * 64 + lane) * 16);
-      }
       const u32x4 a_h = ah[s], a_l = al[s];
+      // four accumulators at a time: 32 registers of B fragments in flight, not 64 (with the next slot's A fragments and the
+      // lane's biases in registers the eight-wide form spilled the head's weights); per accumulator the order is unchanged
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_l, bh[nf], acc[nf]);
+      for (int n0 = 0; n0 < 8; n0 += 4) {
+        u32x4 bh[4], bl[4];
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_h, bl[nf], acc[nf]);
+        for (int j = 0; j < 4; j++) {
+          bh[j] = *reinterpret_cast<const u32x4*>(w1s + s * 16384 + ((n0 + j) * 64 + lane) * 16);
+          bl[j] = *reinterpret_cast<const u32x4*>(w1s + s * 16384 + 8192 + ((n0 + j) * 64 + lane) * 16);
+        }
 #pragma unroll
-      for (int nf = 0; nf < 8; nf++) acc[nf] = split_mfma<PREC>(a_h, bh[nf], acc[nf]);
+        for (int j = 0; j < 4; j++) acc[n0 + j] = split_mfma<PREC>(a_l, bh[j], acc[n0 + j]);
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[n0 + j] = split_mfma<PREC>(a_h, bl[j], acc[n0 + j]);
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[n0 + j] = split_mfma<PREC>(a_h, bh[j], acc[n0 + j]);
+      }
     }
     // bias + ReLU + split: D[pixel = kg * 4 + r][cout = nf * 16 + px_l] -> slab[plane][pixel][cout] (bf16)
 #pragma unroll
     for (int nf = 0; nf < 8; nf++) {
-      const float bv = b1 ? b1[nf * 16 + px_l] : 0.f;
+      const float bv = c.bv1[nf];
 #pragma unroll
       for (int r2 = 0; r2 < 2; r2++) {
         float v0 = dc_finish<PREC>(acc[nf][2 * r2], bv, sc1), v1 = dc_finish<PREC>(acc[nf][2 * r2 + 1], bv, sc1);
@@ -1422,11 +1446,11 @@ __global__ __launch_bounds__(FH_WAVES * 64) void conv1x1_head_fused_kernel(const
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the fragment reads are done before the next tile overwrites the slab
     const int co = px_l;
     if (co < cout2) {
-      const float bv = b2 ? b2[co] : 0.f;
+      const float bv = c.bv2;
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const int m = m0 + kg * 4 + r;
-        if (m >= M) continue;
+        if (kg * 4 + r >= sl.n) continue;
+        const int m = sl.m0 + kg * 4 + r;
         float v = dc_finish<PREC>((c_lh[r] + c_hl[r]) + c_hh[r], bv, sc2);  // small terms first
         if (relu2) v = fmaxf(v, 0.f);
         const int b = m / HW, pix = m - b * HW;
@@ -1434,8 +1458,161 @@ __global__ __launch_bounds__(FH_WAVES * 64) void conv1x1_head_fused_kernel(const
       }
     }
   }
+}
+
+template <int PREC, bool TILES>
+__global__ __launch_bounds__(FH_THREADS) void conv1x1_head_fused_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo,
+                                                                        const bf16_t* __restrict__ w1_img, const float* __restrict__ b1,
+                                                                        int relu1, const bf16_t* __restrict__ w2_img,
+                                                                        const float* __restrict__ b2, int relu2, int M, int HW,
+                                                                        int cout2, int cout2_pad, float* __restrict__ y_nchw,
+                                                                        const FhScales fs, const FhTiles ft) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char fh_smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int* const list = reinterpret_cast<int*>(fh_smem + FH_SMEM);  // (TILES) live tiles ascending from [0], dead ones descending from [n_t - 1]
+  const int tx_n = TILES ? (ft.W + D2_TW - 1) / D2_TW : 1, tpi = TILES ? tx_n * ((ft.H + D2_TH - 1) / D2_TH) : 1;
+  const int n_t = TILES ? ft.B * tpi : 0;  // <= FH_LIST_MAX (the launcher)
+  // (every early load of this kernel is UNCONDITIONAL on a clamped address: a load inside a divergent branch is waited for at the
+  // branch's end, which puts its round trip in front of everything behind it)
+  unsigned st0 = 0u;
+  if constexpr (TILES) {
+    st0 = ft.state[min(tid, n_t - 1)];   // the first request of the kernel:
+    __builtin_amdgcn_sched_barrier(0);   // the scan waits for this word alone, not for the 64 KB behind it
+  }
+  // the 1x1 layer's packed image, as it lies in memory: [step][plane][n-tile][lane][8] -- requested here, stored in front of the scan
+  u32x4 wimg[FH_W1_REGS];
+#pragma unroll
+  for (int j = 0; j < FH_W1_REGS; j++) {
+    const int i = min(tid + j * FH_THREADS, FH_W1_BYTES / 16 - 1);
+    wimg[j] = reinterpret_cast<const u32x4*>(w1_img)[i];
+  }
+  // the head's packed weight column (n-tile 0, hi and lo of the four k-steps) lives in registers for all of the wave's slots
+  u32x4 h_bh[4], h_bl[4];
+  {
+    const size_t pe2 = (size_t)cout2_pad * 32;
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+      h_bh[s] = *reinterpret_cast<const u32x4*>(w2_img + (size_t)s * 2 * pe2 + (size_t)lane * 8);
+      h_bl[s] = *reinterpret_cast<const u32x4*>(w2_img + (size_t)s * 2 * pe2 + pe2 + (size_t)lane * 8);
+    }
+  }
+  // the biases once per wave (per slot they were nine dependent loads in the epilogues) and the scales, requested with the weights
+  FhConsts c{{}, 0.f, relu1, relu2, HW, cout2, y_nchw, DcScales{1.f, 1.f, 3.0e38f}, DcScales{1.f, 1.f, 3.0e38f}};
+#pragma unroll
+  for (int nf = 0; nf < 8; nf++) c.bv1[nf] = b1 ? b1[nf * 16 + (lane & 15)] : 0.f;
+  c.bv2 = b2 ? b2[min(lane & 15, cout2 - 1)] : 0.f;  // (lanes beyond cout2 store nothing)
+  if constexpr (PREC == 1) {
+    c.sc1.undo = fs.in_entry[1] * fs.w1_inv[0];
+    c.sc1.s_out = fs.mid_entry[0];
+    c.sc1.limit = fs.mid_entry[2];
+    c.sc2.undo = fs.mid_entry[1] * fs.w2_inv[0];
+  }
+  // The image's LDS stores.  TILES: the scan's barriers make them visible -- no barrier of their own; a workgroup that turns out to
+  // hold no slot has stored the image for nothing (holding it in registers across the scan to skip these stores cost more: at 168
+  // registers the copies' and the A fragments' loads were waited for one after the other)
+#pragma unroll
+  for (int j = 0; j < FH_W1_REGS; j++) {
+    const int i = tid + j * FH_THREADS;
+    if (i < FH_W1_BYTES / 16) reinterpret_cast<u32x4*>(fh_smem)[i] = wimg[j];
+  }
+  int n_live = 0;
+  if constexpr (TILES) {
+    int* const sums = list + FH_LIST_MAX;
+    for (int base = 0; base < n_t; base += FH_THREADS) {  // (workgroup-uniform bounds)
+      const int t = base + tid;
+      const unsigned st = base == 0 ? st0 : ft.state[min(t, n_t - 1)];
+      const int live = (t < n_t && st != 0u) ? 1 : 0;
+      int tot;
+      const int before = n_live + v3d_block_scan_incl<FH_WAVES>(live, tot, sums) - live;  // live tiles below t
+      if (t < n_t) list[live ? before : n_t - 1 - (t - before)] = t;
+      n_live += tot;
+      __syncthreads();  // the list's stores are visible; `sums` may be written again
+    }
+  }
+  const int n_slots = TILES ? n_live * D2_TH : (M + 15) / 16;
+  const int stride = gridDim.x * FH_WAVES;
+  auto slot_of = [&](const int s) -> FhSlot {  // (wave-uniform)
+    if constexpr (TILES) {
+      const int e = s / D2_TH, i = s - e * D2_TH;
+      const int t = __builtin_amdgcn_readfirstlane(list[e]);
+      const int b = t / tpi, rt = t - b * tpi;
+      const int y = (rt / tx_n) * D2_TH + i, x0 = (rt % tx_n) * D2_TW;
+      return FhSlot{(b * ft.H + y) * ft.W + x0, y < ft.H ? min(16, ft.W - x0) : 0};
+    } else {
+      return FhSlot{s * 16, min(16, M - s * 16)};
+    }
+  };
+  int s = blockIdx.x * FH_WAVES + wave;
+  FhSlot sl{0, 0};
+  u32x4 ah[4], al[4];
+  if (s < n_slots) {
+    sl = slot_of(s);
+    if (sl.n > 0) fh_load_a(x_hi, x_lo, sl, lane, ah, al);  // in flight across the image's stores and the barrier
+  }
+  float vmax = 0.f;
+  // Dead tiles: the head's empty-map response, one tile per workgroup and turn; dead tile k goes to workgroup (g0 + k) % grid,
+  // g0 = the first workgroup without a slot (0 when every workgroup has one).  The workgroup's first FH_CP_EARLY dead tiles are
+  // requested HERE, behind the first slot's A fragments, and stored in front of the barrier: their round trip is the one the A
+  // fragments make anyway (behind the slots they were one more round trip per tile at the kernel's end).
+  const int G = gridDim.x, n_dead = n_t - n_live;
+  const int busy = (n_slots + FH_WAVES - 1) / FH_WAVES, g0 = busy < G ? busy : 0;
+  const int k0 = ((int)blockIdx.x - g0 + G) % G;
+  const size_t hw = (size_t)ft.H * ft.W;
+  // element q of dead tile k: whether it exists, and where it comes from and goes to (0, a valid address, when it does not)
+  auto dead_elem = [&](const int k, const int q, size_t& src, size_t& dst) -> bool {
+    const bool in_list = k < n_dead && q < cout2 * (D2_TH * D2_TW);
+    const int t = list[in_list ? n_t - 1 - k : 0];
+    const int b = t / tpi, rt = t - b * tpi;
+    const int ch = q / (D2_TH * D2_TW), r = q - ch * (D2_TH * D2_TW);
+    const int yy = (rt / tx_n) * D2_TH + r / D2_TW, xx = (rt % tx_n) * D2_TW + r % D2_TW;
+    const bool ok = in_list && yy < ft.H && xx < ft.W;
+    src = ok ? (size_t)ch * hw + (size_t)yy * ft.W + xx : 0;
+    dst = ok ? ((size_t)b * cout2 + ch) * hw + (size_t)yy * ft.W + xx : 0;
+    return ok;
+  };
+  float cp[FH_CP_EARLY][FH_CP_REGS];
+  if constexpr (TILES) {
+#pragma unroll
+    for (int i = 0; i < FH_CP_EARLY; i++)
+#pragma unroll
+      for (int j = 0; j < FH_CP_REGS; j++) {
+        size_t src, dst;
+        dead_elem(k0 + i * G, tid + j * FH_THREADS, src, dst);
+        cp[i][j] = ft.bg[src];
+      }
+  }
+  if constexpr (TILES) {
+#pragma unroll
+    for (int i = 0; i < FH_CP_EARLY; i++)
+#pragma unroll
+      for (int j = 0; j < FH_CP_REGS; j++) {
+        size_t src, dst;
+        if (dead_elem(k0 + i * G, tid + j * FH_THREADS, src, dst)) y_nchw[dst] = cp[i][j];
+      }
+  }
+  if constexpr (!TILES) __syncthreads();  // the image (the first slot's A fragments are in flight across it)
+  {
+    const unsigned char* w1s = fh_smem;
+    unsigned char* slab = fh_smem + FH_W1_BYTES + wave * FH_SLAB;
+    while (s < n_slots) {
+      if (sl.n > 0) fh_slot_body<PREC>(ah, al, sl, w1s, slab, h_bh, h_bl, c, lane, vmax);
+      s += stride;
+      if (s < n_slots) {
+        sl = slot_of(s);
+        if (sl.n > 0) fh_load_a(x_hi, x_lo, sl, lane, ah, al);
+      }
+    }
+  }
+  if constexpr (TILES) {  // the dead tiles beyond the early ones (a nearly empty map)
+    for (int k = k0 + FH_CP_EARLY * G; k < n_dead; k += G)
+      for (int q = tid; q < cout2 * (D2_TH * D2_TW); q += FH_THREADS) {
+        size_t src, dst;
+        if (dead_elem(k, q, src, dst)) y_nchw[dst] = ft.bg[src];
+      }
+  }
   if constexpr (PREC == 1)
-    if (fs.range_flag && vmax > sc1.limit) atomicMax(fs.range_flag, V3D_FLAG_RANGE);
+    if (fs.range_flag && vmax > c.sc1.limit) atomicMax(fs.range_flag, V3D_FLAG_RANGE);
 }
 
 static int dc_check_prec(const v3d_conv2d_prec* pr, bool planes_out) {
@@ -1444,16 +1621,23 @@ static int dc_check_prec(const v3d_conv2d_prec* pr, bool planes_out) {
   return V3D_OK;
 }
 
-extern "C" int v3d_conv2d_1x1_head_fused(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1,
-                                          const void* w2_image, const float* b2, int relu2, int B, int H, int W, int Cmid, int Cout2,
-                                          float* y_nchw, const v3d_conv2d_prec* pr, v3d_stream_t stream) {
-  if (!x_hi || !x_lo || !w1_image || !w2_image || !y_nchw || B < 1 || H < 1 || W < 1) return V3D_EINVAL;
+// Both entry points of the fused tail.  tile_state NULL: every pixel, on up to max_workgroups CUs (0: all of them).  With tile_state
+// (and bg_maps): live tiles only, on up to max_workgroups CUs (0: half of them) -- unless the map has more tiles than the kernel's
+// list holds, which takes the every-pixel form.
+static int fh_launch(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1, const void* w2_image,
+                     const float* b2, int relu2, int B, int H, int W, int Cmid, int Cout2, float* y_nchw, const v3d_conv2d_prec* pr,
+                     const uint32_t* tile_state, const float* bg_maps, int max_workgroups, v3d_stream_t stream) {
+  if (!x_hi || !x_lo || !w1_image || !w2_image || !y_nchw || B < 1 || H < 1 || W < 1 || max_workgroups < 0) return V3D_EINVAL;
   if (Cmid != 128 || Cout2 < 1 || Cout2 > 16) return V3D_EUNSUPPORTED;  // 128 -> 128 -> <= 16: the SECOND RPN tail
   if (dc_check_prec(pr, true)) return V3D_EINVAL;  // (out_entry = the entry of the intermediate 128-channel tensor)
   const int n_cu = v3d_device_cu_count();
   if (n_cu < 1) return V3D_EINVAL;
-  const int M = B * H * W, ntiles = (M + 15) / 16;
-  const int grid = std::min(v3d_ceil_div(ntiles, FH_WAVES), n_cu);
+  const long long tiles2 = (long long)B * v3d_ceil_div(H, D2_TH) * v3d_ceil_div(W, D2_TW);
+  const bool tiles = tile_state && tiles2 <= FH_LIST_MAX;
+  const int M = B * H * W;
+  const int slots = tiles ? (int)tiles2 * D2_TH : (M + 15) / 16;  // (tiles: the most the frame can hold)
+  const int cap = max_workgroups > 0 ? max_workgroups : (tiles ? std::max(n_cu / 2, 1) : n_cu);
+  const int grid = std::min(v3d_ceil_div(slots, FH_WAVES), cap);
   const int cout2_pad = (Cout2 + DC_BN - 1) / DC_BN * DC_BN;
   const bool f16s = pr && pr->prec == V3D_PREC_F16S;
   FhScales fs{nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1464,13 +1648,31 @@ extern "C" int v3d_conv2d_1x1_head_fused(const void* x_hi, const void* x_lo, con
     fs.w2_inv = pr->w_inv2 ? pr->w_inv2 : reinterpret_cast<const float*>(reinterpret_cast<const char*>(w2_image) + dc_image_payload_bytes(128, Cout2, 1)) + V3D_WIMG_INV_SCALE;
     fs.range_flag = pr->range_flag;
   }
-  auto kern = f16s ? conv1x1_head_fused_kernel<1> : conv1x1_head_fused_kernel<0>;
-  V3D_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, FH_SMEM));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(FH_WAVES * 64), FH_SMEM, (hipStream_t)stream, (const bf16_t*)x_hi,
+  auto kern = tiles ? (f16s ? conv1x1_head_fused_kernel<1, true> : conv1x1_head_fused_kernel<0, true>)
+                    : (f16s ? conv1x1_head_fused_kernel<1, false> : conv1x1_head_fused_kernel<0, false>);
+  const int smem = tiles ? FH_SMEM_TILES : FH_SMEM;
+  const FhTiles ft{tiles ? tile_state : nullptr, tiles ? bg_maps : nullptr, B, H, W};
+  V3D_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(FH_THREADS), smem, (hipStream_t)stream, (const bf16_t*)x_hi,
                      (const bf16_t*)x_lo, (const bf16_t*)w1_image, b1, relu1, (const bf16_t*)w2_image, b2, relu2, M, H * W, Cout2,
-                     cout2_pad, y_nchw, fs);
+                     cout2_pad, y_nchw, fs, ft);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
+}
+
+extern "C" int v3d_conv2d_1x1_head_fused(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1,
+                                          const void* w2_image, const float* b2, int relu2, int B, int H, int W, int Cmid, int Cout2,
+                                          float* y_nchw, const v3d_conv2d_prec* pr, v3d_stream_t stream) {
+  return fh_launch(x_hi, x_lo, w1_image, b1, relu1, w2_image, b2, relu2, B, H, W, Cmid, Cout2, y_nchw, pr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int v3d_conv2d_1x1_head_fused_tiles(const void* x_hi, const void* x_lo, const void* w1_image, const float* b1, int relu1,
+                                                const void* w2_image, const float* b2, int relu2, int B, int H, int W, int Cmid,
+                                                int Cout2, float* y_nchw, const v3d_conv2d_prec* pr, const uint32_t* tile_state,
+                                                const float* bg_maps, int max_workgroups, v3d_stream_t stream) {
+  if (!tile_state || !bg_maps) return V3D_EINVAL;
+  return fh_launch(x_hi, x_lo, w1_image, b1, relu1, w2_image, b2, relu2, B, H, W, Cmid, Cout2, y_nchw, pr, tile_state, bg_maps,
+                   max_workgroups, stream);
 }
 
 extern "C" int v3d_conv2d_bg_tiles(int B, int H, int W);

@@ -815,8 +815,8 @@ class DenseHeadPlan(object):
     def _invalidate_background(self):
         """The empty-map responses belong to the old weights / scales: recomputed at the next use -- INTO the same tensors when
         they exist (captured graphs hold their addresses)."""
-        for planes in self._background.values():
-            planes["valid"] = False
+        for rec in self._background.values():
+            rec["valid"] = False  # (the planes and the head's response together)
         self.calibration_generation += 1  # (DenseHeadState: nothing is in place any more)
 
     def recalibrate(self):
@@ -842,6 +842,36 @@ class DenseHeadPlan(object):
         nxt = self.w_inv[i + 1:i + 2] if i + 1 < self.w_inv.numel() else None  # (the fused tail's second image: the head)
         return (src, self.tab[i] if planes_out else None, flag, self.w_inv[i:i + 1], nxt)
 
+    def _tail_fusable(self):
+        """The RPN ends on a 1x1 128 -> 128 layer under a 1x1 head of <= 16 channels: v3d_conv2d_1x1_head_fused's shapes."""
+        head = self.layers[-1]
+        return (head is not None and len(self.layers) >= 2
+                and self.layers[-2]["k"] == 1 and self.layers[-2]["cin"] == 128 and self.layers[-2]["cout"] == 128
+                and head["k"] == 1 and head["cin"] == 128 and head["cout"] <= 16)
+
+    def _head_fused(self, i, x_hi, x_lo, maps, in_entry, range_flag, tile_state=None, bg_maps=None):
+        """The fused tail (RPN layer i = the 1x1 up-conv, then the head) into `maps`; with tile_state / bg_maps over the live tiles only."""
+        ly, head = self.layers[i], self.layers[-1]
+        b, h, w, _ = x_hi.shape
+        ref, keep = _prec_struct(self._pr(i, in_entry, range_flag))
+        args = (L.ptr(x_hi), L.ptr(x_lo), L.ptr(ly["img"]), L.ptr(ly["bias"]), int(bool(ly["relu"])), L.ptr(head["img"]),
+                L.ptr(head["bias"]), int(bool(head["relu"])), b, h, w, 128, head["cout"], L.ptr(maps), ref)
+        with L.device_guard(x_hi.device):
+            if tile_state is None:
+                L.check(L.lib().v3d_conv2d_1x1_head_fused(*args, L.stream_ptr()), "conv2d_1x1_head_fused")
+            else:
+                L.check(L.lib().v3d_conv2d_1x1_head_fused_tiles(*args, L.ptr(tile_state), L.ptr(bg_maps), 0, L.stream_ptr()),
+                        "conv2d_1x1_head_fused_tiles")
+        del keep
+        return maps
+
+    def background_head(self, h, w, device):
+        """The head maps (1, Cout2, H, W) of the EMPTY BEV map: the fused tail over the background planes of the layer that feeds
+        it -- what v3d_conv2d_1x1_head_fused_tiles copies into that layer's background tiles.  Kept, rebuilt in place and
+        invalidated with `background`'s planes; None when the tail does not fuse."""
+        self.background(h, w, device)
+        return self._background[(int(h), int(w), str(device))]["head"]
+
     def background(self, h, w, device):
         """Per RPN layer: its output on an EMPTY (all-zero) BEV map of one image, as split planes -- what every pixel far
         enough from all occupied pixels evaluates to, borders included (`forward(..., occ=...)`).  Computed once per weight
@@ -861,7 +891,14 @@ class DenseHeadPlan(object):
                 (x_hi, x_lo), _ = conv2d_split(x_hi, x_lo, ly["img"], ly["bias"], ly["relu"], ly["cin"], ly["cout"], ly["k"], out=out,
                                                pr=self._pr(i, zero_entry, None))
                 planes.append((x_hi, x_lo))
-            self._background[key] = dict(planes=planes, valid=True)
+            head = None if rec is None else rec["head"]
+            n_rpn = len(self.layers) - 1
+            if self._tail_fusable() and n_rpn >= 2:
+                # the every-pixel entry over the planes in front of the 1x1 up-conv, INTO the tensor captured graphs hold
+                if head is None or head.shape[1] != self.layers[-1]["cout"]:
+                    head = torch.empty((1, self.layers[-1]["cout"], int(h), int(w)), dtype=torch.float32, device=device)
+                self._head_fused(n_rpn - 1, planes[n_rpn - 2][0], planes[n_rpn - 2][1], head, zero_entry, None)
+            self._background[key] = dict(planes=planes, head=head, valid=True)
         return self._background[key]["planes"]
 
     def calibrate(self, x_hi, x_lo, in_entry, headroom_bits=CALIB_HEADROOM_BITS):
@@ -919,9 +956,7 @@ class DenseHeadPlan(object):
         head = self.layers[-1]
         # the RPN's 1x1 up-conv and the 1x1 head on top of it as ONE pass over the pixels (v3d_conv2d_1x1_head_fused: same bits as the
         # two launches) whenever nobody asks for the RPN features themselves
-        fuse_tail = (self.fuse_tail and not want_features and head is not None and len(self.layers) >= 2
-                     and self.layers[-2]["k"] == 1 and self.layers[-2]["cin"] == 128 and self.layers[-2]["cout"] == 128
-                     and head["k"] == 1 and head["cin"] == 128 and head["cout"] <= 16)
+        fuse_tail = self.fuse_tail and not want_features and self._tail_fusable()
         # Tile counters of a persistent state: the layers reset each other's pairs (the first launched layer zeroes the pairs of all the
         # others -- left by the previous frame --, the second the first's) instead of every launch ending on the atomic round trip
         # of a self-resetting pair; needs at least two launched skipping layers
@@ -932,14 +967,16 @@ class DenseHeadPlan(object):
             if last and fuse_tail:
                 b, h, w, _ = x_hi.shape
                 maps = torch.empty((b, head["cout"], h, w), dtype=torch.float32, device=x_hi.device)
-                ref, keep = _prec_struct(self._pr(i, in_entry, range_flag))
-                with L.device_guard(x_hi.device):
-                    L.check(L.lib().v3d_conv2d_1x1_head_fused(L.ptr(x_hi), L.ptr(x_lo), L.ptr(ly["img"]), L.ptr(ly["bias"]),
-                                                               int(bool(ly["relu"])), L.ptr(head["img"]), L.ptr(head["bias"]),
-                                                               int(bool(head["relu"])), b, h, w, 128, head["cout"], L.ptr(maps),
-                                                               ref, L.stream_ptr()), "conv2d_1x1_head_fused")
-                del keep
-                return maps
+                # With a persistent state the layer in front keeps one word per 5 x 16 tile: 0 = the tile holds its empty-map response,
+                # and the head's output there is a constant of the weights (`background_head`) -- the tail runs over the live tiles
+                # only.  (Only the 2-D tile kernel keeps its words in that tiling: a 3x3 layer, 128 -> 128.)
+                prev = self.layers[i - 1] if i >= 1 else None
+                by_tiles = (state is not None and occ is not None and prev is not None and prev["k"] == 3
+                            and prev["cin"] == 128 and prev["cout"] == 128)
+                if by_tiles:
+                    bg_head = self._background[(int(h), int(w), str(x_hi.device))]["head"]
+                    return self._head_fused(i, x_hi, x_lo, maps, in_entry, range_flag, state.tiles[i - 1], bg_head)
+                return self._head_fused(i, x_hi, x_lo, maps, in_entry, range_flag)
             reach += ly["k"] // 2
             (x_hi, x_lo), f = conv2d_split(x_hi, x_lo, ly["img"], ly["bias"], ly["relu"], ly["cin"], ly["cout"], ly["k"],
                                            out_split=True, out_nchw=want_features and last, occ=occ, reach=reach,
