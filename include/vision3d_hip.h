@@ -675,6 +675,22 @@ int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* weight
                           const uint32_t* occ, int reach, const void* bg_hi, const void* bg_lo, uint32_t* work,
                           uint32_t* tile_state, uint32_t* reset_ptr, int reset_words, const v3d_conv2d_prec* pr,
                           v3d_stream_t stream);
+/* A chain of 3x3 128 -> 128 background-skipping layers under ONE persistent state (work, tile_state and output planes per layer, as
+ * above) with a per-frame TILE SCHEDULE: which tiles of a layer are live depends on `occ` and the layer's reach alone, so the FIRST
+ * launch of the chain (list NULL, n_build = the launches behind it, <= 8) draws its own tiles as v3d_conv2d_nhwc_split does and, on
+ * n_build workgroups more, writes for each later launch k its list build_list[k] (v3d_conv2d_tile_sched_words words: live count,
+ * stale count, the live tiles at build_reach[k] in increasing index, the background tiles whose word in build_tile_state[k] -- that
+ * layer's tile_state -- is still nonzero).  A LATER launch (list = its own, n_build 0) runs exactly those tiles: no draws, no
+ * occupancy test, `work` untouched (reset_ptr / reset_words as above).  Same values as v3d_conv2d_nhwc_split with the same occ / reach.
+ * build_reach / build_tile_state / build_list are host arrays.  v3d_conv2d_tile_sched_words returns 0 for a layer that takes no
+ * schedule (another shape, or a map of 4 tiles per CU and more): such a chain uses v3d_conv2d_nhwc_split. */
+int v3d_conv2d_tile_sched_words(int B, int H, int W, int Cin, int Cout, int ksize);
+int v3d_conv2d_nhwc_split_sched(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias, int relu, int B,
+                                int H, int W, int Cin, int Cout, int ksize, void* y_hi, void* y_lo, const uint32_t* occ, int reach,
+                                const void* bg_hi, const void* bg_lo, uint32_t* work, uint32_t* tile_state, uint32_t* reset_ptr,
+                                int reset_words, const v3d_conv2d_prec* pr, const uint32_t* list, int n_build,
+                                const int32_t* build_reach, const uint32_t* const* build_tile_state, uint32_t* const* build_list,
+                                v3d_stream_t stream);
 /* The tail of the SECOND dense head in ONE launch: RPN up-conv 1x1 128 -> 128 (+ folded BatchNorm bias + ReLU, detector/second.py:73-79)
  * followed by the fused [cls | reg] 1x1 head 128 -> Cout2 <= 16 (detector/proposal.py:19-22), split planes (B, H, W, 128) in, fp32
  * NCHW (B, Cout2, H, W) out; w1_image / w2_image from v3d_conv2d_pack_weights(.., ksize 1).  Bit-identical to v3d_conv2d_nhwc_split

@@ -119,6 +119,9 @@ _SIGNATURES = {
     "v3d_conv2d_bg_tiles": (_i, [_i, _i, _i]),
     "v3d_conv2d_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "v3d_conv2d_nhwc_split": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "v3d_conv2d_tile_sched_words": (_i, [_i, _i, _i, _i, _i, _i]),
+    "v3d_conv2d_nhwc_split_sched": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                         _vp, _i, _vp, _vp, _vp, _vp]),
     "v3d_conv2d_1x1_head_fused": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "v3d_conv2d_1x1_head_fused_tiles": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "v3d_nchw_to_split_nhwc": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),

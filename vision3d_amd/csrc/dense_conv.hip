@@ -954,50 +954,71 @@ __device__ __forceinline__ void dl_tile(unsigned char* smem_l, const bf16_t* __r
 static_assert(2 * D2_PLANE <= dl_smem(D2_TH), "the neighbourhood image lives in the tile kernel's LDS request");
 static_assert(D2_TH * 16 * DL_TS * 4 <= 2 * D2_PLANE, "the epilogue tile reuses the image's LDS");
 #define D2_THREADS 256
+// THE LIVENESS RULE of a 5 x 16 tile, stated once (the drawing kernel asks it per drawn tile, one (row, word) pair per lane; the
+// schedule builder per tile and thread): a tile is background <=> no occupied pixel lies within `R` (Chebyshev) of any of its
+// pixels: the rectangle rows y0 - R .. y0 + 4 + R, columns x0 - R .. x0 + 15 + R, clipped to the image, against the inverted
+// bitmap `occ_b` of the tile's image (rows of `wpr` words).  Looks at the pairs first, first + step, ... of the rectangle and
+// returns whether one of them holds an occupied pixel.
+__device__ __forceinline__ bool d2_tile_near(const unsigned* occ_b, const int H, const int W, const int wpr, const int R, const int y0,
+                                             const int x0, const int first, const int step) {
+  const int ylo = max(y0 - R, 0), yhi = min(min(y0 + D2_TH - 1, H - 1) + R, H - 1);
+  const int xlo = max(x0 - R, 0), xhi = min(min(x0 + D2_TW - 1, W - 1) + R, W - 1);
+  const int w0 = xlo >> 5, nw = (xhi >> 5) - w0 + 1, total = (yhi - ylo + 1) * nw;
+  bool near_any = false;
+  for (int q = first; q < total; q += step) {
+    const int row = ylo + q / nw, wd = w0 + q % nw;
+    const int lo = max(xlo, wd * 32), hi = min(xhi, wd * 32 + 31);
+    const unsigned mask = (0xFFFFFFFFu >> (31 - (hi - wd * 32))) & (0xFFFFFFFFu << (lo - wd * 32));
+    near_any |= (~occ_b[(size_t)row * wpr + wd] & mask) != 0u;
+  }
+  return near_any;
+}
+
+// a background tile's values: the layer's empty-map response, copied (every thread of the workgroup)
+__device__ __forceinline__ void d2_copy_background(const DcParams& p, bf16_t* __restrict__ y_hi, bf16_t* __restrict__ y_lo, const int b,
+                                                   const int y0, const int x0) {
+  constexpr int BM = D2_TH * 16, NT = D2_THREADS;
+  const int tid = threadIdx.x;
+  const int parts = p.cout_store >> 3;
+  for (int q = tid; q < BM * parts; q += NT) {
+    const int row = q / parts, part = q - row * parts;
+    const int yy = y0 + (row >> 4), xx = x0 + (row & 15);
+    if (yy >= p.H || xx >= p.W) continue;
+    const size_t src = ((size_t)yy * p.W + xx) * p.cout_store + part * 8, dst = (((size_t)b * p.H + yy) * p.W + xx) * p.cout_store + part * 8;
+    *reinterpret_cast<u32x4*>(y_hi + dst) = *reinterpret_cast<const u32x4*>(p.bg_hi + src);
+    *reinterpret_cast<u32x4*>(y_lo + dst) = *reinterpret_cast<const u32x4*>(p.bg_lo + src);
+  }
+}
+
+// TEST false (the scheduled form): the caller knows the tile is live -- no occupancy test -- and passes s_next = nullptr (no draw).
+// `ngrid`: the drawing workgroups of the launch (the base of the draws).
 // Returns true (workgroup-uniform) when the tile was LIVE and the workgroup's next tile has already been drawn into *s_next: the
 // draw -- an atomic round trip of ~1.5 us -- is issued behind the matrix phase by one thread and travels while the
 // epilogue stores, instead of standing between this tile's last store and the next tile.  (Asking at the START of a live tile hands
 // tiles to workgroups that stay busy for 15 us: 21 -> 32 us; at this point the workgroup is one epilogue away from being free.)
-template <int PREC>
+template <int PREC, bool TEST = true>
 __device__ __forceinline__ bool dl_tile2d(unsigned char* smem_l, const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo,
                                           const bf16_t* __restrict__ w_img, const float* __restrict__ bias, const DcParams& p,
-                                          bf16_t* __restrict__ y_hi, bf16_t* __restrict__ y_lo, const int mtile, int* s_next) {
+                                          bf16_t* __restrict__ y_hi, bf16_t* __restrict__ y_lo, const int mtile, int* s_next,
+                                          const int ngrid) {
   constexpr int MT = D2_TH, BM = MT * 16, NT = D2_THREADS;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tx_n = (p.W + D2_TW - 1) / D2_TW, ty_n = (p.H + D2_TH - 1) / D2_TH;
   const int b = mtile / (ty_n * tx_n), rt = mtile - b * ty_n * tx_n;
   const int y0 = (rt / tx_n) * D2_TH, x0 = (rt % tx_n) * D2_TW;
-  if (p.occ) {
-    // background tile <=> no occupied pixel within `reach` of any pixel of the tile: the rectangle (rows y0 - R .. y0 + 4 + R,
-    // columns x0 - R .. x0 + 15 + R, clipped to the image) against the bitmap, one (row, word) pair per lane
-    const int R = p.reach, wpr = (p.W + 31) >> 5;
-    const int ylo = max(y0 - R, 0), yhi = min(min(y0 + D2_TH - 1, p.H - 1) + R, p.H - 1);
-    const int xlo = max(x0 - R, 0), xhi = min(min(x0 + D2_TW - 1, p.W - 1) + R, p.W - 1);
-    const int w0 = xlo >> 5, nw = (xhi >> 5) - w0 + 1, total = (yhi - ylo + 1) * nw;
+  if (TEST && p.occ) {
+    // background tile <=> d2_tile_near finds nothing, one (row, word) pair of the rectangle per lane
+    const int wpr = (p.W + 31) >> 5;
     const unsigned in_place = p.tile_state ? p.tile_state[mtile] : 1u;  // (requested with the occupancy words, not behind them)
-    bool near_any = false;
-    for (int q = lane; q < total; q += 64) {
-      const int row = ylo + q / nw, wd = w0 + q % nw;
-      const int lo = max(xlo, wd * 32), hi = min(xhi, wd * 32 + 31);
-      const unsigned mask = (0xFFFFFFFFu >> (31 - (hi - wd * 32))) & (0xFFFFFFFFu << (lo - wd * 32));
-      near_any |= (~p.occ[((size_t)b * p.H + row) * wpr + wd] & mask) != 0u;
-    }
+    const bool near_any = d2_tile_near(p.occ + (size_t)b * p.H * wpr, p.H, p.W, wpr, p.reach, y0, x0, lane, 64);
     if (!__builtin_amdgcn_readfirstlane(__ballot(near_any) != 0ull)) {
       if (p.tile_state) {
         if (in_place == 0u) return false;  // the response is already in place (workgroup-uniform: one word)
         __syncthreads();             // every thread has read the word before it is cleared
         if (tid == 0) p.tile_state[mtile] = 0u;
       }
-      const int parts = p.cout_store >> 3;
-      for (int q = tid; q < BM * parts; q += NT) {
-        const int row = q / parts, part = q - row * parts;
-        const int yy = y0 + (row >> 4), xx = x0 + (row & 15);
-        if (yy >= p.H || xx >= p.W) continue;
-        const size_t src = ((size_t)yy * p.W + xx) * p.cout_store + part * 8, dst = (((size_t)b * p.H + yy) * p.W + xx) * p.cout_store + part * 8;
-        *reinterpret_cast<u32x4*>(y_hi + dst) = *reinterpret_cast<const u32x4*>(p.bg_hi + src);
-        *reinterpret_cast<u32x4*>(y_lo + dst) = *reinterpret_cast<const u32x4*>(p.bg_lo + src);
-      }
+      d2_copy_background(p, y_hi, y_lo, b, y0, x0);
       return false;
     }
   }
@@ -1121,7 +1142,7 @@ __device__ __forceinline__ bool dl_tile2d(unsigned char* smem_l, const bf16_t* _
   __syncthreads();  // every fragment read is behind us: the image's LDS becomes the epilogue tile
   const bool draws = s_next != nullptr && p.work != nullptr;
   unsigned drawn = 0u;
-  if (draws && tid == 0) drawn = gridDim.x + atomicAdd(p.work, 1u);  // the next tile, requested now (see the header)
+  if (draws && tid == 0) drawn = ngrid + atomicAdd(p.work, 1u);  // the next tile, requested now (see the header)
   // ---- epilogue (all 8 waves): accumulators -> LDS tile [80 px][128 + 4] fp32 -> bias + ReLU -> split planes
   const DcScales sc = dc_scales<PREC>(p);
   float vmax = 0.f;
@@ -1178,31 +1199,120 @@ __device__ __forceinline__ bool dl_tile2d(unsigned char* smem_l, const bf16_t* _
   return draws;
 }
 
-// persistent grid drawing 2-D tiles from the counter pair (see conv2d_bf16x3_large_kernel)
-template <int PREC>
+// THE TILE SCHEDULE of a frame (D2Sched).  Whether a tile of layer k is live depends on the occupancy bitmap and the layer's reach
+// alone, known before the first RPN layer starts -- yet the drawing grid below finds it out tile by tile in every launch (a dead
+// tile costs its workgroup a round trip for the occupancy words and one for the draw, and every workgroup stays resident until a
+// draw runs past the last tile).  With a chain of tile launches under one persistent state the FIRST launch carries one more
+// workgroup per later launch (behind the drawing grid: neither the base of the draws nor the last-workgroup-out count sees them),
+// which writes that launch's two lists: `live` -- the tiles the test above calls live at that layer's reach, in increasing index
+// -- and `stale` -- the background tiles whose state word is still nonzero (they hold an earlier frame's computed values and get the
+// copy).  The later launches (SCHED 2) read their list: no draw, no test, no counter; workgroups without a tile leave after one
+// round trip.  The lists are read by LATER launches only: the kernel boundary orders them.
+// A list: word 0 = live tiles, word 1 = stale tiles, words 2 .. 2 + tiles - 1 = live[], words 2 + tiles .. = stale[].
+#define D2_SCHED_MAX 8
+struct D2Sched {
+  const unsigned* list;  // SCHED 2: this launch's own list
+  int n_build;           // SCHED 1: lists to build, for the launches behind this one
+  int reach[D2_SCHED_MAX];
+  const unsigned* state[D2_SCHED_MAX];  // their tile_state words as the previous frame left them
+  unsigned* out[D2_SCHED_MAX];
+};
+
+__device__ __forceinline__ void d2_build_schedule(unsigned char* smem_l, const DcParams& p, const int ntiles, const int reach,
+                                                  const unsigned* __restrict__ state, unsigned* __restrict__ out) {
+  const int tid = threadIdx.x;
+  const int wpr = (p.W + 31) >> 5, words = p.B * p.H * wpr;
+  int* lds_rank = reinterpret_cast<int*>(smem_l);  // 4 words for v3d_block_rank, the bitmap behind them where it fits
+  const unsigned* occ = p.occ;
+  if ((words + 4) * 4 <= 2 * D2_PLANE) {
+    unsigned* img = reinterpret_cast<unsigned*>(smem_l) + 4;
+    for (int i = tid; i < words; i += D2_THREADS) img[i] = p.occ[i];
+    __syncthreads();
+    occ = img;
+  }
+  const int tx_n = (p.W + D2_TW - 1) / D2_TW, ty_n = (p.H + D2_TH - 1) / D2_TH;
+  int n_live = 0, n_stale = 0;
+  for (int base = 0; base < ntiles; base += D2_THREADS) {  // workgroup-uniform
+    const int t = base + tid, tc = min(t, ntiles - 1);
+    const unsigned in_place = state[tc];
+    const int b = tc / (ty_n * tx_n), rt = tc - b * ty_n * tx_n;
+    const int y0 = (rt / tx_n) * D2_TH, x0 = (rt % tx_n) * D2_TW;
+    const bool live = t < ntiles && d2_tile_near(occ + (size_t)b * p.H * wpr, p.H, p.W, wpr, reach, y0, x0, 0, 1);
+    const bool stale = t < ntiles && !live && in_place != 0u;
+    int tot_live, tot_stale;
+    const int r_live = v3d_block_rank(live, tot_live, lds_rank);
+    const int r_stale = v3d_block_rank(stale, tot_stale, lds_rank);
+    if (live) out[2 + n_live + r_live] = (unsigned)t;
+    if (stale) out[2 + ntiles + n_stale + r_stale] = (unsigned)t;
+    n_live += tot_live;
+    n_stale += tot_stale;
+  }
+  if (tid == 0) {
+    out[0] = (unsigned)n_live;
+    out[1] = (unsigned)n_stale;
+  }
+}
+
+// persistent grid drawing 2-D tiles from the counter pair (see conv2d_bf16x3_large_kernel).  SCHED 0: that and nothing else;
+// 1: + the schedule builders behind the drawing grid; 2: tiles from this launch's list instead of draws (see D2Sched).
+template <int PREC, int SCHED>
 __global__ __launch_bounds__(D2_THREADS, 2) void conv2d_bf16x3_tile2d_kernel(const bf16_t* __restrict__ x_hi, const bf16_t* __restrict__ x_lo,
                                                                           const bf16_t* __restrict__ w_img, const float* __restrict__ bias,
                                                                           const DcParams p, bf16_t* __restrict__ y_hi,
-                                                                          bf16_t* __restrict__ y_lo) {
+                                                                          bf16_t* __restrict__ y_lo, const D2Sched sc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_l[];
   __shared__ int s_next;
   const int ntiles = p.B * ((p.H + D2_TH - 1) / D2_TH) * ((p.W + D2_TW - 1) / D2_TW);
-  // the first tile of a workgroup is its own index (no round trip to the counter in front of the first tile); later draws
-  // continue behind the grid
-  // (requesting the NEXT draw before the current tile starts hides the counter's round trip but hands tiles to workgroups
-  // that are busy with a live one: 21.0 -> 32.4 us on the real frame)
-  if (p.reset_ptr && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < p.reset_words; i += D2_THREADS) p.reset_ptr[i] = 0u;
-  for (int mtile = blockIdx.x; mtile < ntiles;) {  // workgroup-uniform
-    const bool drew = dl_tile2d<PREC>(smem_l, x_hi, x_lo, w_img, bias, p, y_hi, y_lo, mtile, &s_next);
-    if (!drew && threadIdx.x == 0) s_next = (int)(gridDim.x + atomicAdd(p.work, 1u));
-    __syncthreads();  // everyone is done with this tile's LDS
-    mtile = s_next;
-    __syncthreads();  // ... and has read s_next
-  }
-  if (!p.reset_ptr && threadIdx.x == 0 && atomicAdd(p.work + 1, 1u) == gridDim.x - 1) {  // last workgroup out: every draw has happened
-    p.work[0] = 0u;
-    p.work[1] = 0u;
+  if constexpr (SCHED == 2) {
+    // the counts and the workgroup's first entry in one round trip (the entry on a clamped index)
+    const int g = gridDim.x, wg = blockIdx.x;
+    const int n_live = min((int)sc.list[0], ntiles), n_stale = min((int)sc.list[1], ntiles);
+    int mtile = (int)sc.list[2 + min(wg, ntiles - 1)];
+    if (p.reset_ptr && wg == 0)
+      for (int i = threadIdx.x; i < p.reset_words; i += D2_THREADS) p.reset_ptr[i] = 0u;
+    for (int i = wg; i < n_live; i += g) {  // workgroup-uniform
+      const int next = (int)sc.list[2 + min(i + g, ntiles - 1)];  // (a list longer than the grid: requested in front of the tile)
+      if ((unsigned)mtile >= (unsigned)ntiles) break;  // (not a list of this map: nothing is written outside it)
+      dl_tile2d<PREC, false>(smem_l, x_hi, x_lo, w_img, bias, p, y_hi, y_lo, mtile, nullptr, 0);
+      __syncthreads();  // everyone is done with this tile's LDS
+      mtile = next;
+    }
+    // the stale tiles from the far end of the grid: the workgroups with the fewest live tiles take them
+    const int tx_n = (p.W + D2_TW - 1) / D2_TW, ty_n = (p.H + D2_TH - 1) / D2_TH;
+    for (int i = g - 1 - wg; i < n_stale; i += g) {
+      const int t = (int)sc.list[2 + ntiles + i];
+      if ((unsigned)t >= (unsigned)ntiles) break;
+      const int b = t / (ty_n * tx_n), rt = t - b * ty_n * tx_n;
+      if (threadIdx.x == 0) p.tile_state[t] = 0u;
+      d2_copy_background(p, y_hi, y_lo, b, (rt / tx_n) * D2_TH, (rt % tx_n) * D2_TW);
+    }
+    return;
+  } else {
+    const int ngrid = SCHED == 1 ? (int)gridDim.x - sc.n_build : (int)gridDim.x;  // the drawing workgroups
+    if constexpr (SCHED == 1) {
+      if ((int)blockIdx.x >= ngrid) {  // workgroup-uniform
+        const int k = blockIdx.x - ngrid;
+        d2_build_schedule(smem_l, p, ntiles, sc.reach[k], sc.state[k], sc.out[k]);
+        return;
+      }
+    }
+    // the first tile of a workgroup is its own index (no round trip to the counter in front of the first tile); later draws
+    // continue behind the grid
+    // (requesting the NEXT draw before the current tile starts hides the counter's round trip but hands tiles to workgroups
+    // that are busy with a live one: 21.0 -> 32.4 us on the real frame)
+    if (p.reset_ptr && blockIdx.x == 0)
+      for (int i = threadIdx.x; i < p.reset_words; i += D2_THREADS) p.reset_ptr[i] = 0u;
+    for (int mtile = blockIdx.x; mtile < ntiles;) {  // workgroup-uniform
+      const bool drew = dl_tile2d<PREC>(smem_l, x_hi, x_lo, w_img, bias, p, y_hi, y_lo, mtile, &s_next, ngrid);
+      if (!drew && threadIdx.x == 0) s_next = (int)(ngrid + atomicAdd(p.work, 1u));
+      __syncthreads();  // everyone is done with this tile's LDS
+      mtile = s_next;
+      __syncthreads();  // ... and has read s_next
+    }
+    if (!p.reset_ptr && threadIdx.x == 0 && atomicAdd(p.work + 1, 1u) == (unsigned)ngrid - 1) {  // last workgroup out: every draw has happened
+      p.work[0] = 0u;
+      p.work[1] = 0u;
+    }
   }
 }
 
@@ -1709,11 +1819,25 @@ extern "C" int v3d_conv2d_bg_tiles(int B, int H, int W) {
   return (int)(flat > blocks ? flat : blocks);
 }
 
+// Words of ONE launch's tile list (2 + 2 * tiles), or 0 when a layer of this shape does not take a schedule: not the 2-D tile
+// kernel's shape (3x3, 128 -> 128, W >= 16), or a map of 4 tiles per CU and more (there the drawing grid keeps two workgroups per
+// CU busy; static striding over such lists has not been measured against it).
+extern "C" int v3d_conv2d_tile_sched_words(int B, int H, int W, int Cin, int Cout, int ksize) {
+  if (B < 1 || H < 1 || W < 16 || H >= 32768 || W >= 65536 || ksize != 3 || Cin != DL_KC || Cout != DC_BN) return 0;
+  const int n_cu = v3d_device_cu_count();
+  const long long tiles2 = (long long)B * v3d_ceil_div(H, D2_TH) * v3d_ceil_div(W, D2_TW);
+  if (n_cu < 1 || tiles2 >= 4ll * n_cu) return 0;
+  return (int)(2 + 2 * tiles2);
+}
+
 template <int PREC>
 static int dc_launch(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias, DcParams p, int ksize,
                      void* y_hi, void* y_lo, float* y_nchw, const uint32_t* occ, uint32_t* work, uint32_t* tile_state,
-                     uint32_t* reset_ptr, int reset_words, hipStream_t st) {
+                     uint32_t* reset_ptr, int reset_words, const D2Sched* sched, hipStream_t st) {
   const int B = p.B, H = p.H, W = p.W, Cin = p.Cin, Cout = p.Cout;
+  // a launch with a tile schedule runs on the 2-D tile kernel or not at all
+  if (sched && !v3d_conv2d_tile_sched_words(B, H, W, Cin, Cout, ksize)) return V3D_EUNSUPPORTED;
+  if (sched && !(p.occ && work && tile_state && y_hi)) return V3D_EINVAL;
   if (ksize == 1 && !y_hi && Cout <= 16 && (Cin == 128 || Cin == 256)) {  // the head: stream kernel
     const dim3 sgrid(v3d_ceil_div(v3d_ceil_div(p.M, 16), 4));
     if (Cin == 128)
@@ -1748,11 +1872,21 @@ static int dc_launch(const void* x_hi, const void* x_lo, const void* weight_imag
       // 1.84 -> 1.68 ms per batch, 6 420 -> 6 580 frames/s pipelined)
       const int smem2 = 2 * D2_PLANE;
       static V3dPerDeviceFlag attr2;
-      V3D_CHECK_HIP(v3d_set_max_lds(attr2, (const void*)conv2d_bf16x3_tile2d_kernel<PREC>, smem2));
       const int per_cu = tiles2 >= 4 * n_cu ? 2 : 1;
+      const int grid2 = std::min(tiles2, n_cu * per_cu);
+      if (sched) {  // the first launch of a scheduled chain (+ one builder workgroup per list) or a later one (see D2Sched)
+        static V3dPerDeviceFlag attr_b, attr_c;
+        auto kern = sched->list ? conv2d_bf16x3_tile2d_kernel<PREC, 2> : conv2d_bf16x3_tile2d_kernel<PREC, 1>;
+        V3D_CHECK_HIP(v3d_set_max_lds(sched->list ? attr_c : attr_b, (const void*)kern, smem2));
+        hipLaunchKernelGGL(kern, dim3(grid2 + (sched->list ? 0 : sched->n_build)), dim3(D2_THREADS), smem2, st, (const bf16_t*)x_hi,
+                           (const bf16_t*)x_lo, (const bf16_t*)weight_image, bias, p, (bf16_t*)y_hi, (bf16_t*)y_lo, *sched);
+        V3D_CHECK_LAUNCH();
+        return V3D_OK;
+      }
+      V3D_CHECK_HIP(v3d_set_max_lds(attr2, (const void*)(conv2d_bf16x3_tile2d_kernel<PREC, 0>), smem2));
       // (192 / 384 workgroups at bs = 1 measured again under the round-6 pipeline: 4 770 / 4 730 vs 4 757 frames/s, 192 costs 20 us of latency)
-      hipLaunchKernelGGL(conv2d_bf16x3_tile2d_kernel<PREC>, dim3(std::min(tiles2, n_cu * per_cu)), dim3(D2_THREADS), smem2, st, (const bf16_t*)x_hi,
-                         (const bf16_t*)x_lo, (const bf16_t*)weight_image, bias, p, (bf16_t*)y_hi, (bf16_t*)y_lo);
+      hipLaunchKernelGGL((conv2d_bf16x3_tile2d_kernel<PREC, 0>), dim3(grid2), dim3(D2_THREADS), smem2, st, (const bf16_t*)x_hi,
+                         (const bf16_t*)x_lo, (const bf16_t*)weight_image, bias, p, (bf16_t*)y_hi, (bf16_t*)y_lo, D2Sched{});
       V3D_CHECK_LAUNCH();
       return V3D_OK;
     }
@@ -1794,11 +1928,11 @@ static int dc_launch(const void* x_hi, const void* x_lo, const void* weight_imag
 // reset_words: this launch zeroes those counter words of OTHER call sites before its tiles run -- inside the kernel on the persistent
 // paths, by a fill in front of it otherwise, so a chain of layers may mix both kinds (a layer off the persistent paths used to drop
 // the request silently: ADVICE round 4).
-extern "C" int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias,
-                                     int relu, int B, int H, int W, int Cin, int Cout, int ksize, void* y_hi, void* y_lo,
-                                     float* y_nchw, const uint32_t* occ, int reach, const void* bg_hi, const void* bg_lo,
-                                     uint32_t* work, uint32_t* tile_state, uint32_t* reset_ptr, int reset_words,
-                                     const v3d_conv2d_prec* pr, v3d_stream_t stream) {
+static int dc_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias,
+                                int relu, int B, int H, int W, int Cin, int Cout, int ksize, void* y_hi, void* y_lo,
+                                float* y_nchw, const uint32_t* occ, int reach, const void* bg_hi, const void* bg_lo,
+                                uint32_t* work, uint32_t* tile_state, uint32_t* reset_ptr, int reset_words,
+                                const v3d_conv2d_prec* pr, const D2Sched* sched, v3d_stream_t stream) {
   if (reset_ptr && (reset_words < 0 || reset_words > 4096 || !work)) return V3D_EINVAL;
   if (!x_hi || !x_lo || !weight_image || B < 1 || H < 1 || W < 1 || Cout < 1) return V3D_EINVAL;
   if (occ && (!bg_hi || !bg_lo || reach < 0 || reach > 64)) return V3D_EINVAL;
@@ -1830,6 +1964,41 @@ extern "C" int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const v
                                 : reinterpret_cast<const float*>(reinterpret_cast<const char*>(weight_image) + dc_image_payload_bytes(Cin, Cout, ksize)) + V3D_WIMG_INV_SCALE;
   hipStream_t st = (hipStream_t)stream;
   if (f16s)
-    return dc_launch<1>(x_hi, x_lo, weight_image, bias, p, ksize, y_hi, y_lo, y_nchw, occ, work, tile_state, reset_ptr, reset_words, st);
-  return dc_launch<0>(x_hi, x_lo, weight_image, bias, p, ksize, y_hi, y_lo, y_nchw, occ, work, tile_state, reset_ptr, reset_words, st);
+    return dc_launch<1>(x_hi, x_lo, weight_image, bias, p, ksize, y_hi, y_lo, y_nchw, occ, work, tile_state, reset_ptr, reset_words, sched, st);
+  return dc_launch<0>(x_hi, x_lo, weight_image, bias, p, ksize, y_hi, y_lo, y_nchw, occ, work, tile_state, reset_ptr, reset_words, sched, st);
+}
+
+extern "C" int v3d_conv2d_nhwc_split(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias,
+                                     int relu, int B, int H, int W, int Cin, int Cout, int ksize, void* y_hi, void* y_lo,
+                                     float* y_nchw, const uint32_t* occ, int reach, const void* bg_hi, const void* bg_lo,
+                                     uint32_t* work, uint32_t* tile_state, uint32_t* reset_ptr, int reset_words,
+                                     const v3d_conv2d_prec* pr, v3d_stream_t stream) {
+  return dc_conv2d_nhwc_split(x_hi, x_lo, weight_image, bias, relu, B, H, W, Cin, Cout, ksize, y_hi, y_lo, y_nchw, occ, reach, bg_hi, bg_lo,
+                              work, tile_state, reset_ptr, reset_words, pr, nullptr, stream);
+}
+
+// The same launch as one link of a SCHEDULED chain of 3x3 128 -> 128 layers under one persistent state (see D2Sched): the first
+// launch of the chain (n_build >= 1, `list` NULL) draws its own tiles as v3d_conv2d_nhwc_split does and writes the lists of the
+// n_build launches behind it -- build_reach[k], build_tile_state[k] (that layer's words, as its last launch left them) ->
+// build_list[k]; a later launch (`list` = its own, n_build 0) runs the tiles of its list.  Same values as v3d_conv2d_nhwc_split.
+extern "C" int v3d_conv2d_nhwc_split_sched(const void* x_hi, const void* x_lo, const void* weight_image, const float* bias,
+                                           int relu, int B, int H, int W, int Cin, int Cout, int ksize, void* y_hi, void* y_lo,
+                                           const uint32_t* occ, int reach, const void* bg_hi, const void* bg_lo, uint32_t* work,
+                                           uint32_t* tile_state, uint32_t* reset_ptr, int reset_words, const v3d_conv2d_prec* pr,
+                                           const uint32_t* list, int n_build, const int32_t* build_reach,
+                                           const uint32_t* const* build_tile_state, uint32_t* const* build_list, v3d_stream_t stream) {
+  if ((list != nullptr) == (n_build > 0) || n_build < 0 || n_build > D2_SCHED_MAX) return V3D_EINVAL;
+  if (n_build && (!build_reach || !build_tile_state || !build_list)) return V3D_EINVAL;
+  if (!occ || !work || !tile_state || !y_hi || !y_lo) return V3D_EINVAL;
+  D2Sched sc{};
+  sc.list = list;
+  sc.n_build = n_build;
+  for (int k = 0; k < n_build; k++) {
+    if (build_reach[k] < 0 || build_reach[k] > 64 || !build_tile_state[k] || !build_list[k]) return V3D_EINVAL;
+    sc.reach[k] = build_reach[k];
+    sc.state[k] = build_tile_state[k];
+    sc.out[k] = build_list[k];
+  }
+  return dc_conv2d_nhwc_split(x_hi, x_lo, weight_image, bias, relu, B, H, W, Cin, Cout, ksize, y_hi, y_lo, nullptr, occ, reach, bg_hi, bg_lo,
+                              work, tile_state, reset_ptr, reset_words, pr, &sc, stream);
 }

@@ -237,21 +237,28 @@ class PipelinedSecond(object):
     # ---- stream selection by measurement ---------------------------------------------------------------------
     def _time_streams(self, streams, clouds, frames):
         """seconds per frame of ONE window of `frames` frames on these streams: pipeline empty at its start, the frames still in
-        flight collected inside it -- the definition of a timed window of the benchmark (best of three)."""
+        flight collected inside it -- the definition of a timed window of the benchmark (best of three).  Frames are submitted and
+        collected exactly as `__call__` does on that stream set: QUEUE frames per stream in flight, the oldest collected before the
+        next is submitted, the slots a ring of capacity + 1.  (With ONE frame per stream the depth-4 time was mostly host time and
+        its margin over depth 3 noise around the threshold: a build with a shorter frame fell to depth 3 in 4 of 27 runs and then
+        measured 7 % below its parent -- profiles/head_live_tiles.txt, block 3.)"""
         import time
         best = None
+        capacity = len(streams) * self.QUEUE
         for _ in range(3):
             torch.cuda.synchronize()
-            t0, inflight = time.perf_counter(), []
+            t0, inflight = time.perf_counter(), []  # (slot, stream index) in submission order
+            slot = 0
             for f in range(frames):
-                i = f % len(streams)
-                if len(inflight) == len(streams):
-                    j = inflight.pop(0)
-                    self._finish(j, streams[j])
-                self._launch(i, streams[i], clouds)
-                inflight.append(i)
-            for j in inflight:
-                self._finish(j, streams[j])
+                if len(inflight) == capacity:
+                    i, j = inflight.pop(0)
+                    self._finish(i, streams[j])
+                j = f % len(streams)
+                self._launch(slot, streams[j], clouds)
+                inflight.append((slot, j))
+                slot = (slot + 1) % (capacity + 1)
+            for i, j in inflight:
+                self._finish(i, streams[j])
             torch.cuda.synchronize()
             t = (time.perf_counter() - t0) / frames
             best = t if best is None else min(best, t)

@@ -599,12 +599,15 @@ def _prec_struct(pr):
 
 
 def conv2d_split(x_hi, x_lo, image, bias, relu, cin, cout, ksize, out_split=True, out_nchw=False, occ=None, reach=0, bg=None, work=None,
-                 out=None, tile_state=None, reset=None, pr=None):
+                 out=None, tile_state=None, reset=None, pr=None, sched=None):
     """One split-precision convolution on split NHWC planes; returns (y_hi, y_lo) and/or fp32 (B,cout,H,W).
     occ / reach / bg = (bg_hi, bg_lo) [/ work: 2 zeroed int32 of the caller's, see the header]: background skipping
     (v3d_conv2d_nhwc_split with occ), same values.  out = (y_hi, y_lo): write into these planes; with tile_state (one int32 per
     tile of a PERSISTENT `out`, see the header) background tiles that already hold the empty-map response are not written.
-    pr: None = bf16x3 (image from pack_conv_weight(.., "bf16x3")); (in_entry, out_entry, range_flag) = f16s."""
+    pr: None = bf16x3 (image from pack_conv_weight(.., "bf16x3")); (in_entry, out_entry, range_flag) = f16s.
+    sched: one link of a scheduled chain (v3d_conv2d_nhwc_split_sched; needs occ, work, out and tile_state): ("build", reaches,
+    tile_states, lists) = the chain's first launch, which writes the tile lists of the launches behind it; ("run", list) = a later
+    launch, which runs the tiles of its list."""
     b, h, w, c = x_hi.shape
     assert c == cin
     dev = x_hi.device
@@ -617,6 +620,25 @@ def conv2d_split(x_hi, x_lo, image, bias, relu, cin, cout, ksize, out_split=True
         y = torch.empty((b, cout, h, w), dtype=torch.float32, device=dev)
     skipping = occ is not None and bg is not None
     ref, keep = _prec_struct(pr)
+    if sched is not None:
+        if not (skipping and work is not None and out is not None and tile_state is not None and out_split and not out_nchw):
+            raise RuntimeError("conv2d_split: a scheduled launch needs occ, bg, work, out and tile_state, and writes split planes only")
+        if sched[0] == "build":
+            n = len(sched[1])
+            reaches = (C.c_int32 * n)(*[int(r) for r in sched[1]])
+            states = (C.c_void_p * n)(*[t.data_ptr() for t in sched[2]])
+            lists = (C.c_void_p * n)(*[t.data_ptr() for t in sched[3]])
+            tail = (None, n, reaches, states, lists)
+        else:
+            tail = (L.ptr(sched[1]), 0, None, None, None)
+        with L.device_guard(dev):
+            L.check(L.lib().v3d_conv2d_nhwc_split_sched(L.ptr(x_hi), L.ptr(x_lo), L.ptr(image), L.ptr(bias), int(bool(relu)), b, h, w, cin, cout,
+                                                        ksize, L.ptr(y_hi), L.ptr(y_lo), L.ptr(occ), int(reach), L.ptr(bg[0]), L.ptr(bg[1]),
+                                                        L.ptr(work), L.ptr(tile_state), (reset[0].data_ptr() if reset is not None else None),
+                                                        (int(reset[1]) if reset is not None else 0), ref, *tail, L.stream_ptr()),
+                    "conv2d_nhwc_split_sched")
+        del keep
+        return (y_hi, y_lo), None
     with L.device_guard(dev):
         # reset = (int32 tensor, words): OTHER call sites' counters this launch zeroes before its tiles run (words may be 0) instead
         # of resetting its own pair at its end (v3d_conv2d_nhwc_split; DenseHeadPlan.forward chains the layers)
@@ -700,12 +722,16 @@ class DenseHeadState(object):
     output planes per RPN layer that stays put from frame to frame, and per layer one word per 80-pixel tile saying whether the
     tile currently holds computed values (1) or the layer's empty-map response (0).  That response only depends on the weights
     (and, f16s, on the layer's scale entry): a background tile that was background in the frame before needs no write
-    (csrc/dense_conv.hip, DcParams::tile_state)."""
+    (csrc/dense_conv.hip, DcParams::tile_state).
+    The frame's TILE SCHEDULE lives here too: where the plan has a run of two or more consecutive 3x3 128 -> 128 layers, `sched_first`
+    is the first of them and `sched[i]` the tile list of each later one (at most 8) -- counts, live tiles, stale tiles
+    (csrc/dense_conv.hip, D2Sched): written by the first layer's launch, read by layer i's.  None: the layers draw their tiles."""
 
     def __init__(self, plan, device):
         self.device = device
         self.counters = torch.zeros(2 * len(plan.layers), dtype=torch.int32, device=device)
         self.key, self.out, self.tiles = None, None, None
+        self.sched_first, self.sched = None, None
 
     def ensure(self, plan, b, h, w):
         geom = (int(b), int(h), int(w), tuple(ly["cout"] for ly in plan.layers[:-1]))
@@ -716,6 +742,15 @@ class DenseHeadState(object):
             self.out = [split_planes_like(b, h, w, ly["cout"], self.device) for ly in plan.layers[:-1]]
             n = int(L.lib().v3d_conv2d_bg_tiles(int(b), int(h), int(w)))
             self.tiles = [torch.ones(n, dtype=torch.int32, device=self.device) for _ in plan.layers[:-1]]
+            words = [int(L.lib().v3d_conv2d_tile_sched_words(int(b), int(h), int(w), ly["cin"], ly["cout"], ly["k"])) for ly in plan.layers[:-1]]
+            first = next((i for i, n_w in enumerate(words) if n_w), None)
+            run = []
+            while first is not None and first + len(run) < len(words) and words[first + len(run)]:
+                run.append(first + len(run))
+            self.sched_first, self.sched = None, None
+            if len(run) >= 2:
+                self.sched_first = first
+                self.sched = {i: torch.zeros(words[i], dtype=torch.int32, device=self.device) for i in run[1:9]}
         else:  # new weights or scales: the planes stay where they are (captured graphs hold their addresses), nothing is in place
             for t in self.tiles:
                 t.fill_(1)
@@ -962,6 +997,12 @@ class DenseHeadPlan(object):
         # of a self-resetting pair; needs at least two launched skipping layers
         n_skip = len(self.layers) - 1 - (1 if fuse_tail else 0)
         chain = state is not None and occ is not None and n_skip >= 2
+        # ... and where the state holds a tile schedule, its first layer builds the lists the later ones run (DenseHeadState)
+        sched = state.sched if chain and state.sched else None
+        reaches, r = [], 0
+        for ly in self.layers[:-1]:
+            r += ly["k"] // 2
+            reaches.append(r)
         for i, ly in enumerate(self.layers[:-1]):
             last = i == len(self.layers) - 2
             if last and fuse_tail:
@@ -984,7 +1025,10 @@ class DenseHeadPlan(object):
                                            out=None if state is None else state.out[i],
                                            tile_state=None if state is None else state.tiles[i],
                                            reset=None if not chain else ((work[2:], work.numel() - 2) if i == 0 else (work, 2 if i == 1 else 0)),
-                                           pr=self._pr(i, in_entry, range_flag))
+                                           pr=self._pr(i, in_entry, range_flag),
+                                           sched=None if sched is None or (want_features and last) else
+                                           ("build", [reaches[j] for j in sched], [state.tiles[j] for j in sched], [sched[j] for j in sched])
+                                           if i == state.sched_first else ("run", sched[i]) if i in sched else None)
             feats = f if last else feats
         ly = self.layers[-1]
         if ly is None:
