@@ -128,6 +128,36 @@ int v3d_refine_nms(const float* deltas, const float* proposals, const float* con
                    int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace, size_t workspace_bytes,
                    v3d_stream_t stream);
 
+/* ---- IoU-weighted box voting (cfg.BOX_VOTING of vision3d_amd/core/config.py; box voting / weighted NMS / the DI-NMS of CIA-SSD, which
+ * upstream's tails -- detector/proposal.py:39-80, plain greedy NMS -- do not have).  boxes (G, T, 7) f32 = (x, y, z, w, l, h, yaw),
+ * scores (G, T) f32, out (G, T, 7) f32 (not `boxes`); a group is one (frame, class).  Every candidate k is voted as a centre by the
+ * candidates j of its own group (csrc/box_vote_device.h):
+ *   u_j = v3d_box_iou_rotated(b_k[0,1,3,4,6], b_j[0,1,3,4,6]), centre first, that operator's bits and angle convention;
+ *   j votes iff scores_j > 0, the seven components of b_j are finite and u_j >= iou_threshold (a NaN compares false);
+ *   w_j = scores_j * u_j, W = sum w_j;  out[c] = b_k[c] + sum w_j (b_j[c] - b_k[c]) / W for c = 0 .. 5,
+ *   out[6] = yaw_k + sum w_j wrap(yaw_j - yaw_k) / W, wrap(d) = d - pi * rintf(d / pi) with pi = (float)M_PI;
+ *   W not finite or not > 0: out = b_k with its own bits (the centre votes through its IoU with itself: no special case).
+ * fp32 throughout; the sums of a centre are taken in a fixed order (deterministic).  One launch, no workspace, no host
+ * synchronisation.  G * T < 2^31. */
+int v3d_box_voting(const float* boxes, const float* scores, int G, int T, float iou_threshold, float* out, v3d_stream_t stream);
+/* The two fused tails with that vote behind their NMS, ONE more launch each.  Selection, decode, scores, NMS and score cut are those of
+ * the entry without the vote and are decided on the un-voted boxes; out_batch_idx, out_class_idx, out_scores, *n_out, the order of
+ * the rows and (v3d_refine_nms_vote) `refined` have the bits of that entry.  Every out_boxes row is the vote of the candidates of its
+ * (frame, class) group at IoU >= vote_iou, weighted by the scores the NMS ranked by (the rectified score with_iou, sigmoid(conf) in
+ * stage 2; sentinel rows, score -1, do not vote).  Voted survivors may overlap again.
+ * v3d_proposals_vote_flag: head_maps of v3d_proposals_flag (with_dir = with_iou = 0), v3d_proposals_dir_flag (with_dir != 0) or
+ * v3d_proposals_iou_flag (with_iou != 0, iou_power as there; with_iou = 0 ignores it).  Workspace of both: v3d_proposals_vote_workspace. */
+size_t v3d_proposals_vote_workspace(int B, int n_cls, int topk);
+int v3d_proposals_vote_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                            const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                            int64_t* out_class_idx, float* out_scores, int32_t* n_out /*[2]*/, const int32_t* aux_flag,
+                            void* workspace, size_t workspace_bytes, v3d_stream_t stream, float dir_offset, int with_dir, int with_iou,
+                            int iou_power, float vote_iou);
+int v3d_refine_nms_vote(const float* deltas, const float* proposals, const float* conf, int B, int n_cls, int topk,
+                        const float* score_thresh_host, float iou_threshold, float* refined, float* out_boxes, int64_t* out_batch_idx,
+                        int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace, size_t workspace_bytes,
+                        v3d_stream_t stream, float vote_iou);
+
 /* ---- Training-mode BatchNorm1d (+ ReLU) over sparse features (n, C), C a power of two in [4, 256].
  * Replaces nn.BatchNorm1d(eps, momentum) + nn.ReLU on SparseConvTensor.features (detector/sparse_cnn.py:15-30) in
  * training: forward = chunk statistics (two-pass per chunk) + Chan merge in double + fused normalise/affine/ReLU;

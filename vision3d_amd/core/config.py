@@ -110,6 +110,15 @@ def _defaults():
         # positives / max(#positives, 1) times LOSS_WEIGHT; inference picks the TOPK of a (frame, class) by class score as before, then
         # ranks, suppresses and cuts by score * sigmoid(logit)^POWER (POWER an integer in 0 .. 8; 0: train the head, leave the scores alone)
         IOU_HEAD=dict(ENABLED=False, LOSS_WEIGHT=1.0, POWER=4),
+        # IoU-weighted box voting behind the rotated NMS tails (ops/box_voting.py, csrc/box_voting.hip; box voting / weighted NMS / the
+        # DI-NMS of CIA-SSD, the step those detectors pair with the rectified score of IOU_HEAD; not in the reference), opt-in: after
+        # greedy NMS every surviving box is replaced by the mean of the candidates j of its (frame, class) group with BEV IoU u_j >= IOU
+        # with it, weighted by s_j * u_j -- s_j the score the NMS ranked by --, as offsets from the survivor (yaw differences wrapped
+        # modulo pi: the survivor keeps its heading half).  Boxes move only: the NMS and the score cut decide on the un-voted boxes, and
+        # scores, indices, order and count stay; voted survivors may overlap again.  ProposalLayer's tails (Second; PV_RCNN's final
+        # tail, not its stage-1 proposals) apply it; the centre heatmap head refuses it.  IOU in (0, 1]; 0.3 is a hyper-parameter
+        # default, not a tuned value (no trained weights: the effect on AP is not measured)
+        BOX_VOTING=dict(ENABLED=False, IOU=0.3),
         # pillar feature encoder for SECOND (detector/pillar.py; the PFN layer of PointPillars, not in the reference), opt-in: with a voxel
         # as tall as the grid the voxelizer's slots are pillars; every point becomes [channels | xyz - pillar mean | xyz - pillar centre],
         # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
@@ -192,6 +201,21 @@ def iou_head_config(cfg):
     """-> the keys of cfg.IOU_HEAD over their defaults (a config written before the key existed means "disabled")."""
     out = dict(IOU_HEAD_DEFAULTS)
     out.update(cfg.get("IOU_HEAD") or {})
+    return out
+
+
+BOX_VOTING_DEFAULTS = dict(ENABLED=False, IOU=0.3)
+
+
+def box_voting_config(cfg):
+    """-> the keys of cfg.BOX_VOTING over their defaults (a config written before the key existed means "disabled"); an enabled key
+    whose IOU is not a finite real in (0, 1] is refused (a disabled one does not read it)."""
+    out = dict(BOX_VOTING_DEFAULTS)
+    out.update(cfg.get("BOX_VOTING") or {})
+    if out["ENABLED"]:
+        iou = out["IOU"]
+        if isinstance(iou, bool) or not isinstance(iou, (int, float)) or not math.isfinite(iou) or not 0 < iou <= 1:
+            raise ValueError(f"cfg.BOX_VOTING.IOU must be a finite real in (0, 1], got {iou!r}")
     return out
 
 

@@ -15,6 +15,17 @@ __device__ __forceinline__ float v3d_dpp_max_f32(float v) {
 #undef STEP
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), FULL ? 63 : 15));
 }
+// Wave64 fp32 sum on the same path (box_voting.hip).  A sum is not idempotent, so a lane whose DPP source is out of range, or whose
+// row a step does not write, must add ZERO: `old` is 0.0f.  The quad swaps give every lane its quad's sum; row_shr:4 and row_shr:8
+// leave the row's sum in its last quad; row_bcast:15 into rows 1 and 3 (row mask 0xa) and row_bcast:31 into rows 2 and 3 (0xc) carry
+// it on, and lane 63 holds the wave's sum, which every lane receives.  The order of the additions is fixed: the result is
+// deterministic.
+__device__ __forceinline__ float v3d_dpp_sum_f32(float v) {
+#define STEP(ctrl, rows) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), (rows), 0xf, false))
+  STEP(0xb1, 0xf); STEP(0x4e, 0xf); STEP(0x114, 0xf); STEP(0x118, 0xf); STEP(0x142, 0xa); STEP(0x143, 0xc);
+#undef STEP
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
 template <bool FULL>
 __device__ __forceinline__ int v3d_dpp_min_i32(int v) {
 #define STEP(ctrl) v = min(v, V3D_DPP_I(v, ctrl))

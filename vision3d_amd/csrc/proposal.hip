@@ -1,7 +1,8 @@
 // Fused proposal stage of the BEV head: sigmoid -> top-k per (frame, class) -> VoxelNet decode -> batched rotated
 // NMS -> per-class score cut, entirely on the device, no host synchronisation.  Launches: level-1 top-k | merge + decode + sort +
 // box prep (ONE workgroup when there are at most two (frame, class) groups, else merge and decode separately) | suppression mask |
-// greedy reduction + score cut = 4 at bs = 1 (6 until round 4).
+// greedy reduction + score cut = 4 at bs = 1 (6 until round 4).  The entries that vote their boxes (cfg.BOX_VOTING: v3d_proposals_vote_flag,
+// v3d_refine_nms_vote) put ONE launch of box_voting.hip in front of the last and let it copy its survivors from the voted candidates.
 //
 // Reference: vision3d/detector/proposal.py:39-80 (ProposalLayer.inference / _multiclass_batch_nms),
 // core/box_encode.py:13-21 (decode), ops/iou_nms.py:90-134 (coordinate-offset batched NMS).  The torch statement
@@ -596,6 +597,15 @@ extern "C" size_t v3d_proposals_workspace(int B, int n_cls, int topk) {
          prop_align(N * sizeof(v3d::BoxPrep)) + 1024;
 }
 
+// cfg.BOX_VOTING: the tails that vote (v3d_proposals_vote_flag, v3d_refine_nms_vote) keep the voted copy of the N candidates behind the
+// workspace of the tail without the vote, whose layout and size stay as they are.
+extern "C" size_t v3d_proposals_vote_workspace(int B, int n_cls, int topk) {
+  return v3d_proposals_workspace(B, n_cls, topk) + prop_align((size_t)B * n_cls * topk * 7 * 4);
+}
+static float* prop_voted(void* workspace, int B, int n_cls, int topk) {
+  return (float*)((char*)workspace + v3d_proposals_workspace(B, n_cls, topk));  // (a multiple of 256 bytes)
+}
+
 extern "C" int v3d_proposals(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W,
                              int topk, const float* score_thresh_host, float iou_threshold, float* out_boxes,
                              int64_t* out_batch_idx, int64_t* out_class_idx, float* out_scores, int32_t* n_out,
@@ -609,7 +619,8 @@ extern "C" int v3d_proposals(const float* head_maps, const float* anchors, int B
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores, bool dir = false, float dir_offset = 0.f, bool iou = false, int iou_power = 0);
+                    float* topk_boxes, float* topk_scores, bool dir = false, float dir_offset = 0.f, bool iou = false, int iou_power = 0,
+                    bool vote = false, float vote_iou = 0.f);
 
 extern "C" int v3d_proposals_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W,
                                   int topk, const float* score_thresh_host, float iou_threshold, float* out_boxes,
@@ -670,10 +681,26 @@ extern "C" int v3d_proposals_iou_topk(const float* head_maps, const float* ancho
                   workspace_bytes, stream, boxes, scores, with_dir != 0, dir_offset, true, iou_power);
 }
 
+// The stage with IoU-weighted box voting behind its NMS (cfg.BOX_VOTING; box_voting.hip, box_vote_device.h): the maps of
+// v3d_proposals_flag (with_dir = with_iou = 0), of v3d_proposals_dir_flag (with_dir) or of v3d_proposals_iou_flag (with_iou), and the
+// same selection, decode, scores, NMS and score cut -- decided on the un-voted boxes --, then every returned box is the vote of its
+// group's candidates at IoU >= vote_iou, weighted by the scores the NMS ranked by.  Scores, indices, order and count are those of the
+// entry without the vote; ONE more launch; workspace: v3d_proposals_vote_workspace.
+extern "C" int v3d_proposals_vote_flag(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
+                                       const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx,
+                                       int64_t* out_class_idx, float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace,
+                                       size_t workspace_bytes, v3d_stream_t stream, float dir_offset, int with_dir, int with_iou, int iou_power,
+                                       float vote_iou) {
+  if (!score_thresh_host || !out_boxes || !out_batch_idx || !out_class_idx || !out_scores || !n_out) return V3D_EINVAL;
+  return prop_run(head_maps, anchors, B, n_cls, n_yaw, H, W, topk, score_thresh_host, iou_threshold, out_boxes, out_batch_idx, out_class_idx,
+                  out_scores, n_out, aux_flag, workspace, workspace_bytes, stream, nullptr, nullptr, with_dir != 0, dir_offset, with_iou != 0,
+                  with_iou ? iou_power : 0, true, vote_iou);
+}
+
 static int prop_run(const float* head_maps, const float* anchors, int B, int n_cls, int n_yaw, int H, int W, int topk,
                     const float* score_thresh_host, float iou_threshold, float* out_boxes, int64_t* out_batch_idx, int64_t* out_class_idx,
                     float* out_scores, int32_t* n_out, const int32_t* aux_flag, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
-                    float* topk_boxes, float* topk_scores, bool dir, float dir_offset, bool iou, int iou_power) {
+                    float* topk_boxes, float* topk_scores, bool dir, float dir_offset, bool iou, int iou_power, bool vote, float vote_iou) {
   hipStream_t st = (hipStream_t)stream;
   if (!head_maps || !anchors || !workspace) return V3D_EINVAL;
   if (B < 1 || n_cls < 1 || n_cls > PROP_MAX_CLS || n_yaw < 1 || H < 1 || W < 1 || topk < 1 || topk > PROP_MAX_TOPK)
@@ -682,7 +709,7 @@ static int prop_run(const float* head_maps, const float* anchors, int B, int n_c
   // torch.topk raises as well.  (The cfg.IOU_HEAD entries take such a map: both selection levels pad a short range with (score -1,
   // anchor -1) sentinels, which keep their score, decode the clamped anchor 0, sort last and fall at the score cut.)
   if ((long long)n_yaw * H * W < topk && !iou) return V3D_EINVAL;
-  if (workspace_bytes < v3d_proposals_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
+  if (workspace_bytes < (vote ? v3d_proposals_vote_workspace(B, n_cls, topk) : v3d_proposals_workspace(B, n_cls, topk))) return V3D_EWORKSPACE;
   PropGeom g;
   if (iou && (iou_power < 0 || iou_power > 8)) return V3D_EINVAL;
   g.B = B; g.n_cls = n_cls; g.n_yaw = n_yaw; g.HW = H * W; g.topk = topk; g.ctot = n_cls * n_yaw * ((dir ? 9 : 8) + (iou ? 1 : 0));
@@ -737,8 +764,15 @@ static int prop_run(const float* head_maps, const float* anchors, int B, int n_c
     unsigned long long* mask = (unsigned long long*)nms_ws;  // N*nwords + nwords words <= v3d_nms_rotated_workspace(N)
     const int rc = v3d_i_nms_mask_sorted(prep, (int)N, iou_threshold, mask, st);
     if (rc != V3D_OK) return rc;
+    const float* out_src = boxes;
+    if (vote) {  // v3d_proposals_vote_flag: one more launch; the NMS above and the score cut below decide on the un-voted boxes
+      float* voted = prop_voted(workspace, B, n_cls, topk);
+      const int rv = v3d_i_box_voting(boxes, cand_score, B * n_cls, topk, vote_iou, voted, st);
+      if (rv != V3D_OK) return rv;
+      out_src = voted;
+    }
     hipLaunchKernelGGL(prop_nms_reduce_finalize_kernel, dim3(1), dim3(PROP_NMS_THREADS), 0, st, mask, order, (int)N, mask + N * nwords,
-                       keep, g, boxes, bidx, cidx, cand_score, out_boxes, (long long*)out_batch_idx, (long long*)out_class_idx,
+                       keep, g, out_src, bidx, cidx, cand_score, out_boxes, (long long*)out_batch_idx, (long long*)out_class_idx,
                        out_scores, n_out, aux_flag);
   }
   (void)bev;
@@ -753,17 +787,17 @@ static int prop_run(const float* head_maps, const float* anchors, int B, int n_c
 // the candidates arrive in the layout v3d_proposals_topk produces ((B, n_cls, topk) group-major).  3 launches, no host sync.
 extern "C" size_t v3d_refine_nms_workspace(int B, int n_cls, int topk) { return v3d_proposals_workspace(B, n_cls, topk); }
 
-extern "C" int v3d_refine_nms(const float* deltas, const float* proposals, const float* conf, int B, int n_cls, int topk,
-                              const float* score_thresh_host, float iou_threshold, float* refined, float* out_boxes, int64_t* out_batch_idx,
-                              int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace, size_t workspace_bytes,
-                              v3d_stream_t stream) {
+static int refine_run(const float* deltas, const float* proposals, const float* conf, int B, int n_cls, int topk,
+                      const float* score_thresh_host, float iou_threshold, float* refined, float* out_boxes, int64_t* out_batch_idx,
+                      int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace, size_t workspace_bytes, v3d_stream_t stream,
+                      bool vote, float vote_iou) {
   hipStream_t st = (hipStream_t)stream;
   if (!deltas || !proposals || !conf || !score_thresh_host || !out_boxes || !out_batch_idx || !out_class_idx || !out_scores || !n_out ||
       !workspace)
     return V3D_EINVAL;
   if (B < 1 || n_cls < 1 || n_cls > PROP_MAX_CLS || topk < 1 || topk > PROP_MAX_TOPK) return V3D_EINVAL;
   if ((long long)B * n_cls * topk > PROP_THREADS) return V3D_EUNSUPPORTED;  // one workgroup decodes and sorts all candidates
-  if (workspace_bytes < v3d_refine_nms_workspace(B, n_cls, topk)) return V3D_EWORKSPACE;
+  if (workspace_bytes < (vote ? v3d_proposals_vote_workspace(B, n_cls, topk) : v3d_refine_nms_workspace(B, n_cls, topk))) return V3D_EWORKSPACE;
   PropGeom g;
   g.B = B; g.n_cls = n_cls; g.n_yaw = 1; g.HW = 1; g.topk = topk; g.ctot = 0; g.dir_base = -1; g.dir_offset = 0.f;
   g.iou_base = -1; g.iou_power = 0; g.iou_order = 0;
@@ -784,9 +818,35 @@ extern "C" int v3d_refine_nms(const float* deltas, const float* proposals, const
   const size_t nwords = (N + 63) / 64;
   const int rc = v3d_i_nms_mask_sorted(prep, (int)N, iou_threshold, mask, st);
   if (rc != V3D_OK) return rc;
+  const float* out_src = boxes;
+  if (vote) {  // v3d_refine_nms_vote: one more launch; `refined` (= boxes) stays the un-voted decode
+    float* voted = prop_voted(workspace, B, n_cls, topk);
+    const int rv = v3d_i_box_voting(boxes, scores, B * n_cls, topk, vote_iou, voted, st);
+    if (rv != V3D_OK) return rv;
+    out_src = voted;
+  }
   hipLaunchKernelGGL(prop_nms_reduce_finalize_kernel, dim3(1), dim3(PROP_NMS_THREADS), 0, st, mask, order, (int)N, mask + N * nwords, keep, g,
-                     boxes, bidx, cidx, scores, out_boxes, (long long*)out_batch_idx, (long long*)out_class_idx, out_scores, n_out,
+                     out_src, bidx, cidx, scores, out_boxes, (long long*)out_batch_idx, (long long*)out_class_idx, out_scores, n_out,
                      (const int*)nullptr);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
+}
+
+extern "C" int v3d_refine_nms(const float* deltas, const float* proposals, const float* conf, int B, int n_cls, int topk,
+                              const float* score_thresh_host, float iou_threshold, float* refined, float* out_boxes, int64_t* out_batch_idx,
+                              int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace, size_t workspace_bytes,
+                              v3d_stream_t stream) {
+  return refine_run(deltas, proposals, conf, B, n_cls, topk, score_thresh_host, iou_threshold, refined, out_boxes, out_batch_idx, out_class_idx,
+                    out_scores, n_out, workspace, workspace_bytes, stream, false, 0.f);
+}
+
+// The same tail with IoU-weighted box voting behind its NMS (cfg.BOX_VOTING): the returned boxes are the votes of their group's refined
+// candidates at IoU >= vote_iou, weighted by sigmoid(conf); `refined`, scores, indices, order and count are v3d_refine_nms's.  ONE more
+// launch; workspace: v3d_proposals_vote_workspace.
+extern "C" int v3d_refine_nms_vote(const float* deltas, const float* proposals, const float* conf, int B, int n_cls, int topk,
+                                   const float* score_thresh_host, float iou_threshold, float* refined, float* out_boxes,
+                                   int64_t* out_batch_idx, int64_t* out_class_idx, float* out_scores, int32_t* n_out, void* workspace,
+                                   size_t workspace_bytes, v3d_stream_t stream, float vote_iou) {
+  return refine_run(deltas, proposals, conf, B, n_cls, topk, score_thresh_host, iou_threshold, refined, out_boxes, out_batch_idx, out_class_idx,
+                    out_scores, n_out, workspace, workspace_bytes, stream, true, vote_iou);
 }

@@ -87,6 +87,9 @@ int v3d_i_nms_sorted(const void* prep_sorted, const int* order, int N, float iou
 
 int v3d_i_nms_mask_sorted(const void* prep_sorted, int N, float iou_threshold, unsigned long long* mask, hipStream_t st);
 
+// box_voting.hip: v3d_box_voting on checked pointers (the fused tails of proposal.hip vote their candidates with it): one launch
+int v3d_i_box_voting(const float* boxes, const float* scores, int G, int T, float iou, float* out, hipStream_t st);
+
 // cell_grid.hip: the points of every (job, frame) binned into a cell grid (cell_grid_device.h: layout, shape rule), one launch.
 // The caller has checked its arguments: 1 <= n_jobs <= V3D_CELL_GRID_MAX_JOBS, B >= 1, N >= 1, cell_min > 0 and finite.
 #define V3D_CELL_GRID_MAX_JOBS 8

@@ -89,6 +89,8 @@ class CenterHead(nn.Module):
         refuse_direction(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED regresses sin / cos of the yaw itself)")
         from .proposal import refuse_iou_head
         refuse_iou_head(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED has no anchors to rate)")
+        from .proposal import refuse_box_voting
+        refuse_box_voting(cfg, "the centre heatmap head (cfg.CENTERHEAD.ENABLED decodes through its own fused NMS)")
         self.cfg = cfg
         self.opt = centerhead_config(cfg)
         if len(self.opt["CODE_WEIGHTS"]) != 8:

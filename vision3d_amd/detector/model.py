@@ -601,6 +601,7 @@ class PV_RCNN(nn.Module):
         class_idx = item["proposal_class"].repeat(b)
         n_cls = self.cfg.NUM_CLASSES
         keep = batched_nms_rotated(boxes[:, [0, 1, 3, 4, 6]].contiguous(), scores, class_idx + n_cls * batch_idx, 0.01)
+        boxes = self.proposal_layer._voted(boxes, scores, b * n_cls)  # cfg.BOX_VOTING: what v3d_refine_nms_vote does on the native tail
         boxes, batch_idx, class_idx, scores = (x[keep] for x in (boxes, batch_idx, class_idx, scores))
         mask = self.proposal_layer._above_score_thresh(scores, class_idx)
         return [x[mask] for x in (boxes, batch_idx, class_idx, scores)]

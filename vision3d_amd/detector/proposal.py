@@ -15,6 +15,12 @@ cfg.IOU_HEAD (opt-in, not in the reference): an IoU-aware confidence, the rectif
 map) trained towards the rotated 3-D IoU of the anchor's decoded box with its object (ProposalLoss.iou_targets, iou_loss); inference
 selects the TOPK of a (frame, class) by class score as before and then ranks, suppresses and cuts by `rectified_scores`.
 Definition: DESIGN.md section 7, tests/iou_head_ref.py.
+
+cfg.BOX_VOTING (opt-in, not in the reference): IoU-weighted box voting behind the NMS of every tail here -- `native_proposals`
+(v3d_proposals_vote_flag) and `native_refine_nms` (v3d_refine_nms_vote) in one more launch each, the torch statements
+(`inference_from_maps`, `proposals_padded` + `finalize`) through ops.box_voting_statement.  Boxes move only: scores, indices, order and
+count are those of the tail without the vote.  `native_topk` runs no NMS and does not vote.  Definition: DESIGN.md section 7,
+ops/box_voting.py, tests/box_voting_ref.py.
 """
 import math
 
@@ -24,7 +30,7 @@ from torch import nn
 
 from .. import _lib as L
 from ..core.box_encode import decode
-from ..core.config import iou_head_config
+from ..core.config import box_voting_config, iou_head_config
 from ..core.proposal_targets import direction_config
 from ..ops import batched_nms_rotated, batched_nms_rotated_padded, sigmoid_focal_loss
 from ..stamp import cached
@@ -61,6 +67,24 @@ def checked_iou_head(cfg):
             raise ValueError(f"cfg.IOU_HEAD.POWER must be an integer in 0 .. 8 (0: the scores stay as they are), got {power!r}")
         if cfg.BOX_DOF != 7:
             raise ValueError("cfg.IOU_HEAD.ENABLED: the IoU target is defined for 7-DOF boxes (cfg.BOX_DOF)")
+    return opt
+
+
+def box_voting_enabled(cfg):
+    return bool(box_voting_config(cfg)["ENABLED"])
+
+
+def refuse_box_voting(cfg, what):
+    """The heads whose decode runs its own fused NMS say so instead of ignoring the key."""
+    if box_voting_enabled(cfg):
+        raise ValueError(f"cfg.BOX_VOTING.ENABLED: {what} does not vote its boxes yet (the tails of ProposalLayer do)")
+
+
+def checked_box_voting(cfg):
+    """cfg.BOX_VOTING over its defaults (core.config.box_voting_config validates IOU), refused where the vote is not defined."""
+    opt = box_voting_config(cfg)
+    if opt["ENABLED"] and cfg.BOX_DOF != 7:
+        raise ValueError("cfg.BOX_VOTING.ENABLED: the vote is defined for 7-DOF boxes (cfg.BOX_DOF)")
     return opt
 
 
@@ -141,6 +165,7 @@ class ProposalLayer(nn.Module):
         self.TOPK, self.DOF = cfg.PROPOSAL.TOPK, cfg.BOX_DOF
         self.direction = direction_config(cfg)
         self.iou_head = checked_iou_head(cfg)
+        self.box_voting = checked_box_voting(cfg)
         self._init_weights()
         if self.direction["ENABLED"]:
             # cfg.DIRECTION (opt-in): one more logit per anchor, the half turn the wrapped yaw residual cannot carry.  Built behind the
@@ -181,9 +206,19 @@ class ProposalLayer(nn.Module):
         bev = boxes[:, [0, 1, 3, 4, 6]].contiguous()
         batch_idx, class_idx, group_idx = self._generate_group_idx(B, n_cls, scores.device)
         keep = batched_nms_rotated(bev, scores, group_idx, iou_threshold=0.01)
+        boxes = self._voted(boxes, scores, B * n_cls)
         boxes, batch_idx, class_idx, scores = (x[keep] for x in (boxes, batch_idx, class_idx, scores))
         mask = self._above_score_thresh(scores, class_idx)
         return [x[mask] for x in (boxes, batch_idx, class_idx, scores)]
+
+    def _voted(self, boxes, scores, n_groups):
+        """cfg.BOX_VOTING in the torch statements: the (N, 7) group-major candidates, every one voted by its group (the NMS has been
+        decided on `boxes` as they came; the keep list then selects voted rows); without the key: `boxes` itself."""
+        if not self.box_voting["ENABLED"]:
+            return boxes
+        from ..ops.box_voting import box_voting_statement
+        shape = (n_groups, boxes.shape[0] // n_groups)
+        return box_voting_statement(boxes.reshape(*shape, 7), scores.reshape(shape), self.box_voting["IOU"]).reshape(-1, 7)
 
     def _dir_map(self, dir_map):
         """The direction map a decode of this head needs: None for a head without the classifier, else required."""
@@ -270,7 +305,7 @@ class ProposalLayer(nn.Module):
         # column select without a host-built index tensor (an H2D copy is illegal during graph capture)
         bev = torch.stack((boxes[:, 0], boxes[:, 1], boxes[:, 3], boxes[:, 4], boxes[:, 6]), dim=1)
         keep, n_keep = batched_nms_rotated_padded(bev, scores, group_idx, 0.01)
-        return boxes, batch_idx, class_idx, scores, keep, n_keep
+        return self._voted(boxes, scores, B * n_cls), batch_idx, class_idx, scores, keep, n_keep
 
     def native_supported(self, batch_size, anchors_per_class=None):
         """csrc/proposal.hip sorts the candidates of all (frame, class) groups in one workgroup (<= 1024 of them) and
@@ -313,11 +348,15 @@ class ProposalLayer(nn.Module):
         else:
             n_out = torch.empty((1 if overflow_flag is None else 2,), dtype=torch.int32, device=dev)  # written by the last kernel
         lib = L.lib()
-        ws = L.workspace(lib.v3d_proposals_workspace(B, n_cls, self.TOPK), dev)
+        vote = bool(self.box_voting["ENABLED"])     # cfg.BOX_VOTING: v3d_proposals_vote_flag takes any of the three maps and votes
+        ws = L.workspace((lib.v3d_proposals_vote_workspace if vote else lib.v3d_proposals_workspace)(B, n_cls, self.TOPK), dev)
         thresh = L.host_f32([a["score_thresh"] for a in cfg.ANCHORS[:n_cls]])
         entry, extra = (lib.v3d_proposals_dir_flag, (float(self.direction["OFFSET"]),)) if with_dir else (lib.v3d_proposals_flag, ())
         if with_iou:
             entry, extra = lib.v3d_proposals_iou_flag, (float(self.direction["OFFSET"]), int(with_dir), int(self.iou_head["POWER"]))
+        if vote:
+            entry, extra = lib.v3d_proposals_vote_flag, (float(self.direction["OFFSET"]), int(with_dir), int(with_iou),
+                                                         int(self.iou_head["POWER"]), float(self.box_voting["IOU"]))
         with L.device_guard(dev):
             L.check(entry(L.ptr(maps), L.ptr(anc), B, n_cls, n_yaw, H, W, self.TOPK, thresh, 0.01, L.ptr(boxes),
                           L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(overflow_flag),
@@ -369,12 +408,14 @@ class ProposalLayer(nn.Module):
         scores = torch.empty((N,), dtype=torch.float32, device=dev)
         n_out = torch.empty((1,), dtype=torch.int32, device=dev)
         lib = L.lib()
-        ws = L.workspace(lib.v3d_refine_nms_workspace(B, n_cls, self.TOPK), dev)
+        vote = bool(self.box_voting["ENABLED"])  # cfg.BOX_VOTING: v3d_refine_nms_vote -- `refined` stays the un-voted decode
+        ws = L.workspace((lib.v3d_proposals_vote_workspace if vote else lib.v3d_refine_nms_workspace)(B, n_cls, self.TOPK), dev)
         thresh = L.host_f32([a["score_thresh"] for a in cfg.ANCHORS[:n_cls]])
+        entry, extra = (lib.v3d_refine_nms_vote, (float(self.box_voting["IOU"]),)) if vote else (lib.v3d_refine_nms, ())
         with L.device_guard(dev):
-            L.check(lib.v3d_refine_nms(L.ptr(d), L.ptr(p), L.ptr(c), B, n_cls, self.TOPK, thresh, float(iou_threshold), L.ptr(refined),
-                                       L.ptr(boxes), L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(ws), ws.numel(),
-                                       L.stream_ptr()), "refine_nms")
+            L.check(entry(L.ptr(d), L.ptr(p), L.ptr(c), B, n_cls, self.TOPK, thresh, float(iou_threshold), L.ptr(refined),
+                          L.ptr(boxes), L.ptr(batch_idx), L.ptr(class_idx), L.ptr(scores), L.ptr(n_out), L.ptr(ws), ws.numel(),
+                          L.stream_ptr(), *extra), "refine_nms")
         if not finalize:
             return refined, (boxes, batch_idx, class_idx, scores, n_out)
         return refined, self.finalize_native(boxes, batch_idx, class_idx, scores, n_out)

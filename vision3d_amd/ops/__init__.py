@@ -8,6 +8,7 @@ _EXPORTS = {
     "box_iou_rotated": "iou_nms", "box_iou_rotated_3d": "iou_nms", "nms": "iou_nms", "nms_rotated": "iou_nms",
     "batched_nms": "iou_nms", "batched_nms_rotated": "iou_nms",
     "nms_rotated_padded": "iou_nms", "batched_nms_rotated_padded": "iou_nms",
+    "box_voting_rotated": "box_voting", "box_voting_statement": "box_voting",
     "iou3d_loss": "iou_loss", "box_iou3d_aligned": "iou_loss", "iou3d_loss_torch": "iou_loss",
 }
 __all__ = sorted(_EXPORTS)
