@@ -1026,6 +1026,29 @@ int v3d_pillar_dynamic_train_bwd(const float* points, const int32_t* point_voxel
                                  const double* moments, float* dW, float* d_gamma, float* d_beta, void* workspace,
                                  size_t workspace_bytes, v3d_stream_t stream);
 
+/* ---- The pillar encoder writing the dense head's input itself (opt-in, cfg.PILLAR.PLAN; runtime.PillarPlan; no upstream counterpart):
+ * v3d_pillar_encode whose rows never reach memory as fp32 -- no (M, channels) rows, no canvas, no v3d_nchw_to_split_nhwc.
+ * features (cap, P, C), occupancy (cap), coordinates (cap, 4) as above, but the row count is *n_voxels in DEVICE memory: rows
+ * m < min(max(*n_voxels, 0), cap) count (the grid is sized from cap; no host read).  For each of them the `channels` numbers are bit
+ * for bit those of v3d_pillar_encode; every number is stored as the hi / lo 16-bit pieces of `prec` (csrc/split_prec.h; V3D_PREC_F16S:
+ * of value * act_entry[0]) in out_hi / out_lo (B, H, W, channels) at pixel (b, y, x) = coordinates[m][0, 2, 3] -- the z index is ignored,
+ * as PillarFeatureNet's canvas ignores it -- and bit (b * H + y, x) of occ, the INVERTED bitmap in the layout of
+ * v3d_bev_occupancy_bits, is cleared.  V3D_PREC_F16S: a magnitude beyond act_entry[2] raises *range_flag (nullable) to 2 (atomicMax).
+ * A row whose (b, y, x) lies outside the map is skipped: nothing of it is stored or marked.  Several rows on one pixel (the
+ * voxelizer produces none): one of them wins each 2-byte store.  The planes are written at the rows' pixels only -- the caller
+ * zeroes the rest -- and occ is the caller's to reset: v3d_pillar_planes_clear does both.
+ * Limits: those of v3d_pillar_encode with channels == 128 -- beyond them V3D_EUNSUPPORTED before any launch; cap == 0 launches nothing.
+ * One launch on the caller's stream.
+ * _planes_clear (one launch, in front of _encode_planes on the same stream): occ back to all ones, *flag (nullable) to 0 and, where
+ * prev_coordinates is not NULL, the pixels of the rows m < min(max(*prev_n, 0), cap) of that list zeroed in both planes (16-byte
+ * aligned) -- the start of a frame on PERSISTENT planes, which then need no fill: a pixel of both frames ends on the new values. */
+int v3d_pillar_encode_planes(const float* features, const int32_t* occupancy, const int32_t* coordinates, const int32_t* n_voxels, int cap,
+                             int P, int C, const float* geometry_host, const float* W, int channels, const float* scale,
+                             const float* shift, int B, int H, int Wd, int prec, const float* act_entry, int32_t* range_flag,
+                             void* out_hi, void* out_lo, uint32_t* occ, v3d_stream_t stream);
+int v3d_pillar_planes_clear(const int32_t* prev_coordinates, const int32_t* prev_n, int cap, int B, int H, int Wd, int channels,
+                            void* out_hi, void* out_lo, uint32_t* occ, int32_t* flag, v3d_stream_t stream);
+
 /* ---- Training plan: the sparse half of a train step (train.py:63-67 through detector/second.py:41-46 and
  * detector/sparse_cnn.py:15-30,151-175) as ONE call forwards and ONE call backwards, no host synchronisation.
  * Every layer must be conv + BatchNorm1d (training mode: batch statistics) [+ ReLU] with a power-of-two Cout in [4, 256].

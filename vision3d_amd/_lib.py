@@ -176,6 +176,8 @@ _SIGNATURES = {
     "v3d_pillar_dynamic_train_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "v3d_pillar_dynamic_train_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                           _vp]),
+    "v3d_pillar_encode_planes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "v3d_pillar_planes_clear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "v3d_conv2d_weight_image_bytes": (_sz, [_i, _i, _i]),
     "v3d_densify_nhwc_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "v3d_split_nhwc_to_nchw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),

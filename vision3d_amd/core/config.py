@@ -124,8 +124,12 @@ def _defaults():
         # linear -> BatchNorm1d over all slots -> ReLU -> maximum per pillar gives CHANNELS numbers per occupied BEV cell, scattered
         # straight into the map the dense RPN reads (no sparse 3-D backbone; the dense plans are 128 wide, so Second takes CHANNELS=128).
         # DYNAMIC (inert unless ENABLED; DynamicPillarFeatureNet, the DynamicPillarVFE of MVF): the Preprocessor voxelizes dynamically and
-        # ignores MAX_OCCUPANCY, EVERY point of a pillar enters the maximum and the BatchNorm statistics (no padded rows); same parameters
-        PILLAR=dict(ENABLED=False, CHANNELS=128, DYNAMIC=False),
+        # ignores MAX_OCCUPANCY, EVERY point of a pillar enters the maximum and the BatchNorm statistics (no padded rows); same parameters.
+        # PLAN (inert unless ENABLED; runtime.PillarPlan, inference only): the raw-point entry points of Second -- inference_points, the
+        # captured-graph and pipelined runners, bev / head maps from points -- run on a native plan (voxelizer + an encode kernel that
+        # writes the dense head's split planes, occupancy bitmap and range flag itself, no host read) instead of refusing the pillar
+        # encoder; forward / inference on a Preprocessor item are untouched; refused together with DYNAMIC (a follow-up)
+        PILLAR=dict(ENABLED=False, CHANNELS=128, DYNAMIC=False, PLAN=False),
         # dynamic voxelization (csrc/voxelize.hip "DYNAMIC"; MVF / DynamicScatter, not in the reference), opt-in: a voxel takes EVERY point
         # inside it instead of the first MAX_OCCUPANCY in input order -- same cells, same row order, `occupancy` = the true counts,
         # `voxel_mean` an order-independent mean (integer sums of the values scaled by 2^24), a `point_voxel` map and no `features` slot
@@ -233,6 +237,17 @@ def pillar_dynamic_enabled(cfg):
     return bool(opt.get("ENABLED", False)) and bool(opt.get("DYNAMIC", False))
 
 
+def pillar_plan_enabled(cfg):
+    """cfg.PILLAR.ENABLED and cfg.PILLAR.PLAN (a config written before the key existed means "off": the raw-point entry points refuse
+    the pillar encoder).  Together with cfg.PILLAR.DYNAMIC it is refused."""
+    opt = cfg.get("PILLAR") or {}
+    on = bool(opt.get("ENABLED", False)) and bool(opt.get("PLAN", False))
+    if on and bool(opt.get("DYNAMIC", False)):
+        raise ValueError("cfg.PILLAR.PLAN together with cfg.PILLAR.DYNAMIC: the plan runs the hard pillar encoder; the dynamic encoder "
+                         "is a follow-up -- its encode kernel is the slower of the two (DESIGN.md section 7)")
+    return on
+
+
 def second_car_cfg():
     return _defaults().merge_from_dict(copy.deepcopy(SECOND_CAR))
 
@@ -243,6 +258,10 @@ def pillar_car_cfg():
 
 def pillar_dynamic_car_cfg():
     return pillar_car_cfg().merge_from_dict(dict(PILLAR=dict(DYNAMIC=True)))
+
+
+def pillar_plan_car_cfg():
+    return pillar_car_cfg().merge_from_dict(dict(PILLAR=dict(PLAN=True)))
 
 
 def waymo_range_cfg():

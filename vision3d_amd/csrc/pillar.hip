@@ -12,9 +12,12 @@
 //                          reduction across lanes); the four waves' sums are added in wave order: one partial per workgroup.
 //   pillar_bwd_final_kernel  a workgroup per channel: partials in workgroup order, then the closed forms of pillar_device.h.
 // No atomics: every sum has one fixed order for a given M, so two runs agree bit for bit.  No host synchronisation.
-// The dynamic encoder (cfg.PILLAR.DYNAMIC: the pillars of the dynamic voxelizer, every point counts) follows at the end of the file.
+// The dynamic encoder (cfg.PILLAR.DYNAMIC: the pillars of the dynamic voxelizer, every point counts) follows behind them, and the
+// plan's front (cfg.PILLAR.PLAN: the hard encoder writing the dense head's split planes itself) at the end of the file.
 #include "pillar_device.h"
+#include "pillar_plane_device.h"
 #include "scan_device.h"
+#include "split_prec.h"
 #include "v3d_internal.h"
 
 #define PL_WAVES (V3D_BLOCK / V3D_WAVE)
@@ -75,6 +78,27 @@ __device__ __forceinline__ void pl_read_row(const float* slab, int p, float* f) 
   for (int k = 0; k < K; k++) f[k] = t[k];
 }
 
+// The maximum of a staged pillar (n live rows in the slab, P slots) over the NCH channels a lane owns: rows 0 .. n-1 in order, then the
+// padded candidate where n < P (pillar_device.h, the winner rule).
+template <int K, int NCH>
+__device__ __forceinline__ void pl_pillar_max(const float* slab, int n, int P, const float (*w)[K], const float* sc, const float* sh, float* best,
+                                              int* win) {
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    best[j] = -1.f;
+    win[j] = -1;
+  }
+  for (int p = 0; p < n; p++) {
+    float f[K];
+    pl_read_row<K>(slab, p, f);
+    v3d::pillar_offer_row<K, NCH>(f, p, w, sc, sh, best, win);
+  }
+  if (n < P) {
+#pragma unroll
+    for (int j = 0; j < NCH; j++) v3d::pillar_offer(v3d::pillar_activation(0.f, sc[j], sh[j]), -1, best[j], win[j]);
+  }
+}
+
 template <int C, int NCH>
 __global__ __launch_bounds__(V3D_BLOCK) void pillar_encode_kernel(const float* __restrict__ feat, const int32_t* __restrict__ occ,
                                                                   const int32_t* __restrict__ coords, int M, int P, PillarGeom g,
@@ -101,19 +125,7 @@ __global__ __launch_bounds__(V3D_BLOCK) void pillar_encode_kernel(const float* _
     if (m < M) {
       float best[NCH];
       int win[NCH];
-#pragma unroll
-      for (int j = 0; j < NCH; j++) {
-        best[j] = -1.f;
-        win[j] = -1;
-      }
-      for (int p = 0; p < n; p++) {
-        pl_read_row<K>(slab, p, f);
-        v3d::pillar_offer_row<K, NCH>(f, p, w, sc, sh, best, win);
-      }
-      if (n < P) {
-#pragma unroll
-        for (int j = 0; j < NCH; j++) v3d::pillar_offer(v3d::pillar_activation(0.f, sc[j], sh[j]), -1, best[j], win[j]);
-      }
+      pl_pillar_max<K, NCH>(slab, n, P, w, sc, sh, best, win);
 #pragma unroll
       for (int j = 0; j < NCH; j++) {
         rows[(size_t)m * CH + lane + 64 * j] = best[j];
@@ -746,6 +758,135 @@ extern "C" int v3d_pillar_dynamic_train_bwd(const float* points, const int32_t* 
   V3D_CHECK_LAUNCH();
   hipLaunchKernelGGL(pillar_bwd_final_kernel, dim3(channels), dim3(64), 0, st, (const double*)partials, groups, C + 6, channels, 0.0, 1, moments,
                      W, gamma, eps, dW, d_gamma, d_beta);
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the plan's front
+// cfg.PILLAR.PLAN (runtime.PillarPlan): raw points -> the dense head's input without the (M, CH) rows, the fp32 canvas and its split.
+//   pillar_encode_planes_kernel  pillar_encode_kernel whose wave, instead of its output row, writes the row's hi / lo 16-bit pieces
+//                                (split_prec.h split_one: what v3d_nchw_to_split_nhwc writes for the same number) at the pillar's pixel
+//                                of the two NHWC planes -- a lane owns channels lane and lane + 64, so the wave stores four 128-byte
+//                                runs --, clears the pixel's bit of the inverted occupancy bitmap and, f16s, raises the range flag.
+//                                The row count is read on the device: the grid is sized from the capacity.
+//   pillar_planes_clear_kernel   start of a frame: the bitmap back to 0xFF, the summary word to 0 and -- PERSISTENT planes -- the
+//                                pixels of the list the previous frame kept zeroed with 16-byte stores (no 2 x 9 MB fill per frame).
+//                                A launch of its own in front of the stores above: a pixel of both frames ends on the new values.
+// Where a row lands: pillar_plane_device.h.  Several rows on one pixel (a hand-fed list): one of them wins each 2-byte store.
+#define PP_CH 128
+#define PP_UNITS (PP_CH * 2 / 16)  // 16-byte units per pixel and plane
+
+namespace {
+
+template <int C, int PREC>
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_encode_planes_kernel(const float* __restrict__ feat, const int32_t* __restrict__ occ,
+                                                                         const int32_t* __restrict__ coords, const int32_t* __restrict__ n_ptr,
+                                                                         int cap, int P, PillarGeom g, const float* __restrict__ W,
+                                                                         const float* __restrict__ scale, const float* __restrict__ shift, int B,
+                                                                         int H, int Wd, const float* __restrict__ entry,
+                                                                         int32_t* __restrict__ range_flag, unsigned short* __restrict__ hi,
+                                                                         unsigned short* __restrict__ lo, unsigned* __restrict__ occ_inv) {
+  constexpr int K = C + 6, NCH = PP_CH / 64;
+  __shared__ float4 slabs[PL_WAVES][64 * PL_ROW / 4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float* slab = reinterpret_cast<float*>(slabs[wave]);
+  float w[NCH][K], sc[NCH], sh[NCH];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) {
+    const int c = lane + 64 * j;
+#pragma unroll
+    for (int k = 0; k < K; k++) w[j][k] = W[c * K + k];
+    sc[j] = scale[c];
+    sh[j] = shift[c];
+  }
+  const int M = v3d::pillar_live_rows(*n_ptr, cap);
+  const float s_out = PREC == 1 ? entry[0] : 1.f, limit = PREC == 1 ? entry[2] : 0.f;
+  float vmax = 0.f;
+  for (int base = blockIdx.x * PL_WAVES; base < M; base += gridDim.x * PL_WAVES) {
+    const int m = base + wave;
+    float f[K];
+    const int n = pl_stage<C>(feat, occ, coords, m, M, P, g, slab, f);
+    if (m < M) {
+      float best[NCH];
+      int win[NCH];
+      pl_pillar_max<K, NCH>(slab, n, P, w, sc, sh, best, win);
+      const long long pix = v3d::pillar_plane_pixel(coords + (size_t)m * 4, B, H, Wd);
+      if (pix >= 0) {
+#pragma unroll
+        for (int j = 0; j < NCH; j++) {
+          unsigned short h, l;
+          split_one<PREC>(best[j], s_out, h, l);
+          const size_t o = (size_t)pix * PP_CH + lane + 64 * j;
+          hi[o] = h;
+          lo[o] = l;
+          if constexpr (PREC == 1) vmax = fmaxf(vmax, fabsf(best[j]));
+        }
+        if (lane == 0) atomicAnd(occ_inv + v3d::pillar_occ_word(pix, Wd), ~v3d::pillar_occ_bit(pix, Wd));
+      }
+    }
+    __syncthreads();  // the next pillar's rows overwrite the slab
+  }
+  if constexpr (PREC == 1) {
+    if (range_flag && vmax > limit) atomicMax(range_flag, V3D_FLAG_RANGE);
+  }
+}
+
+__global__ __launch_bounds__(V3D_BLOCK) void pillar_planes_clear_kernel(const int32_t* __restrict__ prev_coords, const int32_t* __restrict__ prev_n,
+                                                                        int cap, int B, int H, int Wd, uint4* __restrict__ hi,
+                                                                        uint4* __restrict__ lo, unsigned* __restrict__ occ_inv,
+                                                                        int32_t* __restrict__ flag) {
+  const long long first = (long long)blockIdx.x * V3D_BLOCK + threadIdx.x, stride = (long long)gridDim.x * V3D_BLOCK;
+  const long long words = (long long)B * H * v3d::pillar_occ_words_per_row(Wd);
+  for (long long t = first; t < words; t += stride) occ_inv[t] = 0xFFFFFFFFu;
+  if (flag && first == 0) *flag = 0;
+  if (!prev_coords) return;
+  const long long total = (long long)v3d::pillar_live_rows(*prev_n, cap) * PP_UNITS;
+  for (long long t = first; t < total; t += stride) {
+    const long long pix = v3d::pillar_plane_pixel(prev_coords + (size_t)(t / PP_UNITS) * 4, B, H, Wd);
+    if (pix < 0) continue;
+    const size_t o = (size_t)pix * PP_UNITS + (size_t)(t % PP_UNITS);
+    hi[o] = make_uint4(0u, 0u, 0u, 0u);
+    lo[o] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+}  // namespace
+
+extern "C" int v3d_pillar_encode_planes(const float* features, const int32_t* occupancy, const int32_t* coordinates, const int32_t* n_voxels,
+                                        int cap, int P, int C, const float* geometry_host, const float* W, int channels, const float* scale,
+                                        const float* shift, int B, int H, int Wd, int prec, const float* act_entry, int32_t* range_flag,
+                                        void* out_hi, void* out_lo, uint32_t* occ, v3d_stream_t stream) {
+  if (cap < 0 || !geometry_host || B < 1 || H < 1 || Wd < 1) return V3D_EINVAL;
+  if (!pl_supported(P, C, channels) || channels != PP_CH) return V3D_EUNSUPPORTED;
+  if (prec == V3D_PREC_F16S ? !act_entry : prec != V3D_PREC_BF16X3) return V3D_EINVAL;
+  if (cap == 0) return V3D_OK;
+  if (!features || !occupancy || !coordinates || !n_voxels || !W || !scale || !shift || !out_hi || !out_lo || !occ) return V3D_EINVAL;
+  const dim3 grid(pl_groups(cap, PL_MAX_ENCODE_GROUPS)), block(V3D_BLOCK);
+  const PillarGeom g = pl_geom(geometry_host);
+  hipStream_t st = (hipStream_t)stream;
+  PL_DISPATCH_C(C, {
+    if (prec == V3D_PREC_F16S)
+      hipLaunchKernelGGL((pillar_encode_planes_kernel<PC, 1>), grid, block, 0, st, features, occupancy, coordinates, n_voxels, cap, P, g, W, scale,
+                         shift, B, H, Wd, act_entry, range_flag, (unsigned short*)out_hi, (unsigned short*)out_lo, occ);
+    else
+      hipLaunchKernelGGL((pillar_encode_planes_kernel<PC, 0>), grid, block, 0, st, features, occupancy, coordinates, n_voxels, cap, P, g, W, scale,
+                         shift, B, H, Wd, (const float*)nullptr, (int32_t*)nullptr, (unsigned short*)out_hi, (unsigned short*)out_lo, occ);
+  });
+  V3D_CHECK_LAUNCH();
+  return V3D_OK;
+}
+
+extern "C" int v3d_pillar_planes_clear(const int32_t* prev_coordinates, const int32_t* prev_n, int cap, int B, int H, int Wd, int channels,
+                                       void* out_hi, void* out_lo, uint32_t* occ, int32_t* flag, v3d_stream_t stream) {
+  if (B < 1 || H < 1 || Wd < 1 || !occ || cap < 0) return V3D_EINVAL;
+  if (channels != PP_CH) return V3D_EUNSUPPORTED;
+  const bool list = prev_coordinates != nullptr && cap > 0;
+  if (list && (!prev_n || !out_hi || !out_lo || ((uintptr_t)out_hi & 15) || ((uintptr_t)out_lo & 15))) return V3D_EINVAL;
+  const long long words = (long long)B * H * v3d::pillar_occ_words_per_row(Wd);
+  const long long work = std::max(words, list ? (long long)cap * PP_UNITS : 0ll);
+  hipLaunchKernelGGL(pillar_planes_clear_kernel, dim3((int)std::min<long long>(v3d_ceil_div(work, (long long)V3D_BLOCK), 2048)), dim3(V3D_BLOCK), 0,
+                     (hipStream_t)stream, list ? prev_coordinates : (const int32_t*)nullptr, prev_n, cap, B, H, Wd, (uint4*)out_hi, (uint4*)out_lo,
+                     occ, flag);
   V3D_CHECK_LAUNCH();
   return V3D_OK;
 }

@@ -15,6 +15,9 @@ the points.
 cfg.PILLAR.DYNAMIC (opt-in; DynamicPillarFeatureNet below): the same layer over the dynamic voxelizer's outputs -- every point of a
 pillar counts, the BatchNorm population is the real points alone.  The key lives in core/config.py (pillar_dynamic_enabled reads it with
 its default, False); PILLAR_DEFAULTS keeps the two keys every pillar configuration has had.
+
+cfg.PILLAR.PLAN (opt-in; core/config.py pillar_plan_enabled): Second's raw-point entry points run on pillar_plan.PillarPlan, which
+reads this module's parameters (linear.weight, _folded()) and writes the dense head's input itself; nothing in this file changes.
 """
 import numpy as np
 import torch

@@ -158,8 +158,11 @@ class Second(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         from .pillar import DynamicPillarFeatureNet, PillarFeatureNet, pillar_enabled
-        from ..core.config import dynamic_voxel_enabled, pillar_dynamic_enabled, refuse_dynamic_with_pillar
+        from ..core.config import dynamic_voxel_enabled, pillar_dynamic_enabled, pillar_plan_enabled, refuse_dynamic_with_pillar
         refuse_dynamic_with_pillar(cfg)
+        # cfg.PILLAR.PLAN (opt-in): the raw-point entry points run on a native plan of the pillar encoder (pillar_plan.PillarPlan) instead
+        # of refusing it; forward / inference on a Preprocessor item stay as they are
+        self.pillar_plan = pillar_plan_enabled(cfg)
         # cfg.DYNAMIC_VOXELIZATION (opt-in): the Preprocessor's items carry voxel_mean over ALL points of a voxel and no `features`; the
         # backbone plans behind the raw-point entry points voxelize the same way (runtime.BackbonePlan)
         self.dynamic_voxels = dynamic_voxel_enabled(cfg)
@@ -193,7 +196,8 @@ class Second(nn.Module):
 
     def _refuse_pillar(self, what):
         from .pillar import refuse_pillar
-        refuse_pillar(self.cfg, what)
+        if not self.pillar_plan:
+            refuse_pillar(self.cfg, what)
 
     def notify_weights_changed(self):
         """Tell the captured-graph runners that parameters / buffers were edited (they check the tensors themselves on their next
@@ -392,6 +396,9 @@ class Second(nn.Module):
         plans = self.__dict__.setdefault("_plans", PlanCache())
         dev = next(self.parameters()).device
         key = (str(dev), int(max_batch), int(max_points)) + ((int(slot),) if slot else ())
+        if key not in plans and self.pillar_plan:  # cfg.PILLAR.PLAN: the encoder's plan presents the same interface
+            from ..pillar_plan import PillarPlan
+            plans[key] = PillarPlan(self.vfe, self.cfg, max_batch=max_batch, max_points=max_points, device=dev, precision=self.precision)
         if key not in plans:
             plans[key] = BackbonePlan(self.cnn, self.cfg, max_batch=max_batch, max_points=max_points, device=dev,
                                       growth=self.__dict__.get("plan_growth", 2.0), precision=self.precision)
